@@ -2,6 +2,7 @@
 """Benchmark of the hot path: D2DEnv.step for a batch of environments on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload stress|default|plugin|hata] [--obs linear|table|none]
+                    [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the fused path over the whole batch: action decode -> SINR / SNR / rate / capacity -> reward
 -> observation table -> LinearObs expansion (reference semantics: obs materialised as [B, N, 6N] in HBM), with fresh
@@ -16,18 +17,27 @@ per step of rewards + the per-step columns of the compact obs table, overlapped 
 --gpus N` - then this process is only a launcher: it starts the N rank processes BEFORE anything touches HIP (it never
 imports torch, never re-execs), waits, and exits non-zero if any rank failed.
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel, HIP-event timed on the library's stream) and
-`cpu_baseline` (the oracle's plain-C restatement timed on this box's host cores on a bounded sample; rank 0, N = 1 only;
-one thread, with the all-core figure and the NumPy oracle's beside it).  Beside `value` and never as it:
+A plain run does only what the headline needs: set up, W warm-up steps, exactly K timed steps, the outputs if
+--dump-outputs is given, one JSON line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = wall ms of
+one timed step).  Its `roofline` is there where the timed steps carry their own HIP events (LinearObs, N > 128).
+--dump-outputs DIR: what the last timed step returned to its caller - obs, rewards, dones and the info arrays of
+VecD2DEnv.step, rank 0's shard - as DIR/<name>.npy in float32 (float64 where the array is float64), 64 MB at most in all:
+an array that does not fit its share is a fixed, seeded sample of its flattened elements (1-D).  Same arguments, same inputs.
+
+--full adds everything else, as below: the ONE JSON line on rank 0 then also has `roofline` for every configuration
+(dominant kernel, HIP-event timed on the library's stream) and `cpu_baseline` (the oracle's plain-C restatement timed on
+this box's host cores on a bounded sample; rank 0, N = 1 only; one thread, with the all-core figure and the NumPy oracle's
+beside it).  Beside `value` and never as it:
   N = 1  `core_mode` (the same envs stepped with the compact-table obs: throughput + the step kernel's roofline block,
          SURVEY.md 8(d); without and with the optional decoded (rb, pwr) planes), `other_workloads` (BASELINE configs 2 and 4
          and an episode loop with the device-side reset, each with its own roofline block), `vec_env_step_ms` (the public
          VecD2DEnv.step against the bare C-ABI handle loop), `box_write_ceiling` / `roofline.box_ceiling_GBs` (the best of a
          family of pure fill kernels on this box), `single_env_step_ms` (the drop-in single-env D2DEnv.step, host dicts in /
          out); `--no-extras` keeps the headline only;
-  N > 1  `rccl_ranks` + all-reduce / all-gather checksums, `value_per_gpu`, `per_rank` (every rank's own ms per step and kernel
-         times), `gather` (bytes per GPU and step, side-stream ms per step, the same steps without the gather, the exposed
-         difference), and `core_mode` with the rewards-only gather plan.
+  N > 1  the same steps without the gather and the exposed difference under `gather`, and `core_mode` with the rewards-only
+         gather plan.
+Every N > 1 line, plain or not, has `rccl_ranks` + all-reduce / all-gather checksums, `value_per_gpu`, `per_rank` (every
+rank's own ms per step and kernel times) and `gather` (bytes per GPU and step, side-stream ms per step).
 """
 import argparse
 import json
@@ -36,6 +46,7 @@ import socket
 import subprocess
 import sys
 import time
+import zlib
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent
@@ -305,7 +316,7 @@ def parse_args(argv=None):
     ap.add_argument('--envs', type=int, default=0, help='override envs per GPU')
     ap.add_argument('--cue-actions', default='', choices=['', 'agent', 'traffic'],
                     help="who drives the CUE links (default: the workload's own choice)")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='N = 1, --full: skip cpu_baseline')
     ap.add_argument('--no-gather', action='store_true', help='N > 1: skip the per-step all-gather')
     ap.add_argument('--gather', default='table', choices=['table', 'rewards', 'planes'],
                     help="N > 1: what the per-step all-gather carries (StepGatherer mode): rewards + the (sinr, snr) columns of the "
@@ -319,12 +330,17 @@ def parse_args(argv=None):
     ap.add_argument('--with-reset', action='store_true', help='redraw all device positions every 10 steps (device-side reset)')
     ap.add_argument('--force-dist', action='store_true', help='init RCCL and run the gather path even with one rank (test hook)')
     ap.add_argument('--no-single-env-latency', action='store_true',
-                    help='N = 1 also times the drop-in single-env D2DEnv.step (host dicts in / out); this skips it')
+                    help='N = 1, --full also times the drop-in single-env D2DEnv.step (host dicts in / out); this skips it')
     ap.add_argument('--rank-timeout', type=float, default=1500.0,
                     help='N > 1, self-launched ranks: seconds after which the launcher terminates its children and exits 124 '
                          '(0 = no deadline)')
     ap.add_argument('--no-extras', action='store_true',
-                    help='N = 1, default run: skip other_workloads / vec_env_step_ms / the write-ceiling probe (the headline only)')
+                    help='N = 1, --full: skip other_workloads / vec_env_step_ms / the write-ceiling probe')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beside the headline: cpu_baseline, single_env_step_ms, core_mode, other_workloads, '
+                         'the roofline pass of one-kernel steps, the N > 1 steps without the gather (a plain run times the headline only)')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='write what the last timed step returned (obs, rewards, dones, info; rank 0) as DIR/<name>.npy, 64 MB at most')
     ap.add_argument('--no-export', action='store_true',
                     help='d2d_set_export_actions(0) for the measured session: no decoded (rb, pwr) planes (a rollout knows its actions)')
     ap.add_argument('--reward-per-env', action='store_true',
@@ -435,7 +451,7 @@ class Session:
             new_episode = with_reset and k % 10 == 0
             if new_episode:                              # EPISODE_LENGTH = 10 (d2d_env.py:16): new layout per episode
                 h.reset_positions(1234, k // 10)
-            step(actions[k % self.pool])
+            self.last = step(actions[k % self.pool])     # what the caller receives (views of the env's buffers): --dump-outputs
             planes = getattr(self, 'planes_gather', None)
             if gatherer is not None and (new_episode or k == 0):
                 # position columns only change at reset (not per step); planes plan: the library's own link rows
@@ -450,8 +466,10 @@ class Session:
         if gatherer is not None:
             gatherer.wait()
 
-    def timed(self, fence, gatherer=None, with_reset=False):
-        """W untimed steps, then exactly K steps between two fences (barrier + device synchronise on both sides)."""
+    def timed(self, fence, gatherer=None, with_reset=False, grouped=True, after=None):
+        """W untimed steps, then exactly K steps between two fences (barrier + device synchronise on both sides).
+        after(): called once the timed steps are done, before anything else runs on the env.  grouped: the second pass
+        that times one-kernel steps in groups (the roofline of a configuration without events in its timed region)."""
         torch, h = self.torch, self.h
         self.run(0, self.warmup, gatherer, with_reset)
         fence()
@@ -468,7 +486,9 @@ class Session:
         step_med = h.profile_median(0) if self.events_in_timed and not self.stub else 0.0
         obs_med = h.profile_median(1) if self.events_in_timed and not self.stub else 0.0
         h.profile_enable(False)
-        if not self.events_in_timed and not self.stub:
+        if after is not None:
+            after()
+        if grouped and not self.events_in_timed and not self.stub:
             stream = torch.cuda.current_stream(self.dev)          # VecD2DEnv runs the library's kernels on this stream
             pairs = []
             for k0 in range(self.warmup, self.total, GROUP):
@@ -580,6 +600,65 @@ def summarise(sess, t, steps, world=1):
             'roofline': sess.roofline(t)}
 
 
+DUMP_LIMIT = 64_000_000      # --dump-outputs: bytes of all the .npy files together, headers included
+DUMP_MIN_SHARE = 4_000_000   # ... of which every array keeps this much (or an equal share, if less) for itself
+DUMP_SEED = 20261016
+
+
+def _output_arrays(result):
+    """(name, array) for every array in what VecD2DEnv.step returned: (obs, rewards, dones, info); None entries are skipped."""
+    items = []
+
+    def add(name, a):
+        if a is None:
+            return
+        if isinstance(a, dict):
+            for k, v in a.items():
+                add(f'{name}_{k}', v)
+        elif isinstance(a, (tuple, list)):
+            for k, v in enumerate(a):
+                add(f'{name}_{k}', v)
+        else:
+            items.append((name, a))
+    obs, rewards, dones, info = result
+    for name, a in (('obs', obs), ('reward', rewards), ('dones', dones), ('info', info)):
+        add(name, a)
+    return items
+
+
+def dump_outputs(torch, result, out_dir):
+    """--dump-outputs: every array of `result` as out_dir/<name>.npy, float64 where it is float64 and float32 otherwise.
+    The smallest arrays are written first, each whole where it fits what is left of DUMP_LIMIT after the larger ones have
+    been promised DUMP_MIN_SHARE each; an array that does not is written as a sample of its flattened elements, drawn from a
+    generator seeded by DUMP_SEED and its name (sorted flat indices, duplicates dropped): the same shapes give the same
+    sample in every run.  The stress workload: obs is sampled (1.3M of its 6.4G elements), everything else is whole."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    items = []
+    for name, a in _output_arrays(result):
+        if torch.is_tensor(a):
+            f64, numel = a.dtype == torch.float64, int(a.numel())
+        else:
+            a = np.asarray(a)
+            f64, numel = a.dtype == np.float64, int(a.size)
+        items.append((name, a, np.dtype(np.float64 if f64 else np.float32), numel))
+    items.sort(key=lambda it: it[3] * it[2].itemsize)
+    left = DUMP_LIMIT
+    for k, (name, a, dt, numel) in enumerate(items):
+        rest = len(items) - k - 1                                                  # larger arrays still to come
+        room = left - rest * min(left // (rest + 1), DUMP_MIN_SHARE)
+        keep = min(numel, (room - 256) // dt.itemsize)                             # 256: room for the .npy header
+        if keep < numel:
+            rng = np.random.default_rng([DUMP_SEED, zlib.crc32(name.encode())])
+            idx = np.unravel_index(np.unique(rng.integers(0, numel, keep, dtype=np.int64)), tuple(a.shape))
+            a = a[tuple(torch.from_numpy(i).to(a.device) for i in idx)] if torch.is_tensor(a) else a[idx]
+        host = a.detach().cpu().numpy() if torch.is_tensor(a) else a
+        path = out_dir / f'{name}.npy'
+        np.save(path, np.ascontiguousarray(host, dtype=dt))
+        left -= path.stat().st_size
+    assert left >= 0, left
+
+
 def worker(args):
     import torch
     rank = int(os.environ.get('RANK', 0))
@@ -599,8 +678,10 @@ def worker(args):
 
     # the CPU baseline runs first: this process has not initialised HIP yet, so its fork()ed pool is safe
     cpu = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline and not stub:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline and not stub:
         cpu = cpu_baseline(w)
+    if args.dump_outputs and stub:
+        raise SystemExit('--dump-outputs: the CPU stub computes nothing to dump')
 
     # stdout carries exactly ONE line (the JSON): RCCL prints a version banner to fd 1 when its first communicator is
     # created, so everything until the result is ready goes to stderr instead
@@ -633,7 +714,7 @@ def worker(args):
     # number, never as `value`; timed before the batch env exists so its 26 GB of buffers are not in the picture.
     c, p, r = w['cues'], w['dues'], w['rbs']
     single_ms = None
-    if rank == 0 and world == 1 and not args.no_single_env_latency and not stub:
+    if args.full and rank == 0 and world == 1 and not args.no_single_env_latency and not stub:
         single_ms = {'25 CUE + 25 DUE pairs, 25 RB (reference default env)': single_env_latency(25, 25, 25, local)}
         if (c, p, r) != (25, 25, 25):
             single_ms[f'{c} CUE + {p} DUE pairs, {r} RB'] = single_env_latency(c, p, r, local)
@@ -663,7 +744,8 @@ def worker(args):
         args.gather = 'planes'                 # no table exists in the obs-less mode: the (sinr, snr) planes travel instead (same bytes)
     gatherer = make_gatherer(args.gather, args.signal_every) if use_dist and not args.no_gather else None
     total_steps = args.steps + args.warmup                    # launches the gatherer sees in the timed run (warm-up included)
-    t = sess.timed(fence, gatherer, args.with_reset)
+    dump = (lambda: dump_outputs(torch, sess.last, args.dump_outputs)) if args.dump_outputs and rank == 0 else None
+    t = sess.timed(fence, gatherer, args.with_reset, grouped=args.full, after=dump)
     flags = sess.env.status_flags()
     gather_ms = gatherer.gather_ms() if gatherer is not None else None
     # evidence that the collective saw every rank: a count all-reduce, and the last step's rewards summed two ways
@@ -692,14 +774,14 @@ def worker(args):
                 dist_info['checksums_note'] = ('the last step is not the end of a gathered reward block (steps + warmup is not a multiple of '
                                                '--reward-every): nothing to compare')
     # what the gather costs the step loop: the same steps again without it
-    t_nogather = sess.timed(fence, None, args.with_reset) if gatherer is not None else None
+    t_nogather = sess.timed(fence, None, args.with_reset) if gatherer is not None and args.full else None
 
     # report the 'core' mode beside the with-obs mode.  Same envs, same actions, obs_fn swapped for the
     # compact table (what a learner that builds its own features consumes): the step is then the step kernel alone.
     # The decoded (rb, pwr) planes behind info['rb'] / info['tx_pwr_dbm'] are a rollout's own actions again: the entry is
     # measured without them (d2d_set_export_actions(0), 64 algorithmic bytes per link) and, beside it, with them.
     core = None
-    if not stub and sess.obs == 'linear' and not sess.f64 and n > 128 and (world == 1 or not args.no_gather):
+    if args.full and not stub and sess.obs == 'linear' and not sess.f64 and n > 128 and (world == 1 or not args.no_gather):
         core = core_mode(torch, sess, dev, args, fence, use_dist, world, make_gatherer)
 
     dt = t['dt']
@@ -717,20 +799,23 @@ def worker(args):
                                   'obs_expand_kernel_ms': float(row[2]) or None, 'gather_ms_per_step': float(row[3]) or None}
                                  for k, row in enumerate(every.cpu())]
         if gatherer is not None:
-            tn = torch.tensor([t_nogather['dt']], device=dev, dtype=torch.float64)
-            dist.all_reduce(tn, op=dist.ReduceOp.MAX)
             dist_info['gather'] = {
                 'mode': args.gather, 'signal_every': args.signal_every, 'reward_every': gatherer.reward_every, 'backend': gatherer.backend,
                 'bytes_per_gpu_per_step': gatherer.bytes_per_signal_launch if args.signal_every == 1 else
                 gatherer.bytes_per_launch + (gatherer.bytes_per_signal_launch - gatherer.bytes_per_launch) / args.signal_every,
                 'gather_ms_per_step': gather_ms,                                   # side-stream events, rank 0
+                'timing': 'HIP events on the gather side stream around (staging copies + all-gathers) of every launch'}
+        if t_nogather is not None:
+            tn = torch.tensor([t_nogather['dt']], device=dev, dtype=torch.float64)
+            dist.all_reduce(tn, op=dist.ReduceOp.MAX)
+            dist_info['gather'].update({
                 'ms_per_step_without_gather': float(tn.item()) / args.steps * 1e3,  # max over ranks
                 'gather_exposed_ms': (dt - float(tn.item())) / args.steps * 1e3,    # what the step loop pays for it
                 'timing': 'HIP events on the gather side stream around (staging copies + all-gathers) of every launch; exposed = '
-                          'ms_per_step with the gather minus the same steps without it'}
+                          'ms_per_step with the gather minus the same steps without it'})
 
     extras = {}
-    if rank == 0 and world == 1 and not stub and not args.no_extras and args.workload == 'stress' and args.obs == 'linear' \
+    if args.full and rank == 0 and world == 1 and not stub and not args.no_extras and args.workload == 'stress' and args.obs == 'linear' \
             and not args.envs and not args.tune and not sess.f64:
         sess.close()
         extras = n1_extras(torch, args, dev, local, fence)
@@ -769,6 +854,9 @@ def worker(args):
             out['stub'] = 'CPU plumbing test - not a measurement'
         if args.share_gpu:
             out['shared_gpu'] = f'{world} ranks on ONE GPU over gloo: multi-rank correctness test - not a measurement'
+        if not (args.full or sess.events_in_timed or stub):      # no kernel times: the grouped pass is --full's
+            for k in ('roofline', 'kernels'):
+                del out[k]
         if single_ms is not None:
             out['single_env_step_ms'] = single_ms
         if core is not None:
@@ -804,7 +892,7 @@ def worker(args):
         if cpu is not None:
             out['cpu_baseline'] = cpu
         elif world > 1:
-            out['cpu_baseline'] = 'N=1 line only (the CPU port is timed on rank 0 of the one-GPU run)'
+            out['cpu_baseline'] = 'N=1 line only (the CPU port is timed on rank 0 of the one-GPU run with --full)'
         sys.stdout.flush()
         os.dup2(saved_stdout, 1)                 # the real stdout is back for the one line that belongs there
         print(json.dumps(out), flush=True)

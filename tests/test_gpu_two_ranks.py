@@ -125,7 +125,7 @@ def test_bench_two_ranks_on_one_gpu_agree_with_one_rank_of_twice_the_envs():
     import json
     import subprocess
     cmd = [sys.executable, str(ROOT / 'bench.py'), '--gpus', '2', '--share-gpu', '--workload', 'default', '--obs', 'table',
-           '--envs', '64', '--steps', '4', '--warmup', '1', '--no-cpu-baseline', '--no-single-env-latency']
+           '--envs', '64', '--steps', '4', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-single-env-latency']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600,
                        env={k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK')})
     assert r.returncode == 0, r.stderr[-3000:]
@@ -157,7 +157,7 @@ def test_bench_two_ranks_headline_shape_with_core_mode_gathers():
     import json
     import subprocess
     cmd = [sys.executable, str(ROOT / 'bench.py'), '--gpus', '2', '--share-gpu', '--envs', '16', '--steps', '8', '--warmup', '2',
-           '--no-cpu-baseline', '--no-single-env-latency']
+           '--full', '--no-cpu-baseline', '--no-single-env-latency']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900,
                        env={k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK')})
     assert r.returncode == 0, r.stderr[-3000:]
@@ -196,7 +196,7 @@ def test_bench_native_gather_backend_with_one_rank():
     import json
     import subprocess
     cmd = [sys.executable, str(ROOT / 'bench.py'), '--gpus', '1', '--force-dist', '--gather-backend', 'native', '--envs', '64',
-           '--steps', '4', '--warmup', '1', '--reward-every', '2', '--no-cpu-baseline', '--no-single-env-latency']
+           '--steps', '4', '--warmup', '1', '--reward-every', '2', '--full', '--no-cpu-baseline', '--no-single-env-latency']
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600,
                        env={k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK')})
     assert r.returncode == 0, r.stderr[-3000:]

@@ -25,7 +25,7 @@ bash tools/profile_bench.sh $tag hata table 1000 --no-export > $O/prof_hata_tabl
 for args in "" "--workload default" "--workload plugin" "--obs table --no-export" "--obs table" \
             "--obs none --no-export --reward-per-env" "--obs-dtype float64 --steps 30" \
             "--workload hata --obs none --no-export --reward-per-env" "--workload hata --obs table --no-export"; do
-  extra="--no-cpu-baseline --no-single-env-latency --no-extras"; [ -z "$args" ] && extra=""
+  extra="--full --no-cpu-baseline --no-single-env-latency --no-extras"; [ -z "$args" ] && extra="--full"
   timeout 1200 python bench.py $args $extra 2>> $O/bench.err | tail -1 >> profiles/${tag}_bench_lines.jsonl
 done
 python3 - "$tag" <<'PY'

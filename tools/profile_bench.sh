@@ -9,7 +9,7 @@ out=$R/gpurun_out/prof_${tag}_${wl}_${obs}${sfx:+_$sfx}
 mkdir -p $out
 cd /tmp; export TMPDIR=/tmp
 wu=10; [ "$steps" -gt 500 ] && wu=$((steps / 2))      # short kernels: long enough to be past the clock ramp behind an idle stretch
-args="--workload $wl --obs $obs --no-cpu-baseline --no-single-env-latency --no-extras $extra"
+args="--workload $wl --obs $obs --full --no-cpu-baseline --no-single-env-latency --no-extras $extra"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt -- python3 $R/bench.py $args --steps $steps --warmup $wu > $out/kt.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/pmc_write -- python3 $R/bench.py $args --steps 5 --warmup 1 > $out/pmc_write.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch -- python3 $R/bench.py $args --steps 5 --warmup 1 > $out/pmc_fetch.log 2>&1
