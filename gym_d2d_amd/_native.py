@@ -1,5 +1,5 @@
-"""ctypes binding of libd2d_hip.so (include/d2d_hip.h).  There is no CPU fallback: if the library or a
-gfx950 GPU is missing, the calls below raise."""
+"""ctypes binding of libd2d_hip.so (include/d2d_hip.h) and libd2d_plugin.so (include/d2d_plugin.h).  There is no CPU
+fallback: if a library or a gfx950 GPU is missing, the calls below raise."""
 from __future__ import annotations
 
 import ctypes as C
@@ -9,7 +9,8 @@ from typing import Optional
 import numpy as np
 
 LIB_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_hip.so'
-ABI_VERSION = 5
+PLUGIN_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_plugin.so'
+ABI_VERSION = 6
 MAX_LINKS = 2048
 
 # d2d_status
@@ -23,7 +24,9 @@ OBS_NONE, OBS_TABLE, OBS_LINEAR = 0, 1, 2
 # d2d_buffer
 (BUF_POS_X, BUF_POS_Y, BUF_ACTIONS, BUF_RB, BUF_PWR, BUF_SINR_DB, BUF_SNR_DB, BUF_RATE_BPS, BUF_CAPACITY,
  BUF_REWARD, BUF_OBS_TABLE, BUF_OBS, BUF_ENV_FLAGS, BUF_LINK_POS, BUF_REWARD_ENV, BUF_COUNT) = range(16)
-FLAG_ZERO_DISTANCE, FLAG_RB_OUT_OF_RANGE, FLAG_NON_FINITE = 1, 2, 4
+FLAG_ZERO_DISTANCE, FLAG_RB_OUT_OF_RANGE, FLAG_NON_FINITE, FLAG_PATH_LOSS_DOMAIN = 1, 2, 4, 8
+# d2d_set_path_loss_link_table_dev's per_env: 0 [N,N], 1 [B,N,N] (converted once), PL_TABLE_LIVE [B,N+1,N] (bound, read every step)
+PL_TABLE_LIVE = 2
 # d2d_tuning (TUNE_OBS_VARIANT, TUNE_STEP_ABLATE, TUNE_OBS_STAGGER: include/d2d_hip_diag.h, diagnostic builds only)
 (TUNE_OBS_ROWS_PER_WG, TUNE_OBS_NONTEMPORAL, TUNE_OBS_XCD_REMAP, TUNE_OBS_BLOCK, TUNE_OBS_VARIANT,
  TUNE_STEP_THREADS, TUNE_STEP_ENVS_PER_WG, TUNE_STEP_BLOCK, TUNE_STEP_FUSE_OBS, TUNE_STEP_ABLATE,
@@ -113,7 +116,14 @@ SIGNATURES = {
     'd2d_profile_median': (C.c_int, [_P, _I, C.POINTER(C.c_double)]),
 }
 
+# every symbol include/d2d_plugin.h declares
+PLUGIN_SIGNATURES = {
+    'd2d_plugin_normal': (C.c_int, [_P, _I, C.c_int64, C.c_uint64, _I, _I, C.c_uint64, _I, C.c_uint64, _P]),
+    'd2d_plugin_last_error': (C.c_char_p, []),
+}
+
 _lib: Optional[C.CDLL] = None
+_plugin: Optional[C.CDLL] = None
 
 
 def load_library() -> C.CDLL:
@@ -133,6 +143,32 @@ def load_library() -> C.CDLL:
         raise ImportError('libd2d_hip.so ABI version mismatch - rebuild it')
     _lib = lib
     return lib
+
+
+def load_plugin_library() -> C.CDLL:
+    """dlopen libd2d_plugin.so and type its entry points.  Raises if it has not been built."""
+    global _plugin
+    if _plugin is not None:
+        return _plugin
+    if not PLUGIN_PATH.exists():
+        raise ImportError(f'{PLUGIN_PATH} is missing - build it with `python -m gym_d2d_amd.build`')
+    lib = C.CDLL(str(PLUGIN_PATH))
+    for name, (res, args) in PLUGIN_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    _plugin = lib
+    return lib
+
+
+def plugin_normal(out_ptr: int, dtype: int, n_envs: int, first_env: int, n_rows: int, n_cols: int, step: int, kind: int,
+                  seed: int, stream_ptr: int = 0) -> None:
+    """d2d_plugin_normal: standard normals of the built-in shadowing stream into device memory [n_envs, n_rows, n_cols]."""
+    lib = load_plugin_library()
+    rc = lib.d2d_plugin_normal(_P(out_ptr), dtype, n_envs, C.c_uint64(first_env), n_rows, n_cols, C.c_uint64(step & (2 ** 64 - 1)),
+                               kind, C.c_uint64(seed & (2 ** 64 - 1)), _P(stream_ptr or None))
+    if rc != 0:
+        raise NativeError(rc, lib.d2d_plugin_last_error().decode(errors='replace'))
 
 
 def _check(rc: int) -> None:
@@ -210,8 +246,9 @@ class Handle:
             raise ValueError(f'link path-loss table must be [N,N] or [{self.num_envs},N,N], got {t.shape}')
         _check(self._lib.d2d_set_path_loss_link_table(self._h, _dptr(t), n, int(t.ndim == 3)))
 
-    def set_path_loss_link_table_dev(self, dev_ptr: int, dtype: int, n_links: int, per_env: bool) -> None:
-        """The link table from DEVICE memory (float32 / float64 dB, [N,N] or [B,N,N]): converted to gains by a kernel, no host copy."""
+    def set_path_loss_link_table_dev(self, dev_ptr: int, dtype: int, n_links: int, per_env) -> None:
+        """The link table from DEVICE memory (float32 / float64 dB, [N,N] or [B,N,N]): converted to gains by a kernel, no host copy.
+        per_env = PL_TABLE_LIVE binds a [B,N+1,N] table instead, read in place by every later step."""
         _check(self._lib.d2d_set_path_loss_link_table_dev(self._h, _P(dev_ptr), dtype, n_links, int(per_env)))
 
     def set_links(self, tx_dev, rx_dev, link_type) -> None:
@@ -323,6 +360,7 @@ class Handle:
 
     def set_env_offset(self, first_env: int) -> None:
         _check(self._lib.d2d_set_env_offset(self._h, C.c_uint64(first_env)))
+        self.env_offset = int(first_env)
 
     # -- hot path
     def step(self, actions_ptr: int = 0) -> None:

@@ -92,6 +92,8 @@ struct d2d_handle {
     size_t gain_elems = 0;
     int table_per_env = 0;
     int table_links = 0;            // > 0: gain_table is [B or 1][n][n] by (tx LINK, rx LINK) of that link list (d2d_set_path_loss_link_table)
+    const void* live_table = nullptr;   // D2D_PL_TABLE_LIVE: the caller's [B][n+1][n] dB table, read in place by every step (never freed here)
+    int live_f64 = 0;
     unsigned* status = nullptr;
     // host-side copies used to derive the device columns
     std::vector<double> eirp_off, rx_off, noise, sens, bw, a_tx, a_rx, expo;
@@ -175,16 +177,16 @@ int refresh_tables(d2d_handle* h) {
     std::vector<float> cols((size_t)7 * D);
     bool all_two = true;
     for (int d = 0; d < D; ++d) {
-        const double a_tx = h->mode == d2d::PL_TABLE ? 0.0 : h->a_tx[d];
-        const double a_rx = h->mode == d2d::PL_TABLE ? 0.0 : h->a_rx[d];
+        const double a_tx = d2d::pl_is_table(h->mode) ? 0.0 : h->a_tx[d];
+        const double a_rx = d2d::pl_is_table(h->mode) ? 0.0 : h->a_rx[d];
         cols[0 * D + d] = (float)std::pow(10.0, (h->eirp_off[d] - a_tx) / 10.0);
         cols[1 * D + d] = (float)std::pow(10.0, -a_rx / 10.0);
         cols[2 * D + d] = (float)std::pow(10.0, h->rx_off[d] / 10.0);
         cols[3 * D + d] = (float)std::pow(10.0, h->noise[d] / 10.0);
         cols[4 * D + d] = (float)h->sens[d];
         cols[5 * D + d] = (float)(1e-6 * h->bw[d]);
-        cols[6 * D + d] = h->mode == d2d::PL_TABLE ? 2.0f : (float)h->expo[d];
-        if (h->mode != d2d::PL_TABLE && h->expo[d] != 2.0) all_two = false;
+        cols[6 * D + d] = d2d::pl_is_table(h->mode) ? 2.0f : (float)h->expo[d];
+        if (!d2d::pl_is_table(h->mode) && h->expo[d] != 2.0) all_two = false;
         // The kernels work in linear float32 (mW and plain gain factors): a link-budget constant beyond about +-300 dB
         // (COST-Hata's mobile-height correction applied to a receiving antenna above ~100 m, path_loss.py:105-112) leaves that range
         // and would surface as inf / NaN results.  Refused here, by name, instead.
@@ -195,7 +197,7 @@ int refresh_tables(d2d_handle* h) {
                                                  " (tx_lin, rx_pl, rx_lin, noise_mw) is outside the float32 linear range 1e-30 .. 1e30 (a term beyond +-300 dB)");
         }
     }
-    if (h->mode != d2d::PL_TABLE && h->mode != d2d::PL_SHADOW) {
+    if (!d2d::pl_is_table(h->mode) && h->mode != d2d::PL_SHADOW) {
         h->mode = all_two ? d2d::PL_INV_SQUARE : d2d::PL_POWER;
         // PL_POWK: the exponents of the transmitters of the CURRENT links all lie within 1/2 of one integer k in 1 .. 8 (COST-Hata's
         // 3.6 / 4.375, a log-distance ple of 3.5: k = 4) - then (d^2)^(-n/2) = (d^2)^(-k/2) (d^2)^phi with |phi| <= 1/4, and the
@@ -259,7 +261,7 @@ int refresh_tables(d2d_handle* h) {
             rech[2 * i + 1] = 0.0f;
             continue;
         }
-        const double hd = h->mode == d2d::PL_TABLE ? -1.0 : -0.5 * h->expo[h->host_tx[i]];
+        const double hd = d2d::pl_is_table(h->mode) ? -1.0 : -0.5 * h->expo[h->host_tx[i]];
         float head = (float)hd;
         uint32_t hb;
         std::memcpy(&hb, &head, 4); hb &= 0xFFFFF000u; std::memcpy(&head, &hb, 4);
@@ -665,6 +667,12 @@ int run_step(d2d_handle* h, int action_mode, const int32_t* a0, const int32_t* a
     s.table_by_link = h->table_links > 0;
     s.table_pitch = h->table_links > 0 ? h->table_links : D;
     s.table_env_stride = h->table_per_env ? (long long)s.table_pitch * s.table_pitch : 0;
+    if (h->mode == d2d::PL_TABLE_DB) {               // the live dB table: [B][N+1][N], the entry width in table_by_link
+        s.gain_table = static_cast<const float*>(h->live_table);
+        s.table_by_link = h->live_f64 ? 2 : 1;
+        s.table_pitch = N;
+        s.table_env_stride = (long long)(N + 1) * N;
+    }
     s.env_offset = h->env_offset;
     if (h->mode == d2d::PL_SHADOW) {
         s.shadow_chi = (float)h->shadow_chi;
@@ -884,6 +892,7 @@ int d2d_set_path_loss_power_law(d2d_handle* h, int32_t n_dev, const double* a_tx
     h->a_tx.assign(a_tx_db, a_tx_db + n_dev);
     h->a_rx.assign(a_rx_db, a_rx_db + n_dev);
     h->expo.assign(exponent, exponent + n_dev);
+    h->live_table = nullptr;
     h->mode = d2d::PL_POWER;   // refined to PL_INV_SQUARE in refresh_tables when every exponent is 2
     h->have_pl = true; h->tables_dirty = true;
     return D2D_OK;
@@ -907,8 +916,9 @@ namespace {
 // From the first byte a new table overwrites until it is complete, the handle has NO table: a failed allocation or copy must not
 // leave PL_TABLE selected over a null or half-written one (the next step then fails with D2D_ERR_STATE instead of faulting).
 void gain_table_invalid(d2d_handle* h) {
-    if (h->mode == d2d::PL_TABLE) h->have_pl = false;
+    if (d2d::pl_is_table(h->mode)) h->have_pl = false;
     h->table_links = 0;
+    h->live_table = nullptr;
     h->tables_dirty = true;
 }
 
@@ -972,9 +982,30 @@ int d2d_set_path_loss_table(d2d_handle* h, const double* pl_db, int32_t per_env)
 int d2d_set_path_loss_link_table_dev(d2d_handle* h, const void* pl_db_dev, int32_t dtype, int32_t n_links, int32_t per_env) try {
     if (!h || !pl_db_dev) return fail(D2D_ERR_INVALID, "null argument");
     if (dtype != D2D_F32 && dtype != D2D_F64) return fail(D2D_ERR_INVALID, "dtype must be D2D_F32 or D2D_F64");
+    if (per_env < 0 || per_env > D2D_PL_TABLE_LIVE) return fail(D2D_ERR_INVALID, "per_env must be 0, 1 or D2D_PL_TABLE_LIVE");
     USE_DEVICE(h);
     if (!h->have_links) return fail(D2D_ERR_STATE, "d2d_set_links first: the table is indexed by its link list");
     if (n_links != h->N || n_links < 1) return fail(D2D_ERR_INVALID, "n_links must be the length of the current link list (" + std::to_string(h->N) + ")");
+    // Every pointer is checked before anything is launched on it: device (or managed) memory of this handle's device, or refused.
+    {
+        hipPointerAttribute_t attr;
+        const hipError_t e = hipPointerGetAttributes(&attr, pl_db_dev);
+        if (e != hipSuccess) (void)hipGetLastError();              // an unknown host pointer: the query's error is not sticky
+        if (e != hipSuccess || (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged) ||
+            attr.device != h->cfg.device_ordinal)
+            return fail(D2D_ERR_INVALID, "pl_db_dev must be device or managed memory on device " + std::to_string(h->cfg.device_ordinal));
+    }
+    if (per_env == D2D_PL_TABLE_LIVE) {
+        // bound, not copied: every later step reads the entries it uses from the caller's [B][n+1][n] table, in stream order
+        gain_table_invalid(h);
+        h->live_table = pl_db_dev;
+        h->live_f64 = dtype == D2D_F64;
+        h->table_per_env = 1;
+        h->table_links = n_links;
+        h->mode = d2d::PL_TABLE_DB;
+        h->have_pl = true; h->tables_dirty = true;
+        return D2D_OK;
+    }
     const size_t elems = (size_t)n_links * n_links * (per_env ? (size_t)h->B : 1);
     int rc = reserve_gain_table(h, elems);
     if (rc) return rc;
@@ -1024,9 +1055,10 @@ int d2d_set_links(d2d_handle* h, int32_t n_links, const int32_t* tx_dev, const i
     h->tables_dirty = true;          // the per-link records follow the link table (uploaded by the next step)
     h->lpos_dirty = true;
     h->have_links = true;
-    if (h->table_links) {            // a table indexed by the OLD link list: gone with it
+    if (h->table_links) {            // a table indexed by the OLD link list (or a live binding): gone with it
         h->table_links = 0;
-        if (h->mode == d2d::PL_TABLE) h->have_pl = false;
+        h->live_table = nullptr;
+        if (d2d::pl_is_table(h->mode)) h->have_pl = false;
     }
     return D2D_OK;
 } D2D_CATCH

@@ -11,11 +11,16 @@ enum PlMode : int {
     PL_POWER = 1,        // per-tx exponent (ple != 2, COST-Hata): gain = k * (d^2)^(-e/2)
     PL_TABLE = 2,        // host-evaluated [D,D] (or [B,D,D]) linear gain table
     PL_SHADOW = 3,       // PL_POWER + log-normal shadowing beyond d0, fresh Philox Gaussian per evaluation
-    PL_POWK = 4          // PL_POWER where the exponent of every link's transmitter lies within 1/2 of ONE integer k (StepArgs::pow_k;
+    PL_POWK = 4,         // PL_POWER where the exponent of every link's transmitter lies within 1/2 of ONE integer k (StepArgs::pow_k;
                          // COST-Hata's 3.6 / 4.375: k = 4): gain = (d^2)^(-k/2) by reciprocals and products, times (d^2)^phi,
                          // phi = -(n - k) / 2 in [-1/4, 1/4] - three transcendentals and four products per pair instead of the
                          // general split's two and fourteen (pow_k_gains, d2d_step_device.h)
+    PL_TABLE_DB = 5      // live dB table by (tx link, rx link) in caller memory (D2D_PL_TABLE_LIVE), [B][N+1][N]: row N holds the SNR's own
+                         // evaluation of the signal path; each entry the step reads is converted where it is read (table_gain_db)
 };
+
+// the table-driven modes: no device constants in the records, no power law
+__host__ __device__ constexpr bool pl_is_table(int mode) { return mode == PL_TABLE || mode == PL_TABLE_DB; }
 
 // Per-link record, three 16-byte rows shared by all envs and read coalesced by link index (L2-resident).  Built on
 // the host from the per-device columns + the link table whenever links, tables or fixed actions change.
@@ -87,8 +92,10 @@ struct StepArgs {
                              // OPT_XPOS form every difference as (tx_hi - rx_hi) + (tx_lo - rx_lo): exact to ~1e-7 of the DIFFERENCE
                              // where float32 absolute coordinates carry 3e-5 m at 500 m (position.py:11-12 works in Python floats)
     const float* gain_table; // PL_TABLE: linear gain, tx major: [D,D] by (tx device, rx device), or [N,N] by (tx link, rx link)
-    long long table_env_stride; // 0 or pitch * pitch
+                             // PL_TABLE_DB: the caller's dB table (float32 or float64 per table_by_link), [B][N+1][N]
+    long long table_env_stride; // 0 or pitch * pitch (PL_TABLE_DB: (N + 1) * N entries)
     int table_by_link;       // rows / columns are link indices (d2d_set_path_loss_link_table), else device indices
+                             // (PL_TABLE_DB: 1 = float32 dB entries, 2 = float64)
     int table_pitch;         // row length: N or D
     // PL_SHADOW (ShadowingPathLoss, path_loss.py:69-81)
     float shadow_chi;        // std of the shadowing term, dB

@@ -126,13 +126,17 @@ __global__ __launch_bounds__(1024) void step_kernel(const StepArgs a) {
     constexpr bool POWLAW = MODE == PL_POWER || MODE == PL_SHADOW || MODE == PL_POWK;   // per-link exponents (rec_h, LDS expo[])
     // a zero distance shows as a non-finite gain (1 / d^2, and PL_POWK's reciprocal): no smallest-distance tracking per pair
     constexpr bool NF_ONLY = MODE == PL_INV_SQUARE || MODE == PL_POWK;
+    // PL_TABLE_DB converts every entry it reads with a double exp2 (a dozen 64-bit constants): one copy per loop, not one per
+    // unrolled iteration, keeps its strided kernels' scalars out of lanes (the other modes keep their unrolling)
+    constexpr int LIST_UNROLL = MODE == PL_TABLE_DB ? 1 : LIST_SLOTS - 1;
+    constexpr int PAIR_UNROLL = MODE == PL_TABLE_DB ? 1 : 4;
     const int cfg_action_mode = HOT ? 0 : a.action_mode;
     const int cfg_col_mode = HOT ? 0 : a.col_mode;
     const int cfg_reward_fn = HOT ? 1 : a.reward_fn;
     const int cfg_write_table = HOT == 2 ? 1 : a.write_table;     // HOT 1 serves D2D_OBS_TABLE and D2D_OBS_NONE (one uniform branch around three stores)
     // (the flattened walk is an A/B shape of the power-law kernels: the table / shadowing kernels, whose pair evaluation is
     // hundreds of instructions, carry the nested one only)
-    const int cfg_walk = (HOT || LISTS || MODE == PL_SHADOW || MODE == PL_TABLE) ? 0 : a.walk;
+    const int cfg_walk = (HOT || LISTS || MODE == PL_SHADOW || pl_is_table(MODE)) ? 0 : a.walk;
     const bool cfg_export_actions = a.rb_out != nullptr;          // the info dict's rb / tx_pwr_dbm (d2d_set_export_actions)
     extern __shared__ __align__(16) unsigned char smem_raw[];
     const int N = a.N, R = a.R, D = a.D, W = a.mask_words, TPE = a.tpe;
@@ -212,7 +216,7 @@ __global__ __launch_bounds__(1024) void step_kernel(const StepArgs a) {
         if (LPT == 0) s.rx[i] = make_float2(in.pos.z, in.pos.w);
         // tx_dev | link_type << 24 (HOT: only the cold all-pairs route wants the type, and reads it from the record); the low bits
         // are the transmitter's ROW in the gain table: its device, or - a table by (tx link, rx link) - the link itself
-        if (!HOT) s.aux[i] = MODE == PL_TABLE && a.table_by_link ? (i | (in.ra.x & 0x0F000000)) : (in.ra.x & 0x0FFFFFFF);
+        if (!HOT) s.aux[i] = (MODE == PL_TABLE && a.table_by_link) || MODE == PL_TABLE_DB ? (i | (in.ra.x & 0x0F000000)) : (in.ra.x & 0x0FFFFFFF);
         if (IN_REGS(u)) me0[KEPT(u)] = tuple;                            // own links stay in registers for pass 2
         if (POWLAW) s.expo[i] = in.hh;
         if (XPOS) s.lo[i] = make_float2(in.plo.x, in.plo.y);
@@ -288,6 +292,9 @@ __global__ __launch_bounds__(1024) void step_kernel(const StepArgs a) {
     }
 
     const float* gtab = MODE == PL_TABLE ? a.gain_table + (size_t)b * a.table_env_stride : nullptr;
+    // PL_TABLE_DB: this env's [N+1][N] block of the caller's live dB table (4- or 8-byte entries)
+    const void* gdb = MODE == PL_TABLE_DB ? static_cast<const void*>(reinterpret_cast<const char*>(a.gain_table) +
+                                                                     (size_t)b * a.table_env_stride * (a.table_by_link == 2 ? 8u : 4u)) : nullptr;
     const unsigned genv = (unsigned)(a.env_offset + (unsigned long long)b);   // global env index (RNG counter)
 
     // ---- pass 2: interference reduction + SINR/SNR/rate/capacity + obs table
@@ -310,7 +317,7 @@ __global__ __launch_bounds__(1024) void step_kernel(const StepArgs a) {
         const bool use_masks = masks_on && (unsigned)rb < (unsigned)R;
         const int type = (in.ra.x >> D2D_REC_TYPE_SHIFT) & D2D_REC_TYPE_MASK;
         const int txd = in.ra.x & D2D_REC_TXDEV_MASK, rxd = in.ra.y;
-        const int tcol = MODE == PL_TABLE && a.table_by_link ? i : rxd;      // column of this receiver in the gain table
+        const int tcol = (MODE == PL_TABLE && a.table_by_link) || MODE == PL_TABLE_DB ? i : rxd;      // column of this receiver in the gain table
         const float rx_pl = in.rb_.y, rx_lin = in.rb_.z, noise = in.rb_.w;
         const float sens = in.rc.x, bw_mhz = in.rc.y;
         // the interference sum in DOUBLE: each term is one rounded float product, but the running sum no longer drifts with the
@@ -335,6 +342,7 @@ __global__ __launch_bounds__(1024) void step_kernel(const StepArgs a) {
                 const float d2 = fmaf(dx, dx, dy * dy);                                                                 \
                 float g;                                                                                                \
                 if (MODE == PL_TABLE) g = gtab[(size_t)(s.aux[j] & 0xFFFFFF) * a.table_pitch + tcol];                                \
+                else if (MODE == PL_TABLE_DB) g = table_gain_db(a, gdb, (size_t)(j) * a.table_pitch + tcol, my_flags);     \
                 else { g = pair_gain<MODE>(d2, POWLAW ? s.expo[j] : make_float2(-1.0f, 0.0f), a.pow_k); if (!NF_ONLY) dmin = min(dmin, __float_as_int(d2)); } \
                 if (MODE == PL_SHADOW && d2 > a.shadow_d0sq) g *= shadow_factor(a, genv, (int)(j), i, 0u);              \
                 acc += (double)((o).z * g);                              /* simulator.py:97-101, linear mW */            \
@@ -362,7 +370,7 @@ __global__ __launch_bounds__(1024) void step_kernel(const StepArgs a) {
                     }
                 }
             } else {
-#pragma unroll
+#pragma unroll LIST_UNROLL
                 for (int k = 0; k < LIST_SLOTS - 1; ++k) {
                     const unsigned j = v[k];
                     if (j == LIST_EMPTY) break;
@@ -397,6 +405,7 @@ __global__ __launch_bounds__(1024) void step_kernel(const StepArgs a) {
                         const float d2 = fmaf(dx, dx, dy * dy);
                         float g;
                         if (MODE == PL_TABLE) g = gtab[(size_t)(s.aux[j] & 0xFFFFFF) * a.table_pitch + tcol];
+                        else if (MODE == PL_TABLE_DB) g = table_gain_db(a, gdb, (size_t)j * a.table_pitch + tcol, my_flags);
                         else { g = pair_gain<MODE>(d2, POWLAW ? s.expo[j] : make_float2(-1.0f, 0.0f), a.pow_k); if (!NF_ONLY) dmin = min(dmin, __float_as_int(d2)); }
                         if (MODE == PL_SHADOW && d2 > a.shadow_d0sq) g *= shadow_factor(a, genv, j, i, 0u);
                         acc += (double)(o.z * g);                        // simulator.py:97-101, linear mW
@@ -424,6 +433,7 @@ __global__ __launch_bounds__(1024) void step_kernel(const StepArgs a) {
                             const float d2 = fmaf(dx, dx, dy * dy);
                             float g;
                             if (MODE == PL_TABLE) g = gtab[(size_t)(s.aux[j] & 0xFFFFFF) * a.table_pitch + tcol];
+                            else if (MODE == PL_TABLE_DB) g = table_gain_db(a, gdb, (size_t)j * a.table_pitch + tcol, my_flags);
                             else { g = pair_gain<MODE>(d2, POWLAW ? s.expo[j] : make_float2(-1.0f, 0.0f), a.pow_k); if (!NF_ONLY) dmin = min(dmin, __float_as_int(d2)); }
                             if (MODE == PL_SHADOW && d2 > a.shadow_d0sq) g *= shadow_factor(a, genv, j, i, 0u);
                             acc += (double)(o.z * g);                    // simulator.py:97-101, linear mW
@@ -437,7 +447,7 @@ __global__ __launch_bounds__(1024) void step_kernel(const StepArgs a) {
                 }
             }
         } else {
-#pragma unroll 4
+#pragma unroll PAIR_UNROLL
             for (int j = 0; j < N; ++j) {
                 const float4 o = s.link[j];                              // same address in every lane: LDS broadcast
                 const bool same = (__float_as_int(o.w) == rb) & (j != i);
@@ -445,6 +455,7 @@ __global__ __launch_bounds__(1024) void step_kernel(const StepArgs a) {
                 const float d2 = fmaf(dx, dx, dy * dy);
                 float g;
                 if (MODE == PL_TABLE) g = same ? gtab[(size_t)(s.aux[j] & 0xFFFFFF) * a.table_pitch + tcol] : 0.0f;
+                else if (MODE == PL_TABLE_DB) g = same ? table_gain_db(a, gdb, (size_t)j * a.table_pitch + tcol, my_flags) : 0.0f;
                 else { g = pair_gain<MODE>(d2, POWLAW ? s.expo[j] : make_float2(-1.0f, 0.0f), a.pow_k); if (!NF_ONLY) dmin = same ? min(dmin, __float_as_int(d2)) : dmin; }
                 if (MODE == PL_SHADOW && same && d2 > a.shadow_d0sq) g *= shadow_factor(a, genv, j, i, 0u);
                 acc += same ? (double)(o.z * g) : 0.0;
@@ -499,10 +510,20 @@ __global__ __launch_bounds__(1024) void step_kernel(const StepArgs a) {
         const float dy = XPOS ? coord_diff(me.y, rx.y, in.plo.y, rxlo.y) : me.y - rx.y;
         const float d2 = fmaf(dx, dx, dy * dy);
         float g;
+        float g_snr = 0.0f;
         if (MODE == PL_TABLE) g = gtab[(size_t)(a.table_by_link ? i : txd) * a.table_pitch + tcol];
-        else { g = pair_gain<MODE>(d2, in.hh, a.pow_k); if (!NF_ONLY) dmin = min(dmin, __float_as_int(d2)); }
+        else if (MODE == PL_TABLE_DB) {
+            // the signal path (row i) and the SNR's own evaluation of it (row N, simulator.py:114) through ONE conversion site
+            g = 0.0f;
+#pragma unroll 1
+            for (int r = 0; r < 2; ++r) {
+                const float t = table_gain_db(a, gdb, (size_t)(r ? N : i) * a.table_pitch + tcol, my_flags);
+                if (r) g_snr = t; else g = t;
+            }
+        } else { g = pair_gain<MODE>(d2, in.hh, a.pow_k); if (!NF_ONLY) dmin = min(dmin, __float_as_int(d2)); }
         float sig = me.z * g * rx_pl * rx_lin;                           // mW at the receiver, with rx gains
         float sig_snr = sig;
+        if (MODE == PL_TABLE_DB) sig_snr = me.z * g_snr * rx_pl * rx_lin;
         if (MODE == PL_SHADOW && d2 > a.shadow_d0sq) {
             sig_snr = sig * shadow_factor(a, genv, i, i, 1u);            // simulator.py:114: a second, independent draw
             sig *= shadow_factor(a, genv, i, i, 0u);                     // simulator.py:93
@@ -914,6 +935,7 @@ hipError_t launch_step(const StepArgs& a, PlMode mode, int block_threads, hipStr
         case PL_POWK: D2D_LAUNCH(PL_POWK); break;
         case PL_TABLE: D2D_LAUNCH_COLD(PL_TABLE); break;          // the rollout specialisations exist for the power laws only
         case PL_SHADOW: D2D_LAUNCH_COLD(PL_SHADOW); break;
+        case PL_TABLE_DB: D2D_LAUNCH_COLD(PL_TABLE_DB); break;    // the live dB table (D2D_PL_TABLE_LIVE)
     }
 #undef D2D_LAUNCH
 #undef D2D_LAUNCH_COLD

@@ -17,6 +17,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 #define FLAG_ZERO_DISTANCE 1
 #define FLAG_RB_OOR 2
 #define FLAG_NON_FINITE 4
+#define FLAG_PL_DOMAIN 8          // D2D_FLAG_PATH_LOSS_DOMAIN: a live dB entry the step read is NaN or -inf
 
 #define LINK_UPLINK 1
 #define LINK_DOWNLINK 2
@@ -181,24 +182,40 @@ __device__ __forceinline__ float cos_turns(float u) {
     return ((k + 1) & 2) ? -b : b;
 }
 
-// Linear-domain factor 10^(-X/10), X ~ N(0, chi^2) dB, for the call (tx link j -> rx link i, kind) of this step.
-// ShadowingPathLoss.__call__ draws gauss(0, chi) on EVERY call with d > d0 (path_loss.py:76-79): the signal term of
-// the SINR (kind 0, j == i), every interferer term (kind 0, j != i) and the SNR's own re-evaluation of the signal
-// path loss (kind 1, simulator.py:114) are independent draws.
+// Standard normal z of the call (tx link j -> rx link i, kind) of step `step` in env `env`: Box-Muller of Philox4x32-10 with counter
+// (env, step, j | i << 16, kind) and key (seed_lo, seed_hi).  Shared by the step kernel's shadowing (shadow_factor) and the plugin
+// library's generator (csrc/d2d_plugin.hip, ArrayPathLoss's view.normal()), so a plugin that adds chi * z draws what PL_SHADOW draws.
 // Box-Muller to ~1e-7 absolute in z (round 6; the oracle does the same transform of the same words in double): u1 = (k + 0.5) 2^-24 is
 // a float32 value only for k < 2^23 - above, k + 0.5 needs 25 bits and rounds, and near u1 = 1 the Gaussian's radius sqrt(-2 ln u1)
 // amplifies that by 1 / (z u1) (z = 0.01: 3e-6; the largest k: the radius itself) - so the upper half goes through
 // log1p(-(1 - u1)), whose argument (2^24 - k - 0.5) 2^-24 IS exact; the angle by cos_turns.
-__device__ __forceinline__ float shadow_factor(const StepArgs& a, unsigned env, int j, int i, unsigned kind) {
+__device__ __forceinline__ float philox_normal(unsigned env, unsigned step, unsigned ctr2, unsigned kind, unsigned seed_lo, unsigned seed_hi) {
     unsigned w0, w1;
-    philox_step(env, a.shadow_step, (unsigned)j | ((unsigned)i << 16), kind, a.shadow_seed_lo, a.shadow_seed_hi, w0, w1);
+    philox_step(env, step, ctr2, kind, seed_lo, seed_hi, w0, w1);
     const unsigned k1 = w0 >> 8;
     const float lo_half = logf(((float)(k1 & 0x7FFFFFu) + 0.5f) * 5.9604644775390625e-08f);                 // k1 < 2^23: exact argument
     const float hi_half = log1pf(-(((float)(0x1000000u - k1) - 0.5f) * 5.9604644775390625e-08f));          // k1 >= 2^23: 1 - u1 exact
     const float nl = -(k1 < 0x800000u ? lo_half : hi_half);                                                 // -ln(u1), u1 in (0, 1)
     const float u2 = (float)(w1 >> 8) * 5.9604644775390625e-08f;               // [0, 1)
-    const float z = sqrtf(2.0f * nl) * cos_turns(u2);                          // Box-Muller
+    return sqrtf(2.0f * nl) * cos_turns(u2);                                   // Box-Muller
+}
+
+// Linear-domain factor 10^(-X/10), X ~ N(0, chi^2) dB, for the call (tx link j -> rx link i, kind) of this step.
+// ShadowingPathLoss.__call__ draws gauss(0, chi) on EVERY call with d > d0 (path_loss.py:76-79): the signal term of
+// the SINR (kind 0, j == i), every interferer term (kind 0, j != i) and the SNR's own re-evaluation of the signal
+// path loss (kind 1, simulator.py:114) are independent draws.
+__device__ __forceinline__ float shadow_factor(const StepArgs& a, unsigned env, int j, int i, unsigned kind) {
+    const float z = philox_normal(env, a.shadow_step, (unsigned)j | ((unsigned)i << 16), kind, a.shadow_seed_lo, a.shadow_seed_hi);
     return exp2f(-0.33219280948873623f * a.shadow_chi * z);                     // 10^(-chi z / 10)
+}
+
+// PL_TABLE_DB: entry k of the env's live dB table -> linear gain, as gain_from_db_kernel converts it (the exponential in double,
+// rounded once: the same bits as the once-per-reset route).  An entry that is NaN or -inf is where the reference's plugin would
+// have raised (math.log10(0), path_loss.py:66): flagged, and only when the step reads it.
+__device__ __forceinline__ float table_gain_db(const StepArgs& a, const void* env_tab, size_t k, int& flags) {
+    const double x = a.table_by_link == 2 ? static_cast<const double*>(env_tab)[k] : (double)static_cast<const float*>(env_tab)[k];
+    if (!(x > -__builtin_huge_val())) flags |= FLAG_PL_DOMAIN;
+    return (float)exp2(-0.33219280948873623478703194294894 * x);
 }
 
 // LDS layout of ONE env (byte offsets, all computed on the host by step_lds_layout and passed in StepArgs::lds):

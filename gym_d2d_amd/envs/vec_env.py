@@ -76,8 +76,9 @@ class VecD2DEnv:
         arrays); the default float32 is the kernels' own block, zero copy.
 
         reset() checks the status flags once and raises ValueError('math domain error') if two interacting devices
-        coincide (what the reference's log10(0) does, path_loss.py:66); step() does not synchronise - poll
-        status_flags() for FLAG_ZERO_DISTANCE / FLAG_NON_FINITE if positions are written from outside."""
+        coincide (what the reference's log10(0) does, path_loss.py:66) or a per-step ArrayPathLoss returned NaN / -inf dB for a
+        pair the step used; step() does not synchronise - poll status_flags() for FLAG_ZERO_DISTANCE / FLAG_NON_FINITE /
+        FLAG_PATH_LOSS_DOMAIN if positions are written from outside."""
         env_config = dict(env_config or {})
         self.export_actions = bool(export_actions)
         obs_cls = env_config.pop('obs_fn', LinearObsFunction)
@@ -207,6 +208,7 @@ class VecD2DEnv:
         if ptr != self._stream_ptr:
             self.simulator.handle.set_stream(ptr)
             self._stream_ptr = ptr
+            self.simulator._pl_stream = ptr              # a per-step ArrayPathLoss evaluates on this stream: no synchronisation
 
     def _view(self) -> SimpleNamespace:
         sim = self.simulator
@@ -254,14 +256,15 @@ class VecD2DEnv:
             if self.num_agents:
                 self._t['actions'].copy_(_rng.uniform_ints_torch(torch, self._seed, self._episode, self.first_env,
                                                                   self.num_envs, self.num_agents, highs, self.device))
+            self.simulator.prepare_step()
             self.simulator.handle.step()
         else:
             a = _rng.uniform_ints_numpy(self._seed, self._episode, self.first_env, self.num_envs, self.num_agents, highs) \
                 if self.num_agents else np.zeros((self.num_envs, 0), np.int32)
             self.simulator.step_arrays(a)
         self._episode += 1
-        if self.simulator.handle.status_flags() & _native.FLAG_ZERO_DISTANCE:
-            raise ValueError('math domain error')            # log10(0) in path_loss.py:66
+        if self.simulator.handle.status_flags() & (_native.FLAG_ZERO_DISTANCE | _native.FLAG_PATH_LOSS_DOMAIN):
+            raise ValueError('math domain error')            # log10(0) in path_loss.py:66 (or in a per-step ArrayPathLoss)
         if self._placement_trials > 1 and self.placement is None:
             self._choose_obs_placement(self._placement_trials)
         return self._observe(self._view())
@@ -275,6 +278,9 @@ class VecD2DEnv:
         h = self.simulator.handle
         if getattr(self.simulator, 'shadowing_seed', None) is not None:
             self.placement = {'skipped': 'ShadowingPathLoss draws per step'}
+            return
+        if getattr(self.simulator, '_per_step', False):
+            self.placement = {'skipped': 'a per-step ArrayPathLoss is evaluated before every step'}
             return
         key, which = self._placement_target
         base = self._t[key]                                     # a view of the bound allocation (capacity may exceed the active part)
@@ -344,6 +350,7 @@ class VecD2DEnv:
             src = actions if torch.is_tensor(actions) else torch.as_tensor(np.asarray(actions), device=self.device)
             if tuple(src.shape) != (self.num_envs, self.num_agents):
                 raise ValueError(f'actions must be [{self.num_envs},{self.num_agents}], got {tuple(src.shape)}')
+            sim.prepare_step()                                # a per-step ArrayPathLoss: this step's table
             if src.dtype == torch.int32 and src.is_contiguous() and src.device == self.device:
                 sim.handle.step(src.data_ptr())               # zero copy: the kernel reads the caller's tensor
             else:

@@ -11,15 +11,19 @@ A user subclass that only defines __call__ is evaluated on the host once per epi
 (`table_db`, d2d_set_path_loss_table) - legal because positions are static between resets (simulator.py:61-75).
 For batches a per-object __call__ is B x N x N Python calls per reset (1.1e9 at 4096 x 512): `ArrayPathLoss` is the
 array-native form of the same plugin - compute(view) -> pl_db[B,N,N] on whole arrays (torch CUDA tensors in a batch, NumPy
-for a single pair), handed to the library from device memory (d2d_set_path_loss_link_table_dev).
+for a single pair), handed to the library from device memory (d2d_set_path_loss_link_table_dev).  An ArrayPathLoss with
+`per_step = True` is evaluated before EVERY step instead (a stochastic model: shadowing, fading), into a table the step kernel
+reads in place (D2D_PL_TABLE_LIVE); its view carries the step counter and the built-in shadowing's normal stream.
 """
 from __future__ import annotations
 
 import math
+import random
+import warnings
 from abc import ABC, abstractmethod
 from enum import Enum
 from random import gauss
-from typing import Dict, Optional, Sequence
+from typing import Callable, Dict, Optional, Sequence
 
 import numpy as np
 
@@ -75,15 +79,44 @@ class PathLossView:
         tx_devices, rx_devices   length-N lists of Device (antenna gains, heights, ... - the attributes device.py:85-173 exposes)
         distance()            [B, N, N] float64   d[b, j, i] = |tx of link j - rx of link i| (position.py:11-12)
         tx_column(fn) / rx_column(fn)   fn(device) per transmitter / receiver as an array shaped [1, N, 1] / [1, 1, N]
+        step                  steps enqueued since the model was installed (the reset's initial step included; not reset between
+                              episodes) - the counter the built-in ShadowingPathLoss draws by
+        first_env             global index of the view's env 0 (the env offset of a sharded run plus the chunk start)
+        seed                  the model's seed: env_config['seed'], else (per_step) one random.getrandbits(63) at construction, as
+                              ShadowingPathLoss's (a once-per-reset model without a seed takes one from the OS)
+        normal(kind=0)        standard normals, float64: kind 0 [B, N, N] by (tx link j, rx link i), kind 1 [B, N] (the SNR's
+                              own-link draws) - on the GPU the built-in ShadowingPathLoss's stream exactly (Box-Muller of
+                              Philox4x32-10, counter (first_env + b, step, j | i << 16, kind), key seed: libd2d_plugin.so), so
+                              pl + chi * where(d > d0, view.normal(), 0) draws what the built-in model draws; a single-pair NumPy
+                              view draws fresh values from NumPy's global generator
 
     pl_db[b, j, i] = PathLoss(tx of link j, rx of link i): j == i is the link's own signal path (simulator.py:93,114), j != i
     an interferer's (simulator.py:97-101) - the pairs d2d_set_path_loss_link_table names."""
 
-    def __init__(self, xp, tx_x, tx_y, rx_x, rx_y, tx_devices, rx_devices, like=None):
+    def __init__(self, xp, tx_x, tx_y, rx_x, rx_y, tx_devices, rx_devices, like=None, *, step: int = 0, first_env: int = 0,
+                 seed: int = 0):
         self.xp = xp
         self.tx_x, self.tx_y, self.rx_x, self.rx_y = tx_x, tx_y, rx_x, rx_y
         self.tx_devices, self.rx_devices = list(tx_devices), list(rx_devices)
         self._like = like if like is not None else tx_x
+        self.step, self.first_env, self.seed = int(step), int(first_env), int(seed)
+
+    def normal(self, kind: int = 0):
+        b, n = tuple(self.tx_x.shape)
+        if kind not in (0, 1):
+            raise ValueError('kind must be 0 (tx link j, rx link i) or 1 (own link i, the SNR)')
+        shape = (b, n, n) if kind == 0 else (b, n)
+        if self.xp.__name__ != 'torch':
+            return np.random.standard_normal(shape)
+        from . import _native
+        dev = self._like.device
+        out = self.xp.empty(shape, dtype=self.xp.float64, device=dev)
+        if out.numel():
+            with self.xp.cuda.device(dev):
+                stream = self.xp.cuda.current_stream(dev).cuda_stream
+                _native.plugin_normal(out.data_ptr(), _native.F64, b, self.first_env, n if kind == 0 else 1, n, self.step, kind,
+                                      self.seed, stream)
+        return out
 
     def _f64(self, a):
         return a.double() if self.xp.__name__ == 'torch' else np.asarray(a, dtype=np.float64)
@@ -120,7 +153,19 @@ class ArrayPathLoss(PathLoss):
                 return view.xp.where(d <= 50.0, near, far) - view.tx_column(lambda t: t.tx_antenna_gain_dBi)
 
     A batch evaluates it once per reset on the GPU (torch) and hands the result to the library from device memory
-    (d2d_set_path_loss_link_table_dev): no host table, no Python loop."""
+    (d2d_set_path_loss_link_table_dev): no host table, no Python loop.
+
+    per_step = True: a stochastic model (the reference calls its PathLoss on every step, path_loss.py:12-25, simulator.py:93,
+    97-101,114).  compute(view) then runs before every step - VecD2DEnv, Simulator.step_arrays and the single-env D2DEnv, the
+    step inside reset() included - into a [B, N+1, N] float64 table the step kernel reads in place (D2D_PL_TABLE_LIVE); torch
+    with a GPU is required.  compute may return pl_db or (pl_db, snr_pl_db[B, N]): the SNR's own evaluation of the signal
+    path (simulator.py:114 calls the model again: an independent draw for a stochastic model); omitted, the diagonal of pl_db.
+
+    env_chunk: compute runs on env slices of this many envs, each written into the table as it comes (None: as many as keep one
+    [b, N, N] float64 temporary within about 1 GiB); the results do not depend on it."""
+
+    per_step: bool = False
+    env_chunk: Optional[int] = None
 
     @abstractmethod
     def compute(self, view: PathLossView):
@@ -133,6 +178,37 @@ class ArrayPathLoss(PathLoss):
         if out.size != 1 or not np.isfinite(out[0]):
             raise ValueError('math domain error')          # what math.log10(0) raises in a per-object model (path_loss.py:66)
         return float(out[0])
+
+
+def is_deterministic(model: Callable, tx: Device, rx: Device) -> bool:
+    """Two calls of a per-object model on one pair give the same value (NaN == NaN; a pair it refuses counts as the same).
+    Python's and NumPy's global random states are put back, so checking consumes no draw the model would otherwise see."""
+    py_state, np_state = random.getstate(), np.random.get_state()
+    try:
+        vals = []
+        for _ in range(2):
+            try:
+                vals.append(float(model(tx, rx)))
+            except (ValueError, ZeroDivisionError):
+                vals.append(None)
+    finally:
+        random.setstate(py_state)
+        np.random.set_state(np_state)
+    a, b = vals
+    if a is None or b is None:
+        return a is b
+    return a == b or (math.isnan(a) and math.isnan(b))
+
+
+def warn_if_stochastic(model: Callable, tx: Device, rx: Device) -> bool:
+    """UserWarning when a per-object PathLoss gives two values for one pair: its table is evaluated once per reset, so every
+    draw would stay frozen for the episode.  Returns whether it warned."""
+    if is_deterministic(model, tx, rx):
+        return False
+    warnings.warn(f'{type(model).__name__} returned two different path losses for one (tx, rx) pair: a per-object PathLoss is '
+                  'evaluated once per reset and its draws stay frozen for the whole episode.  Write it as an ArrayPathLoss with '
+                  'per_step = True to have it evaluated on every step.', UserWarning, stacklevel=3)
+    return True
 
 
 def pl_constant_dB(carrier_freq_GHz: float, ple: float) -> float:

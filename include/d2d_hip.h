@@ -25,7 +25,8 @@
 extern "C" {
 #endif
 
-#define D2D_ABI_VERSION 5      /* 5: float64 positions (d2d_set_positions_f64), device-resident path-loss table (d2d_set_path_loss_link_table_dev) */
+#define D2D_ABI_VERSION 6      /* 5: float64 positions (d2d_set_positions_f64), device-resident path-loss table (d2d_set_path_loss_link_table_dev)
+                                  6: live dB table (D2D_PL_TABLE_LIVE), D2D_FLAG_PATH_LOSS_DOMAIN */
 #define D2D_MAX_LINKS 2048      /* links per env the step kernel's LDS staging is sized for */
 #define D2D_UNIQUE_ID_BYTES 128 /* size of an RCCL unique id (ncclUniqueId)                  */
 
@@ -91,6 +92,10 @@ typedef enum d2d_buffer {
 #define D2D_FLAG_RB_OUT_OF_RANGE 2u /* rb outside [0,num_rbs): accepted like the reference does
                                      (d2d_env.py:94-96); the env took the all-pairs code path       */
 #define D2D_FLAG_NON_FINITE 4u    /* a non-finite SINR was produced                                  */
+#define D2D_FLAG_PATH_LOSS_DOMAIN 8u /* a live path-loss table entry (D2D_PL_TABLE_LIVE) the step actually
+                                     used is NaN or -inf: where the reference's plugin raises
+                                     ValueError('math domain error') (math.log10(0), path_loss.py:66).
+                                     Entries no link reads raise nothing, as in the reference          */
 
 /* EnvConfig fields the device side needs (env_config.py:12-27) + batch geometry (new). */
 typedef struct d2d_config {
@@ -164,7 +169,15 @@ int d2d_set_path_loss_link_table(d2d_handle* h, const double* pl_db, int32_t n_l
  * carry 3.8e-6 dB of their own: prefer float64), [N,N] (per_env = 0) or [B,N,N]; converted to linear gains by one streaming
  * kernel (csrc/d2d_gain.hip: the exponential in double, rounded once) on the handle's stream - work that produced the table on
  * ANOTHER stream must have finished.  Synchronous: the caller may free the table when the call returns.  A failed call leaves
- * the handle without a path-loss table (the next step answers D2D_ERR_STATE), never with a partial one.                      */
+ * the handle without a path-loss table (the next step answers D2D_ERR_STATE), never with a partial one.
+ * per_env = D2D_PL_TABLE_LIVE binds the table instead: [B][N+1][N] dB entries, rows j < N = PathLoss(tx of link j, rx of link i),
+ * row N = the SNR's own evaluation of the signal path of link i (simulator.py:114; a stochastic model draws it anew).  The handle
+ * keeps the pointer - no copy, no conversion pass, never freed here - and every later step reads the entries it uses from it and
+ * converts each where it is read (the same double exponential, rounded once).  The caller may rewrite the table between steps in
+ * stream order (on the handle's stream, or after it); later steps do not synchronise for it.  d2d_set_links, any other path-loss
+ * setter and d2d_destroy drop the binding.  Any mode: pl_db_dev must be device or managed memory on the handle's device, checked
+ * (hipPointerGetAttributes) before anything is launched - anything else is D2D_ERR_INVALID.                                  */
+#define D2D_PL_TABLE_LIVE 2
 int d2d_set_path_loss_link_table_dev(d2d_handle* h, const void* pl_db_dev, int32_t dtype, int32_t n_links, int32_t per_env);
 
 /* Which (tx, rx) device pairs act this step and as what (Action.tx/rx/link_type, actions.py:9-15;
