@@ -198,6 +198,7 @@ class Handle:
         self.max_links = max_links or (num_cues + num_due_pairs)
         self.num_links = 0
         self.num_fixed = 0
+        self.env_offset = 0
 
     # -- lifetime
     def close(self) -> None:

@@ -20,6 +20,7 @@ from typing import Optional
 import numpy as np
 
 from .. import _native
+from ..path_loss_table import PER_STEP
 from ..simulator import BASE_STATION_ID, Simulator
 from ..traffic_model import DownlinkTrafficModel
 from . import _rng
@@ -206,9 +207,8 @@ class VecD2DEnv:
         the torch ops that produce actions / consume results.  Re-bound only when the caller switches streams."""
         ptr = self._current_stream_ptr()
         if ptr != self._stream_ptr:
-            self.simulator.handle.set_stream(ptr)
+            self.simulator.set_stream(ptr)
             self._stream_ptr = ptr
-            self.simulator._pl_stream = ptr              # a per-step ArrayPathLoss evaluates on this stream: no synchronisation
 
     def _view(self) -> SimpleNamespace:
         sim = self.simulator
@@ -263,8 +263,7 @@ class VecD2DEnv:
                 if self.num_agents else np.zeros((self.num_envs, 0), np.int32)
             self.simulator.step_arrays(a)
         self._episode += 1
-        if self.simulator.handle.status_flags() & (_native.FLAG_ZERO_DISTANCE | _native.FLAG_PATH_LOSS_DOMAIN):
-            raise ValueError('math domain error')            # log10(0) in path_loss.py:66 (or in a per-step ArrayPathLoss)
+        self.simulator.check_flags()
         if self._placement_trials > 1 and self.placement is None:
             self._choose_obs_placement(self._placement_trials)
         return self._observe(self._view())
@@ -276,10 +275,10 @@ class VecD2DEnv:
         model's step counter would advance, so that model keeps the block it has."""
         import time
         h = self.simulator.handle
-        if getattr(self.simulator, 'shadowing_seed', None) is not None:
+        if self.simulator.shadowing_seed is not None:
             self.placement = {'skipped': 'ShadowingPathLoss draws per step'}
             return
-        if getattr(self.simulator, '_per_step', False):
+        if self.simulator.path_loss_table.route == PER_STEP:
             self.placement = {'skipped': 'a per-step ArrayPathLoss is evaluated before every step'}
             return
         key, which = self._placement_target

@@ -2,11 +2,15 @@
 traffic-model actions, error types) with the C-ABI handle replaced by a recording stub.  The stub computes nothing:
 numbers are checked by the -m gpu tests; here only what the host hands to the boundary is."""
 import json
+import math
+import random
+from unittest.mock import ANY
 
 import numpy as np
 import pytest
 
 from gym_d2d_amd import _native
+from gym_d2d_amd.path_loss import ArrayPathLoss, PathLoss
 
 
 class RecordingHandle:
@@ -20,6 +24,7 @@ class RecordingHandle:
         self.max_links = kw.get('max_links') or (kw['num_cues'] + kw['num_due_pairs'])
         self.num_links = 0
         self.num_fixed = 0
+        self.env_offset = 0
         self.calls = []
         self.uploads = {}
         RecordingHandle.instances.append(self)
@@ -31,11 +36,16 @@ class RecordingHandle:
     def set_path_loss_power_law(self, a, b, e): self._rec('power_law', np.asarray(a), np.asarray(b), np.asarray(e))
     def set_path_loss_shadowing(self, a, b, e, d0, chi, seed): self._rec('shadowing', d0, chi, seed)
     def set_path_loss_table(self, t): self._rec('table', np.asarray(t))
+    def set_path_loss_link_table(self, t): self._rec('link_table', np.asarray(t))
     def set_reward(self, rid, param=0.0): self._rec('reward', rid, param)
     def set_obs_mode(self, m): self._rec('obs_mode', m)
-    def set_env_offset(self, k): self._rec('env_offset', k)
     def set_export_actions(self, on): self._rec('export_actions', on)
     def set_stream(self, p): self._rec('stream', p)
+    def synchronize(self): self._rec('synchronize')
+
+    def set_env_offset(self, k):
+        self.env_offset = int(k)
+        self._rec('env_offset', k)
     def reset_positions(self, seed, episode=0, mask=None, xy=None): self._rec('reset', seed, episode, mask, xy)
     def set_positions(self, x, y, env_begin=0): self._rec('positions', np.asarray(x), np.asarray(y))
     def status_flags(self): return 0
@@ -288,3 +298,195 @@ def test_vec_env_host_side(stub):
         def get_state(self, a, s, d): return {}
     with pytest.raises(TypeError):
         VecD2DEnv({'obs_fn': DictObs}, num_envs=2, use_torch=False)
+
+
+# ---------------------------------------------------------------------------------------------- path-loss table routes
+# What a Python PathLoss the kernels cannot evaluate hands to the handle, call by call, on every route that needs no GPU.
+
+class _Plugin(PathLoss):
+    """Deterministic and position-dependent; refuses a zero distance (math.log10(0)), as the reference's models do."""
+    def __call__(self, tx, rx):
+        return 30.0 + 31.0 * math.log10(tx.position.distance(rx.position)) - 0.5 * tx.tx_antenna_gain_dBi
+
+
+class _ArrayPlugin(ArrayPathLoss):
+    def compute(self, view):
+        return 30.0 + 31.0 * view.xp.log10(view.distance()) - 0.5 * view.tx_column(lambda t: t.tx_antenna_gain_dBi)
+
+
+class _ArrayPluginPerObject(PathLoss):
+    """_ArrayPlugin's own per-object call, as a plain PathLoss."""
+    def __call__(self, tx, rx):
+        return _ArrayPlugin(self.carrier_freq_GHz)(tx, rx)
+
+
+class _Gauss(PathLoss):
+    def __call__(self, tx, rx):
+        return 80.0 + random.gauss(0.0, 4.0)
+
+
+class _GaussArray(ArrayPathLoss):
+    def compute(self, view):
+        return 80.0 + np.random.standard_normal(tuple(view.tx_x.shape) + (view.tx_x.shape[-1],))
+
+
+_UPLINKS = [('cue00', 'mbs'), ('cue01', 'mbs'), ('due00', 'due01')]          # devices: mbs 0, cue00 1, cue01 2, due00 3, due01 4
+_MIXED = [('mbs', 'cue00'), ('cue00', 'mbs'), ('due00', 'due01')]            # a downlink: mbs transmits, cue00 receives
+
+
+def _sim(model, num_envs=1):
+    from gym_d2d_amd.simulator import Simulator
+    sim = Simulator({'num_rbs': 4, 'num_cues': 2, 'num_due_pairs': 1, 'num_envs': num_envs, 'path_loss_model': model})
+    return sim, RecordingHandle.instances[-1]
+
+
+def _pl(gains, xy, i, j):
+    """_Plugin's value for device i -> device j at xy [D, 2], NaN where it refuses."""
+    d = ((float(xy[i][0]) - float(xy[j][0])) ** 2 + (float(xy[i][1]) - float(xy[j][1])) ** 2) ** 0.5
+    return 30.0 + 31.0 * math.log10(d) - 0.5 * gains[i] if d > 0 else np.nan
+
+
+def _device_table(gains, xy, txs, rxs):
+    out = np.full((len(gains), len(gains)), np.nan)
+    for i in txs:
+        for j in rxs:
+            if i != j:
+                out[i, j] = _pl(gains, xy, i, j)
+    return out
+
+
+def _link_table(gains, xy, tx, rx):
+    return np.array([[[_pl(gains, xy[b], t, r) if t != r else np.nan for r in rx] for t in tx] for b in range(len(xy))])
+
+
+def _assert_log(got, want):
+    assert [n for n, _ in got] == [n for n, _ in want]
+    for (name, args), (_, expected) in zip(got, want):
+        if expected is ANY:
+            continue
+        assert len(args) == len(expected), name
+        for a, e in zip(args, expected):
+            if isinstance(e, np.ndarray):
+                a = np.asarray(a)
+                assert a.dtype == e.dtype and a.shape == e.shape and np.array_equal(a, e, equal_nan=True), (name, a, e)
+            else:
+                assert a == e, name
+
+
+def test_path_loss_device_table_route_is_incremental_over_link_changes(stub):
+    """One env: a [D, D] table of the pairs the links read, topped up when a new link list reads more, evaluated afresh when the
+    positions change; prepare_step() hands nothing over."""
+    sim, h = _sim(_Plugin)
+    gains = [d.tx_antenna_gain_dBi for d in sim.devices.values()]
+    rng = np.random.default_rng(3)
+    xy = rng.uniform(-300.0, 300.0, (1, 5, 2))
+    xy32 = rng.uniform(-300.0, 300.0, (1, 5, 2)).astype(np.float32)
+    sim.set_links(_UPLINKS)                          # no positions yet: nothing evaluated
+    sim.set_positions(xy)
+    sim.prepare_step()
+    sim.set_links(_MIXED)                            # adds mbs -> cue00 and the pairs it crosses
+    sim.set_links(_UPLINKS)                          # every pair it reads is there already
+    sim.prepare_step()
+    sim.set_positions(xy32)                          # new positions: only the current list's pairs
+    _assert_log(h.calls, [
+        ('device_table', ANY),
+        ('links', ([1, 2, 3], [0, 0, 4], [1, 1, 3])),
+        ('positions', (xy[..., 0], xy[..., 1])),
+        ('table', (_device_table(gains, xy[0], {1, 2, 3}, {0, 4}),)),
+        ('links', ([0, 1, 3], [1, 0, 4], [2, 1, 3])),
+        ('table', (_device_table(gains, xy[0], {0, 1, 2, 3}, {0, 1, 4}),)),
+        ('links', ([1, 2, 3], [0, 0, 4], [1, 1, 3])),
+        ('positions', (xy32[..., 0], xy32[..., 1])),
+        ('table', (_device_table(gains, xy32[0], {1, 2, 3}, {0, 4}),)),
+    ])
+
+
+def _drive_batch(sim, h):
+    """reset_device, float32 and float64 set_positions, a link-list change, an empty link list and back; returns the positions
+    each link table should come from."""
+    rng = np.random.default_rng(5)
+    dev = rng.uniform(-300.0, 300.0, (3, 5, 2)).astype(np.float32)
+    dev[1, 4] = dev[1, 3]                            # env 1: due01 on top of due00 - the model refuses that pair
+    h.uploads[_native.BUF_POS_X], h.uploads[_native.BUF_POS_Y] = dev[..., 0].copy(), dev[..., 1].copy()
+    p32 = rng.uniform(-300.0, 300.0, (3, 5, 2)).astype(np.float32)
+    p64 = rng.uniform(-300.0, 300.0, (3, 5, 2))
+    p32b = rng.uniform(-300.0, 300.0, (3, 5, 2)).astype(np.float32)
+    sim.set_links(_UPLINKS)                          # no positions yet: nothing evaluated
+    sim.reset_device(7)
+    sim.prepare_step()
+    sim.set_positions(p32)
+    sim.set_positions(p64)
+    sim.set_links(_MIXED)
+    sim.set_links([])                                # no links, no pairs
+    sim.set_positions(p32b)
+    sim.set_links(_UPLINKS)
+    sim.prepare_step()
+    return dev, p32, p64, p32b
+
+
+def test_path_loss_link_table_route_follows_positions_and_links(stub):
+    """A batch with a per-object model: [B, N, N] by (tx link, rx link) of the current list, evaluated again on every position
+    or link change, from the positions as given (float64 kept) or, after a device-side reset, as the handle holds them."""
+    sim, h = _sim(_Plugin, num_envs=3)
+    gains = [d.tx_antenna_gain_dBi for d in sim.devices.values()]
+    dev, p32, p64, p32b = _drive_batch(sim, h)
+    up, mixed = ([1, 2, 3], [0, 0, 4]), ([0, 1, 3], [1, 0, 4])
+    _assert_log(h.calls, [
+        ('device_table', ANY),
+        ('links', (*up, [1, 1, 3])),
+        ('reset', (7, 0, None, None)),
+        ('link_table', (_link_table(gains, dev, *up),)),
+        ('positions', (p32[..., 0], p32[..., 1])),
+        ('link_table', (_link_table(gains, p32, *up),)),
+        ('positions', (p64[..., 0], p64[..., 1])),
+        ('link_table', (_link_table(gains, p64, *up),)),
+        ('links', (*mixed, [2, 1, 3])),
+        ('link_table', (_link_table(gains, p64, *mixed),)),
+        ('links', ([], [], [])),
+        ('positions', (p32b[..., 0], p32b[..., 1])),
+        ('links', (*up, [1, 1, 3])),
+        ('link_table', (_link_table(gains, p32b, *up),)),
+    ])
+    assert np.isnan(_link_table(gains, dev, *up)[1, 2, 2])          # the refused pair stays NaN in the table handed over
+
+
+@pytest.fixture
+def no_gpu(monkeypatch):
+    """torch without a GPU, whichever machine runs the suite."""
+    try:
+        import torch
+    except ImportError:         # pragma: no cover - torch is part of the platform
+        return
+    monkeypatch.setattr(torch.cuda, 'is_available', lambda: False)
+
+
+def test_array_path_loss_without_a_gpu_takes_the_link_table_route(stub, no_gpu):
+    """A once-per-reset ArrayPathLoss on a batch, with no GPU for compute(view): the link-table route through its own per-object
+    call, the same calls as that per-object model makes."""
+    logs = []
+    with np.errstate(divide='ignore'):
+        for model in (_ArrayPlugin, _ArrayPluginPerObject):
+            sim, h = _sim(model, num_envs=3)
+            _drive_batch(sim, h)
+            logs.append(h.calls)
+    assert [n for n, _ in logs[0]].count('link_table') == 5
+    _assert_log(logs[0], logs[1])
+
+
+def test_stochastic_per_object_model_warns_once(stub, no_gpu):
+    """A per-object PathLoss that draws per call is frozen into its table: one UserWarning per simulator, on either table route.
+    An ArrayPathLoss is not asked (its stochastic form is per_step)."""
+    import warnings
+    for model, num_envs, expected in ((_Gauss, 1, 1), (_Gauss, 3, 1), (_Plugin, 3, 0), (_GaussArray, 1, 0), (_GaussArray, 3, 0)):
+        with warnings.catch_warnings(record=True) as got:
+            warnings.simplefilter('always')
+            sim, h = _sim(model, num_envs=num_envs)
+            if num_envs == 1:
+                sim.set_links(_UPLINKS)
+                sim.set_positions(np.random.default_rng(1).uniform(-300.0, 300.0, (1, 5, 2)))
+                sim.set_links(_MIXED)
+                sim.set_positions(np.random.default_rng(2).uniform(-300.0, 300.0, (1, 5, 2)))
+            else:
+                _drive_batch(sim, h)
+        frozen = [w for w in got if issubclass(w.category, UserWarning) and 'frozen' in str(w.message)]
+        assert len(frozen) == expected, (model.__name__, num_envs, [str(w.message) for w in got])
