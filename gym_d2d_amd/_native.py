@@ -1,5 +1,5 @@
-"""ctypes binding of libd2d_hip.so (include/d2d_hip.h) and libd2d_plugin.so (include/d2d_plugin.h).  There is no CPU
-fallback: if a library or a gfx950 GPU is missing, the calls below raise."""
+"""ctypes binding of libd2d_hip.so (include/d2d_hip.h), libd2d_plugin.so (include/d2d_plugin.h) and libd2d_episode.so
+(include/d2d_episode.h).  There is no CPU fallback: if a library or a gfx950 GPU is missing, the calls below raise."""
 from __future__ import annotations
 
 import ctypes as C
@@ -10,7 +10,8 @@ import numpy as np
 
 LIB_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_hip.so'
 PLUGIN_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_plugin.so'
-ABI_VERSION = 6
+EPISODE_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_episode.so'
+ABI_VERSION = 7
 MAX_LINKS = 2048
 
 # d2d_status
@@ -23,10 +24,13 @@ REWARD_NONE, REWARD_SYSTEM_CAPACITY, REWARD_SHANNON, REWARD_CUE_SINR_SHANNON = 0
 OBS_NONE, OBS_TABLE, OBS_LINEAR = 0, 1, 2
 # d2d_buffer
 (BUF_POS_X, BUF_POS_Y, BUF_ACTIONS, BUF_RB, BUF_PWR, BUF_SINR_DB, BUF_SNR_DB, BUF_RATE_BPS, BUF_CAPACITY,
- BUF_REWARD, BUF_OBS_TABLE, BUF_OBS, BUF_ENV_FLAGS, BUF_LINK_POS, BUF_REWARD_ENV, BUF_COUNT) = range(16)
+ BUF_REWARD, BUF_OBS_TABLE, BUF_OBS, BUF_ENV_FLAGS, BUF_LINK_POS, BUF_REWARD_ENV, BUF_RESET_PENDING, BUF_EPISODE,
+ BUF_COUNT) = range(18)
 FLAG_ZERO_DISTANCE, FLAG_RB_OUT_OF_RANGE, FLAG_NON_FINITE, FLAG_PATH_LOSS_DOMAIN = 1, 2, 4, 8
 # d2d_set_path_loss_link_table_dev's per_env: 0 [N,N], 1 [B,N,N] (converted once), PL_TABLE_LIVE [B,N+1,N] (bound, read every step)
 PL_TABLE_LIVE = 2
+# d2d_reset_positions's episode: reset the envs BUF_RESET_PENDING marks, each at its BUF_EPISODE entry
+EPISODE_PER_ENV = (1 << 64) - 1
 # d2d_tuning (TUNE_OBS_VARIANT, TUNE_STEP_ABLATE, TUNE_OBS_STAGGER: include/d2d_hip_diag.h, diagnostic builds only)
 (TUNE_OBS_ROWS_PER_WG, TUNE_OBS_NONTEMPORAL, TUNE_OBS_XCD_REMAP, TUNE_OBS_BLOCK, TUNE_OBS_VARIANT,
  TUNE_STEP_THREADS, TUNE_STEP_ENVS_PER_WG, TUNE_STEP_BLOCK, TUNE_STEP_FUSE_OBS, TUNE_STEP_ABLATE,
@@ -38,7 +42,8 @@ REWARD_PER_AGENT, REWARD_PER_ENV = 0, 1
 F32, F64 = 0, 1
 UNIQUE_ID_BYTES = 128
 
-BUFFER_DTYPES = {BUF_ACTIONS: np.int32, BUF_RB: np.int32, BUF_PWR: np.int32, BUF_ENV_FLAGS: np.int32}
+BUFFER_DTYPES = {BUF_ACTIONS: np.int32, BUF_RB: np.int32, BUF_PWR: np.int32, BUF_ENV_FLAGS: np.int32, BUF_RESET_PENDING: np.int32,
+                 BUF_EPISODE: np.uint32}
 
 
 class Config(C.Structure):
@@ -122,8 +127,16 @@ PLUGIN_SIGNATURES = {
     'd2d_plugin_last_error': (C.c_char_p, []),
 }
 
+# every symbol include/d2d_episode.h declares
+EPISODE_SIGNATURES = {
+    'd2d_episode_merge_actions': (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, _I, C.c_uint64, C.c_uint64, _P]),
+    'd2d_episode_advance': (C.c_int, [_P, _P, _P, _P, _P, _P, _I, C.c_int64, _I, _P]),
+    'd2d_episode_last_error': (C.c_char_p, []),
+}
+
 _lib: Optional[C.CDLL] = None
 _plugin: Optional[C.CDLL] = None
+_episode: Optional[C.CDLL] = None
 
 
 def load_library() -> C.CDLL:
@@ -169,6 +182,43 @@ def plugin_normal(out_ptr: int, dtype: int, n_envs: int, first_env: int, n_rows:
                                kind, C.c_uint64(seed & (2 ** 64 - 1)), _P(stream_ptr or None))
     if rc != 0:
         raise NativeError(rc, lib.d2d_plugin_last_error().decode(errors='replace'))
+
+
+def load_episode_library() -> C.CDLL:
+    """dlopen libd2d_episode.so and type its entry points.  Raises if it has not been built."""
+    global _episode
+    if _episode is not None:
+        return _episode
+    if not EPISODE_PATH.exists():
+        raise ImportError(f'{EPISODE_PATH} is missing - build it with `python -m gym_d2d_amd.build`')
+    lib = C.CDLL(str(EPISODE_PATH))
+    for name, (res, args) in EPISODE_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    _episode = lib
+    return lib
+
+
+def _check_episode(rc: int) -> None:
+    if rc != 0:
+        raise NativeError(rc, load_episode_library().d2d_episode_last_error().decode(errors='replace'))
+
+
+def episode_merge_actions(in_ptr: int, out_ptr: int, pending_ptr: int, episode_ptr: int, high_ptr: int, n_envs: int, n_cols: int,
+                          first_env: int, seed: int, stream_ptr: int = 0) -> None:
+    """d2d_episode_merge_actions: out[b] = pending[b] ? the reset's random actions at episode[b] : in[b] (device pointers)."""
+    _check_episode(load_episode_library().d2d_episode_merge_actions(
+        _P(in_ptr), _P(out_ptr), _P(pending_ptr), _P(episode_ptr), _P(high_ptr), n_envs, n_cols, C.c_uint64(first_env),
+        C.c_uint64(seed & (2 ** 64 - 1)), _P(stream_ptr or None)))
+
+
+def episode_advance(pending_ptr: int, episode_ptr: int, elapsed_ptr: int, done_ptr: int, reset_ptr: int, reward_ptr: int,
+                    reward_cols: int, n_envs: int, episode_length: int, stream_ptr: int = 0) -> None:
+    """d2d_episode_advance: per-env counters after a step; zeroes the reward rows of the envs that were reset (reward_ptr 0: none)."""
+    _check_episode(load_episode_library().d2d_episode_advance(
+        _P(pending_ptr), _P(episode_ptr), _P(elapsed_ptr), _P(done_ptr), _P(reset_ptr), _P(reward_ptr or None), reward_cols, n_envs,
+        episode_length, _P(stream_ptr or None)))
 
 
 def _check(rc: int) -> None:
@@ -304,7 +354,7 @@ class Handle:
             return (b, n, 6)
         if which == BUF_OBS:
             return (b, n, 6 * n)
-        if which in (BUF_ENV_FLAGS, BUF_REWARD_ENV):
+        if which in (BUF_ENV_FLAGS, BUF_REWARD_ENV, BUF_RESET_PENDING, BUF_EPISODE):
             return (b,)
         if which == BUF_LINK_POS:
             return (b, n, 4)
@@ -348,6 +398,7 @@ class Handle:
             _check(self._lib.d2d_set_positions(self._h, x.ctypes.data_as(_FP), y.ctypes.data_as(_FP), env_begin, x.shape[0]))
 
     def reset_positions(self, seed: int, episode: int = 0, fixed_mask=None, fixed_xy=None) -> None:
+        """episode = EPISODE_PER_ENV: only the envs BUF_RESET_PENDING marks, each at its BUF_EPISODE entry (asynchronous)."""
         m = xy = None
         if fixed_mask is not None:
             m = np.ascontiguousarray(fixed_mask, dtype=np.uint8)

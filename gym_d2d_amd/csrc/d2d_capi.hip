@@ -130,6 +130,7 @@ struct d2d_handle {
     unsigned long long shadow_seed = 0, shadow_step = 0;
     unsigned char* fixed_mask_dev = nullptr;   // [D] + pad
     float* fixed_xy_dev = nullptr;             // [D,2]
+    bool fixed_live = false;                   // the last full d2d_reset_positions pinned devices: a per-env reset pins the same
     // profiling
     bool prof = false;
     std::vector<EventPair> events;
@@ -147,7 +148,7 @@ size_t active_bytes(const d2d_handle* h, int which, int n_links) {
         case D2D_BUF_POS_X: case D2D_BUF_POS_Y: return B * D * 4;
         case D2D_BUF_OBS_TABLE: return B * N * 6 * 4;
         case D2D_BUF_OBS: return B * N * 6 * N * (h->obs_f64 ? 8 : 4);
-        case D2D_BUF_ENV_FLAGS: case D2D_BUF_REWARD_ENV: return B * 4;
+        case D2D_BUF_ENV_FLAGS: case D2D_BUF_REWARD_ENV: case D2D_BUF_RESET_PENDING: case D2D_BUF_EPISODE: return B * 4;
         case D2D_BUF_LINK_POS: return B * N * 16;
         default: return B * N * 4;
     }
@@ -164,7 +165,8 @@ int ensure_buffer(d2d_handle* h, int which, void** out) {
     if (bf.ptr) { HIP_TRY(hipStreamSynchronize(h->stream)); HIP_TRY(hipFree(bf.ptr)); bf.ptr = nullptr; }
     HIP_TRY(hipMalloc(&bf.ptr, need ? need : 4));
     bf.bytes = need; bf.owned = true;
-    if (which == D2D_BUF_ENV_FLAGS) HIP_TRY(hipMemsetAsync(bf.ptr, 0, need, h->stream));
+    if (which == D2D_BUF_ENV_FLAGS || which == D2D_BUF_RESET_PENDING || which == D2D_BUF_EPISODE)
+        HIP_TRY(hipMemsetAsync(bf.ptr, 0, need, h->stream));
     *out = bf.ptr;
     return D2D_OK;
 }
@@ -1371,15 +1373,44 @@ int d2d_set_env_offset(d2d_handle* h, uint64_t first_env) try {
     return D2D_OK;
 } D2D_CATCH
 
+// d2d_reset_positions(.., D2D_EPISODE_PER_ENV, ..): the pending envs only, asynchronous, every other env's bytes as they were
+int reset_pending(d2d_handle* h, uint64_t seed, float* px, float* py) {
+    if (!h->have_pos) return fail(D2D_ERR_STATE, "a per-env reset needs positions for the other envs: reset or set them first");
+    void *pending = nullptr, *episode = nullptr;
+    int rc = ensure_buffer(h, D2D_BUF_RESET_PENDING, &pending);
+    if (rc) return rc;
+    rc = ensure_buffer(h, D2D_BUF_EPISODE, &episode);
+    if (rc) return rc;
+    const size_t bd = (size_t)h->B * h->D;
+    float* lo_x = h->have_lo ? h->pos_lo : nullptr;
+    float* lo_y = h->have_lo ? h->pos_lo + bd : nullptr;
+    // rows that are current stay current: written by the units themselves (standard link list) or gathered per reset env;
+    // rows already due for a rebuild are rebuilt from POS_X / POS_Y (and the low parts) before the next step as always
+    const bool rows = !h->tables_dirty && !h->lpos_dirty && h->lpos && h->N > 0;
+    const bool unit_rows = rows && h->std_layout;
+    const bool gather = rows && !h->std_layout;
+    float4* rows_lo = rows && h->have_lo ? h->lpos_lo : nullptr;
+    HIP_TRY(d2d::launch_reset_masked(h->B, h->D, h->cfg.num_cues, h->cfg.cell_radius_m, h->cfg.d2d_radius_m, seed, h->env_offset,
+                                     h->fixed_live ? h->fixed_mask_dev : nullptr, h->fixed_live ? h->fixed_xy_dev : nullptr, px, py,
+                                     unit_rows ? h->lpos : nullptr, h->N, static_cast<const int*>(pending),
+                                     static_cast<const unsigned*>(episode), lo_x, lo_y,
+                                     gather ? reinterpret_cast<const int4*>(h->rec) : nullptr, gather ? h->lpos : nullptr, rows_lo,
+                                     h->stream));
+    return D2D_OK;
+}
+
 int d2d_reset_positions(d2d_handle* h, uint64_t seed, uint64_t episode, const uint8_t* fixed_mask, const float* fixed_xy) try {
     if (!h) return fail(D2D_ERR_INVALID, "null handle");
     USE_DEVICE(h);
     if ((fixed_mask == nullptr) != (fixed_xy == nullptr)) return fail(D2D_ERR_INVALID, "fixed_mask and fixed_xy go together");
+    if (episode == D2D_EPISODE_PER_ENV && fixed_mask)
+        return fail(D2D_ERR_INVALID, "a per-env reset pins the devices of the last full reset: fixed_mask / fixed_xy must be NULL");
     void *px = nullptr, *py = nullptr;
     int rc = ensure_buffer(h, D2D_BUF_POS_X, &px);
     if (rc) return rc;
     rc = ensure_buffer(h, D2D_BUF_POS_Y, &py);
     if (rc) return rc;
+    if (episode == D2D_EPISODE_PER_ENV) return reset_pending(h, seed, static_cast<float*>(px), static_cast<float*>(py));
     const unsigned char* m = nullptr;
     const float* xy = nullptr;
     if (fixed_mask) {
@@ -1401,6 +1432,7 @@ int d2d_reset_positions(d2d_handle* h, uint64_t seed, uint64_t episode, const ui
     h->have_pos = true;
     h->lpos_dirty = !rows_here;
     h->have_lo = false;            // the sampler draws float32 coordinates
+    h->fixed_live = m != nullptr;
     return D2D_OK;
 } D2D_CATCH
 

@@ -146,5 +146,11 @@ hipError_t launch_gain_from_db(const void* pl_db, int is_f64, size_t elems, floa
 hipError_t launch_reset(int B, int D, int C, float cell_radius, float d2d_radius, unsigned long long seed,
                         unsigned long long episode, unsigned long long env_offset, const unsigned char* fixed_mask,
                         const float* fixed_xy, float* pos_x, float* pos_y, float4* lpos, int N, hipStream_t stream);
+// the envs with pending[b] != 0 only, each at episode[b]; lo_x / lo_y: low parts to zero; rec_a: gather the rows of a non-standard
+// link list into rows (lpos null), rows_lo: low parts of the rows to zero
+hipError_t launch_reset_masked(int B, int D, int C, float cell_radius, float d2d_radius, unsigned long long seed,
+                               unsigned long long env_offset, const unsigned char* fixed_mask, const float* fixed_xy, float* pos_x,
+                               float* pos_y, float4* lpos, int N, const int* pending, const unsigned* episode, float* lo_x, float* lo_y,
+                               const int4* rec_a, float4* rows, float4* rows_lo, hipStream_t stream);
 
 }  // namespace d2d

@@ -8,6 +8,7 @@
 //     counter = (global env index, device index, try, episode)      key = 64-bit seed
 //     word 0 -> theta = 2*pi*u, u = (word >> 8) * 2^-24 in [0,1);  word 1 -> r = radius*sqrt(u), u = ((word >> 8) + 0.5) * 2^-24 in (0,1)
 // One thread per (env, placement unit): base station, CUE, or DUE pair (transmitter, then its receiver's rejection loop).
+// reset_masked_kernel re-places only the envs marked pending, each at its own episode, with the same units and draws.
 #include "d2d_internal.h"
 
 namespace d2d {
@@ -81,15 +82,9 @@ __device__ __forceinline__ float2 draw(const ResetArgs& a, unsigned env, unsigne
     return disc_offset(w[0], w[1], radius);
 }
 
-// One thread per placement UNIT of an env: the base station, one CUE, or one DUE PAIR.  A pair thread draws the
-// transmitter and then runs the receiver's rejection loop against it, so the anchor is drawn once (a thread per device
-// would re-derive it) and a wave holds one kind of work instead of alternating transmitter / receiver lanes.
-__global__ __launch_bounds__(256) void reset_kernel(const ResetArgs a) {
-    const unsigned gid = blockIdx.x * 256u + threadIdx.x;
-    if (gid >= a.total) return;
-    unsigned b = __umulhi(gid, a.units_magic);                           // gid / units: estimate is exact or one short
-    unsigned u = gid - b * a.units;
-    if (u >= a.units) { u -= a.units; ++b; }
+// Placement unit u of env b (the base station, one CUE, or one DUE PAIR) at the episode a.episode: the pair draws its transmitter
+// and then runs the receiver's rejection loop against it, so the anchor is drawn once (a thread per device would re-derive it).
+__device__ __forceinline__ void place_unit(const ResetArgs& a, unsigned b, unsigned u) {
     const unsigned env = (unsigned)(a.env_offset + b);
     const size_t base = (size_t)b * (size_t)a.D;
     if (u <= (unsigned)a.C) {                                            // base station (origin, simulator.py:63-64) or a CUE
@@ -123,17 +118,66 @@ __global__ __launch_bounds__(256) void reset_kernel(const ResetArgs a) {
     if (a.lpos) a.lpos[(size_t)b * (size_t)a.N + (u - 1u)] = make_float4(tx.x, tx.y, rx.x, rx.y);
 }
 
-hipError_t launch_reset(int B, int D, int C, float cell_radius, float d2d_radius, unsigned long long seed,
-                        unsigned long long episode, unsigned long long env_offset, const unsigned char* fixed_mask,
-                        const float* fixed_xy, float* pos_x, float* pos_y, float4* lpos, int N, hipStream_t stream) {
-    ResetArgs a;
+// Every env: one thread per placement unit.
+__global__ __launch_bounds__(256) void reset_kernel(const ResetArgs a) {
+    const unsigned gid = blockIdx.x * 256u + threadIdx.x;
+    if (gid >= a.total) return;
+    unsigned b = __umulhi(gid, a.units_magic);                           // gid / units: estimate is exact or one short
+    unsigned u = gid - b * a.units;
+    if (u >= a.units) { u -= a.units; ++b; }
+    place_unit(a, b, u);
+}
+
+// What the per-env reset (d2d_reset_positions with D2D_EPISODE_PER_ENV) adds to the full reset's arguments.
+struct MaskedArgs {
+    const int* pending;          // [B] non-zero: reset this env (D2D_BUF_RESET_PENDING)
+    const unsigned* episode;     // [B] the episode index of its reset (D2D_BUF_EPISODE)
+    float* lo_x;                 // [B, D] low parts of exact positions, or null: zeroed for the reset envs
+    float* lo_y;
+    const int4* rec_a;           // link records, or null: a non-standard link list, whose rows of the reset envs are gathered here
+    float4* rows;                // [B, N] position rows of that gather
+    float4* rows_lo;             // [B, N] low parts of the rows, or null: zeroed for the reset envs
+};
+
+// Pending envs only, one wave per env: a wave whose env is not pending leaves at its first (scalar) load, so a step in which no
+// env resets costs B / 4 near-empty workgroups.  The units of a reset env are the full reset's, at the env's own episode.
+__global__ __launch_bounds__(256) void reset_masked_kernel(const ResetArgs a, const MaskedArgs m) {
+    const unsigned b = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
+    if (b >= (unsigned)a.B || __builtin_amdgcn_readfirstlane(m.pending[b]) == 0) return;
+    const unsigned lane = threadIdx.x & 63u;
+    ResetArgs e = a;
+    e.episode = __builtin_amdgcn_readfirstlane(m.episode[b]);
+    for (unsigned u = lane; u < a.units; u += 64u) place_unit(e, b, u);
+    const size_t pb = (size_t)b * (size_t)a.D, lb = (size_t)b * (size_t)a.N;
+    if (m.lo_x) {
+        for (unsigned k = lane; k < (unsigned)a.D; k += 64u) { m.lo_x[pb + k] = 0.f; m.lo_y[pb + k] = 0.f; }
+    }
+    if (m.rec_a) {
+        // the rows read positions other lanes of this wave just wrote: all of the wave's stores before any of its loads (one CU,
+        // one L1: workgroup scope is enough)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        for (unsigned i = lane; i < (unsigned)a.N; i += 64u) {
+            const int4 ra = m.rec_a[i];
+            const int txd = ra.x & D2D_REC_TXDEV_MASK, rxd = ra.y;
+            m.rows[lb + i] = make_float4(a.pos_x[pb + txd], a.pos_y[pb + txd], a.pos_x[pb + rxd], a.pos_y[pb + rxd]);
+        }
+    }
+    if (m.rows_lo) {
+        for (unsigned i = lane; i < (unsigned)a.N; i += 64u) m.rows_lo[lb + i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
+static hipError_t reset_args(int B, int D, int C, float cell_radius, float d2d_radius, unsigned long long seed,
+                             unsigned long long episode, unsigned long long env_offset, const unsigned char* fixed_mask,
+                             const float* fixed_xy, float* pos_x, float* pos_y, float4* lpos, int N, ResetArgs& a) {
     a.lpos = lpos; a.N = N;
     a.B = B; a.D = D; a.C = C;
     a.units = 1u + (unsigned)C + (unsigned)((D - 1 - C) / 2);
     a.units_magic = a.units == 1u ? 0xFFFFFFFFu : (unsigned)(0x100000000ull / a.units);   // one short at most: the kernel corrects
     const unsigned long long total = (unsigned long long)B * a.units;
     if (total >= 0xFFFFFF00ull) return hipErrorInvalidValue;
-    if (total == 0) return hipSuccess;
     a.total = (unsigned)total;
     a.cell_radius = cell_radius; a.d2d_radius = d2d_radius;
     a.seed_lo = (unsigned)(seed & 0xFFFFFFFFull); a.seed_hi = (unsigned)(seed >> 32);
@@ -142,7 +186,29 @@ hipError_t launch_reset(int B, int D, int C, float cell_radius, float d2d_radius
     a.fixed_mask = fixed_mask; a.fixed_xy = fixed_xy;
     a.pos_x = pos_x; a.pos_y = pos_y;
     a.max_tries = 64;
+    return hipSuccess;
+}
+
+hipError_t launch_reset(int B, int D, int C, float cell_radius, float d2d_radius, unsigned long long seed,
+                        unsigned long long episode, unsigned long long env_offset, const unsigned char* fixed_mask,
+                        const float* fixed_xy, float* pos_x, float* pos_y, float4* lpos, int N, hipStream_t stream) {
+    ResetArgs a;
+    const hipError_t e = reset_args(B, D, C, cell_radius, d2d_radius, seed, episode, env_offset, fixed_mask, fixed_xy, pos_x, pos_y,
+                                    lpos, N, a);
+    if (e != hipSuccess || a.total == 0) return e;
     hipLaunchKernelGGL(reset_kernel, dim3((a.total + 255u) / 256u), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_reset_masked(int B, int D, int C, float cell_radius, float d2d_radius, unsigned long long seed,
+                               unsigned long long env_offset, const unsigned char* fixed_mask, const float* fixed_xy, float* pos_x,
+                               float* pos_y, float4* lpos, int N, const int* pending, const unsigned* episode, float* lo_x, float* lo_y,
+                               const int4* rec_a, float4* rows, float4* rows_lo, hipStream_t stream) {
+    ResetArgs a;
+    const hipError_t e = reset_args(B, D, C, cell_radius, d2d_radius, seed, 0, env_offset, fixed_mask, fixed_xy, pos_x, pos_y, lpos, N, a);
+    if (e != hipSuccess || a.total == 0) return e;
+    const MaskedArgs m{pending, episode, lo_x, lo_y, rec_a, rows, rows_lo};
+    hipLaunchKernelGGL(reset_masked_kernel, dim3(((unsigned)B + 3u) / 4u), dim3(256), 0, stream, a, m);
     return hipGetLastError();
 }
 

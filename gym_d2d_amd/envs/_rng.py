@@ -43,6 +43,24 @@ def uniform_ints_numpy(seed: int, episode: int, first_env: int, num_envs: int, n
     return ((x >> np.uint64(11)) % high[None, :]).astype(np.int32)
 
 
+def uniform_ints_numpy_per_env(seed: int, episodes, first_env: int, num_cols: int, high) -> np.ndarray:
+    """int32 [len(episodes), num_cols]: row b is uniform_ints_numpy(seed, episodes[b], first_env, ...)'s row b - the random actions
+    of a per-env reset (VecD2DEnv(autoreset=True), libd2d_episode.so's d2d_episode_merge_actions), each env at its own episode."""
+    episodes = np.asarray(episodes, dtype=np.uint64).reshape(-1)
+    high = np.broadcast_to(np.asarray(high, dtype=np.uint64), (num_cols,))
+    env = (np.arange(len(episodes), dtype=np.uint64) + np.uint64(first_env))[:, None]
+    col = np.arange(num_cols, dtype=np.uint64)[None, :]
+
+    def mix(x):
+        x = (x ^ (x >> np.uint64(30))) * np.uint64(_M1)
+        x = (x ^ (x >> np.uint64(27))) * np.uint64(_M2)
+        return x ^ (x >> np.uint64(31))
+    with np.errstate(over='ignore'):
+        key = mix(np.uint64(_mix_int(seed)) ^ ((episodes + np.uint64(1)) * np.uint64(_GOLDEN)))[:, None]
+        x = mix(key + (env * np.uint64(num_cols) + col + np.uint64(1)) * np.uint64(_GOLDEN))
+    return ((x >> np.uint64(11)) % high[None, :]).astype(np.int32)
+
+
 def uniform_ints_torch(torch, seed: int, episode: int, first_env: int, num_envs: int, num_cols: int, high, device):
     """Same values as uniform_ints_numpy, computed on `device` (int64 holds the uint64 bit patterns; logical right
     shifts are arithmetic shifts with the sign extension masked off)."""

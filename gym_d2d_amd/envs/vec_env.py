@@ -8,6 +8,9 @@ same reward / obs definitions) but speaks arrays:
     obs = env.reset(seed=1234)                        # [B, N, 6N] float32 (LinearObsFunction)
     obs, rewards, dones, info = env.step(actions)     # actions int32 [B, N]; rewards [B, N]; dones [B] bool
 
+    env = VecD2DEnv(config, num_envs=4096, autoreset=True)  # done envs start their next episode inside step(), on the GPU
+    obs = env.reset(seed=1234, elapsed=np.arange(4096) % 10)  # staggered: env b's first episode is 10 - elapsed[b] steps
+
 With PyTorch-ROCm present all arrays are CUDA tensors that alias the library's HBM buffers (zero copy: the tensors are
 allocated by torch and bound into the handle, kernels run on torch's current stream).  Without torch they are NumPy
 copies.  Agent order along N: all CUE uplinks, then all DUE sidelinks (d2d_env.py:54-60).
@@ -20,7 +23,7 @@ from typing import Optional
 import numpy as np
 
 from .. import _native
-from ..path_loss_table import PER_STEP
+from ..path_loss_table import NATIVE, PER_STEP
 from ..simulator import BASE_STATION_ID, Simulator
 from ..traffic_model import DownlinkTrafficModel
 from . import _rng
@@ -41,7 +44,7 @@ class VecD2DEnv:
     def __init__(self, env_config: Optional[dict] = None, num_envs: Optional[int] = None, *,
                  cue_actions: str = 'agent', use_torch: Optional[bool] = None, first_env: int = 0,
                  export_actions: bool = True, reward_per_env: bool = False, placement_trials: int = 0,
-                 placement_budget_bytes: int = 1 << 30) -> None:
+                 placement_budget_bytes: int = 1 << 30, autoreset: bool = False) -> None:
         """cue_actions: 'agent' - step() takes actions for CUEs and DUEs [B, C+P] (reference behaviour);
         'traffic' - CUE links follow the env's traffic model (round-robin RB at max power,
         traffic_model.py:15-22): their (rb, pwr) are constants of the kernel's link records
@@ -72,6 +75,17 @@ class VecD2DEnv:
 
         step()'s `dones` on the torch path is one of two preallocated CONSTANT tensors (all False / all True), shared by
         every call: treat it as read-only (clone it before an in-place update).
+
+        autoreset: True - next-step autoreset (gymnasium's NEXT_STEP): the step() after the one that returned dones[b] = True
+        ignores env b's action row and resets env b on the device instead - new positions at its own episode index, the reset's
+        uniformly random actions, one step with them - and returns that step's obs and planes, reward 0, done False and
+        info['reset'][b] = True.  From each env's side the sequence is the reference loop `obs = reset() if done else step(a)`;
+        episode k of env b draws what the k-th reset() of a lockstep env draws (same seed, same global env index).  Nothing is
+        synchronised: `dones` and info['reset'] are bool [B] device tensors the library writes every step - the SAME two tensor
+        objects on every call, like the other aliased outputs (clone them to keep a step's values).  reset(elapsed=...) staggers
+        the first episodes; request_reset(mask) resets chosen envs at the next step.  Needs the torch path and a path-loss model
+        the kernels evaluate per step (the native laws, ShadowingPathLoss, a per-step ArrayPathLoss): a table evaluated once per
+        reset, or pinned device_config coordinates float32 cannot hold, would need the host between steps (ValueError).
 
         env_config['obs_dtype'] = 'float64' returns observations in the reference's dtype (obs_fn.py:51 builds float64
         arrays); the default float32 is the kernels' own block, zero copy.
@@ -158,6 +172,36 @@ class VecD2DEnv:
         self._placement_trials = placement_trials if self.use_torch and self._placement_target is not None else 0
         self._placement_budget = int(placement_budget_bytes)
         self.placement = None                      # after the trials: {'buffer': ..., 'us_per_step': [...], 'chosen': k}
+        self.autoreset = bool(autoreset)
+        if self.autoreset:
+            self._setup_autoreset()
+
+    def _setup_autoreset(self) -> None:
+        """Refuse what a device-side per-env reset cannot serve, then allocate the per-env bookkeeping: pending / episode are bound
+        into the handle (D2D_BUF_RESET_PENDING / D2D_BUF_EPISODE), elapsed / done / reset belong to libd2d_episode.so's kernels."""
+        sim = self.simulator
+        if not self.use_torch:
+            raise ValueError('autoreset=True needs the torch path (use_torch): the per-env bookkeeping lives in device tensors')
+        route = sim.path_loss_table.route
+        if route not in (NATIVE, PER_STEP):
+            raise ValueError(f"autoreset=True cannot serve the '{route}' path-loss route: its table is evaluated once per reset, "
+                             'which a device-side reset inside step() cannot follow without the host (use a per-step ArrayPathLoss '
+                             'or a native model)')
+        mask, xy = sim.fixed_positions()
+        if mask.any() and (xy != xy.astype(np.float32)).any():
+            raise ValueError('autoreset=True cannot pin device_config coordinates that float32 cannot hold: they need the host '
+                             'upload of a full reset')
+        sim.path_loss_table.device_resets = True
+        h, b, dev = sim.handle, self.num_envs, self.device
+        for name, which in (('pending', _native.BUF_RESET_PENDING), ('episode', _native.BUF_EPISODE)):
+            t = torch.zeros(b, dtype=torch.int32, device=dev)
+            h.bind_buffer(which, t.data_ptr(), t.numel() * t.element_size())
+            self._t[name] = t
+        self._t['elapsed'] = torch.zeros(b, dtype=torch.int32, device=dev)
+        self._t['done'] = torch.zeros(b, dtype=torch.bool, device=dev)
+        self._t['reset'] = torch.zeros(b, dtype=torch.bool, device=dev)
+        self._t['high'] = torch.as_tensor(np.asarray(self._initial_action_highs(), dtype=np.int32), device=dev)
+        self._view_cache = None
 
     # ------------------------------------------------------------------ buffers
     def _bind_torch_buffers(self) -> None:
@@ -241,12 +285,25 @@ class VecD2DEnv:
         n_due = self.config.num_rbs * self.num_pwr_actions['due']
         return ([n_cue] * self.num_cues if self.cue_actions == 'agent' else []) + [n_due] * self.num_due_pairs
 
-    def reset(self, seed: Optional[int] = None):
+    def reset(self, seed: Optional[int] = None, *, elapsed=None):
         """New positions for every env (device-side sampler), then one step with uniformly random actions on every
         agent-driven link to produce the initial SINRs (d2d_env.py:45-60).  Both draws are counter-based and keyed
-        by global env index (first_env + b)."""
+        by global env index (first_env + b).
+
+        elapsed (autoreset only): int [B] in [0, EPISODE_LENGTH) - env b's first episode then ends after EPISODE_LENGTH -
+        elapsed[b] steps.  Without a seed, the episode index continues after the largest one any env has drawn."""
+        if elapsed is not None:
+            if not self.autoreset:
+                raise ValueError('elapsed staggers the episodes of autoreset=True; a lockstep env has one episode clock')
+            elapsed = np.asarray(elapsed.cpu() if torch is not None and torch.is_tensor(elapsed) else elapsed)
+            if elapsed.shape != (self.num_envs,) or elapsed.dtype.kind not in 'iu' or \
+                    (elapsed.size and (elapsed.min() < 0 or elapsed.max() >= EPISODE_LENGTH)):
+                raise ValueError(f'elapsed must be ints [{self.num_envs}] in [0, {EPISODE_LENGTH})')
         if seed is not None:
             self._seed, self._episode = int(seed), 0
+        elif self.autoreset:
+            # per-env resets drew episodes up to (not including) the largest counter: continue after them (reset() syncs anyway)
+            self._episode = max(self._episode, int(self._t['episode'].max()))
         self.num_steps = 0
         if self.use_torch:
             self._follow_torch_stream()
@@ -263,6 +320,15 @@ class VecD2DEnv:
                 if self.num_agents else np.zeros((self.num_envs, 0), np.int32)
             self.simulator.step_arrays(a)
         self._episode += 1
+        if self.autoreset:
+            self._t['episode'].fill_(self._episode)
+            self._t['pending'].zero_()
+            self._t['done'].zero_()
+            self._t['reset'].zero_()
+            if elapsed is None:
+                self._t['elapsed'].zero_()
+            else:
+                self._t['elapsed'].copy_(torch.as_tensor(elapsed.astype(np.int32), device=self.device))
         self.simulator.check_flags()
         if self._placement_trials > 1 and self.placement is None:
             self._choose_obs_placement(self._placement_trials)
@@ -344,6 +410,8 @@ class VecD2DEnv:
         Asynchronous on the torch path: nothing here waits for the GPU, so error flags are NOT checked per step -
         see status_flags()."""
         sim = self.simulator
+        if self.autoreset:
+            return self._step_autoreset(actions)
         if self.use_torch:
             self._follow_torch_stream()
             src = actions if torch.is_tensor(actions) else torch.as_tensor(np.asarray(actions), device=self.device)
@@ -370,6 +438,54 @@ class VecD2DEnv:
         info = {'rb': view.rb, 'tx_pwr_dbm': view.pwr, 'snr_db': view.snr_db, 'sinr_db': view.sinr_db,
                 'rate_bps': view.rate_bps, 'capacity_mbps': view.capacity_mbps}
         return obs, rewards, np.full(self.num_envs, done), info
+
+    def _step_autoreset(self, actions):
+        """One step of autoreset=True, enqueued on torch's current stream: the pending envs' positions (masked reset) -> a per-step
+        path-loss table for the step -> the action rows, pending envs' replaced by their reset's random actions, into the bound
+        action buffer -> d2d_step -> the per-env counters, dones and next pending set (libd2d_episode.so).  No synchronisation."""
+        sim, t = self.simulator, self._t
+        h = sim.handle
+        self._follow_torch_stream()
+        src = actions if torch.is_tensor(actions) else torch.as_tensor(np.asarray(actions), device=self.device)
+        if tuple(src.shape) != (self.num_envs, self.num_agents):
+            raise ValueError(f'actions must be [{self.num_envs},{self.num_agents}], got {tuple(src.shape)}')
+        if src.dtype != torch.int32 or not src.is_contiguous() or src.device != self.device:
+            src = src.to(device=self.device, dtype=torch.int32).contiguous()
+        stream = self._stream_ptr
+        h.reset_positions(self._seed, _native.EPISODE_PER_ENV)
+        sim.prepare_step()                                    # a per-step ArrayPathLoss: this step's table, at the new positions
+        if self.num_agents:
+            _native.episode_merge_actions(src.data_ptr(), t['actions'].data_ptr(), t['pending'].data_ptr(), t['episode'].data_ptr(),
+                                          t['high'].data_ptr(), self.num_envs, self.num_agents, self.first_env, self._seed, stream)
+        h.step()
+        self.num_steps += 1
+        view = self._view()
+        native = self._native_reward
+        reward = view.reward if native else None
+        _native.episode_advance(t['pending'].data_ptr(), t['episode'].data_ptr(), t['elapsed'].data_ptr(), t['done'].data_ptr(),
+                                t['reset'].data_ptr(), reward.data_ptr() if native else 0,
+                                1 if self.reward_per_env else self.num_links, self.num_envs, EPISODE_LENGTH, stream)
+        obs = self._observe(view)
+        if native:
+            rewards = view.reward
+        else:
+            rewards = self.reward_fn.compute(view)
+            reset = t['reset'].view((-1,) + (1,) * (rewards.dim() - 1))
+            rewards = torch.where(reset, torch.zeros((), dtype=rewards.dtype, device=rewards.device), rewards)
+        info = dict(self._info)
+        info['reset'] = t['reset']
+        return obs, rewards, t['done'], info
+
+    def request_reset(self, mask) -> None:
+        """Reset the envs mask marks (bool [B], tensor or ndarray) at the next step() instead of stepping them - device-side and
+        asynchronous (autoreset=True only)."""
+        if not self.autoreset:
+            raise ValueError('request_reset needs autoreset=True')
+        m = torch.as_tensor(mask, device=self.device)
+        if tuple(m.shape) != (self.num_envs,) or m.dtype != torch.bool:
+            raise ValueError(f'mask must be bool [{self.num_envs}]')
+        self._follow_torch_stream()
+        self._t['pending'].masked_fill_(m, 1)
 
     def _observe(self, view):
         obs = self.obs_fn.compute(view) if self._array_obs else view.obs

@@ -64,6 +64,9 @@ class PathLossTable:
         self.covered = (set(), set())               # device_table: the transmitters and receivers the bound table holds
         self.cols = self.live = None                # per_step: per-link coordinates; the live table, held while steps may read it
         self.live_bound = False                     # per_step: self.live is bound for the current link list
+        # per_step: positions may move on the device between steps (VecD2DEnv(autoreset=True) resets envs inside step()): the
+        # per-link coordinates are gathered from POS_X / POS_Y again before every step
+        self.device_resets = False
 
     def install(self) -> None:
         """Hand the native route's law to the handle and draw the seeds (again: restarts the built-in shadowing's stream)."""
@@ -106,8 +109,8 @@ class PathLossTable:
             with torch.cuda.device(dev):
                 stream = torch.cuda.current_stream(dev)
                 same = self.stream is not None and self.stream == stream.cuda_stream
-                if self.cols is None:
-                    self.cols = self._link_coordinates(torch, dev)
+                if self.cols is None or self.device_resets:
+                    self.cols = self._link_coordinates(torch, dev, sync=not same)
                 if not same and self.live is not None:
                     self.handle.synchronize()       # the last step still reads the table this evaluation overwrites
                 if not self.live_bound:
@@ -170,13 +173,14 @@ class PathLossTable:
             for d, p in zip(self.devices, saved):
                 d.set_position(p)
 
-    def _link_coordinates(self, torch, dev):
+    def _link_coordinates(self, torch, dev, sync: bool = True):
         """(tx_x, tx_y, rx_x, rx_y) [B, N] of every link as tensors on `dev`: host-supplied positions as given (float64 possible),
-        the Device objects' float64 positions for one env, else POS_X / POS_Y where the device-side reset wrote them."""
+        the Device objects' float64 positions for one env, else POS_X / POS_Y where the device-side reset wrote them (sync = False:
+        the handle runs on torch's current stream, which orders the gather after the reset)."""
         jt, jr = (torch.as_tensor(j.astype(np.int64), device=dev) for j in (self.link_tx, self.link_rx))
         if self.positions is not None:
             p = torch.as_tensor(self.positions, device=dev)
-        elif self.num_envs == 1:
+        elif self.num_envs == 1 and not self.device_resets:
             # one env: the reference's own float64 coordinates (the kernels take them as exact (hi, lo) pairs)
             p = torch.as_tensor(np.array([d.position.as_tuple() for d in self.devices], dtype=np.float64)[None], device=dev)
         else:
@@ -185,7 +189,8 @@ class PathLossTable:
                        'data': (self.handle.get_buffer(which)[0], False)}
                 return torch.as_tensor(SimpleNamespace(__cuda_array_interface__=cai), device=dev)
             px, py = plane(_native.BUF_POS_X), plane(_native.BUF_POS_Y)
-            self.handle.synchronize()               # the sampler wrote them on the handle's stream; torch reads on its own
+            if sync or not self.device_resets:
+                self.handle.synchronize()           # the sampler wrote them on the handle's stream; torch reads on its own
             return (px[:, jt], py[:, jt], px[:, jr], py[:, jr])
         return (p[:, jt, 0], p[:, jt, 1], p[:, jr, 0], p[:, jr, 1])
 

@@ -25,8 +25,9 @@
 extern "C" {
 #endif
 
-#define D2D_ABI_VERSION 6      /* 5: float64 positions (d2d_set_positions_f64), device-resident path-loss table (d2d_set_path_loss_link_table_dev)
-                                  6: live dB table (D2D_PL_TABLE_LIVE), D2D_FLAG_PATH_LOSS_DOMAIN */
+#define D2D_ABI_VERSION 7      /* 5: float64 positions (d2d_set_positions_f64), device-resident path-loss table (d2d_set_path_loss_link_table_dev)
+                                  6: live dB table (D2D_PL_TABLE_LIVE), D2D_FLAG_PATH_LOSS_DOMAIN
+                                  7: per-env resets (D2D_BUF_RESET_PENDING, D2D_BUF_EPISODE, D2D_EPISODE_PER_ENV) */
 #define D2D_MAX_LINKS 2048      /* links per env the step kernel's LDS staging is sized for */
 #define D2D_UNIQUE_ID_BYTES 128 /* size of an RCCL unique id (ncclUniqueId)                  */
 
@@ -84,7 +85,11 @@ typedef enum d2d_buffer {
                                positions from here once per episode and (sinr, snr) from the planes     */
     D2D_BUF_REWARD_ENV = 14,/* f32 [B]     SystemCapacity's one scalar per env (reward_fn.py:42-44),
                                written instead of D2D_BUF_REWARD under D2D_REWARD_PER_ENV             */
-    D2D_BUF_COUNT = 15
+    D2D_BUF_RESET_PENDING = 15, /* i32 [B] non-zero: d2d_reset_positions(.., D2D_EPISODE_PER_ENV, ..) resets
+                               this env (zero-filled when the library allocates it)                 */
+    D2D_BUF_EPISODE = 16,   /* u32 [B]     the episode index of each env's next per-env reset (zero-filled
+                               when the library allocates it)                                       */
+    D2D_BUF_COUNT = 17
 } d2d_buffer;
 
 #define D2D_FLAG_ZERO_DISTANCE 1u /* an interacting tx/rx pair at distance 0: the reference raises
@@ -295,6 +300,13 @@ int d2d_positions_changed(d2d_handle* h);
  * (simulator.py:65-66).  Asynchronous.                                                             */
 int d2d_reset_positions(d2d_handle* h, uint64_t seed, uint64_t episode, const uint8_t* fixed_mask,
                         const float* fixed_xy);
+/* episode = D2D_EPISODE_PER_ENV: reset only the envs whose D2D_BUF_RESET_PENDING entry is non-zero, env b at episode
+ * D2D_BUF_EPISODE[b] - positions and D2D_BUF_LINK_POS rows bit-identical to a full reset at that episode, every other env's
+ * bytes untouched.  The buffers are read, not changed (the caller clears them: libd2d_episode.so's d2d_episode_advance).
+ * Pinned devices are those of the last full reset (already on the device); fixed_mask / fixed_xy must be NULL.  Float64
+ * positions (d2d_set_positions_f64) stay on: the reset envs' low parts become zero, the other envs keep theirs.  Never
+ * synchronises: meant to be enqueued before every step ("Autoreset").                                           */
+#define D2D_EPISODE_PER_ENV ((uint64_t)-1)
 /* Global index of this handle's env 0 (multi-GPU sharding of one logical batch); default 0.        */
 int d2d_set_env_offset(d2d_handle* h, uint64_t first_env);
 

@@ -1,0 +1,285 @@
+"""VecD2DEnv(autoreset=True): next-step autoreset on the GPU, against the reference loop `obs = reset() if done else step(a)` run by a
+lockstep env, per env against single-env envs, at the C ABI (d2d_reset_positions with D2D_EPISODE_PER_ENV), and sharded.  Every
+comparison is bit for bit."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+SEED = 5
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def _cfg(**extra):
+    cfg = {'num_rbs': 25, 'num_cues': 25, 'num_due_pairs': 25, 'seed': 7}
+    cfg.update(extra)
+    return cfg
+
+
+def _actions(env, gen):
+    """int32 [B, A] uniform in every column's action range."""
+    torch = _torch()
+    highs = torch.as_tensor(env._initial_action_highs(), device=env.device)
+    u = torch.rand((env.num_envs, env.num_agents), generator=gen, device=env.device, dtype=torch.float64)
+    return (u * highs).to(torch.int32)
+
+
+def _outputs(env, obs, info=None):
+    """Everything a step shows, cloned: obs (or the planes), the info planes and the link position rows."""
+    torch = _torch()
+    out = {}
+    if isinstance(obs, tuple):
+        for k, o in enumerate(obs):
+            out[f'obs{k}'] = o.clone()
+    else:
+        out['obs'] = obs.clone()
+    view = env._view()
+    for name in ('sinr_db', 'snr_db', 'rate_bps', 'capacity_mbps', 'rb', 'pwr'):
+        v = getattr(view, name)
+        if v is not None:
+            out[name] = v.clone()
+    out['link_pos'] = env.link_positions().clone()
+    torch.cuda.synchronize()
+    return out
+
+
+def _bits(t):
+    return t.contiguous().view(-1).view(_torch().uint8).cpu().numpy()
+
+
+def _assert_bits(a, b, what):
+    np.testing.assert_array_equal(_bits(a), _bits(b), err_msg=what)
+
+
+def _assert_outputs(got, want, what, row=None):
+    assert got.keys() == want.keys(), what
+    for k in got:
+        g = got[k] if row is None else got[k][row:row + 1]
+        assert tuple(g.shape) == tuple(want[k].shape) and g.dtype == want[k].dtype, (what, k)
+        _assert_bits(g, want[k], f'{what}: {k}')
+
+
+@pytest.mark.parametrize('name', ['linear_64', 'planes_per_env_32'])
+def test_autoreset_equals_the_lockstep_reset_loop(name):
+    torch = _torch()
+    from gym_d2d_amd.envs import VecD2DEnv
+    from gym_d2d_amd.envs.obs_fn import SignalPlanesObsFunction
+    if name == 'linear_64':
+        cfg, b, kw = _cfg(), 64, {}
+    else:
+        cfg, b, kw = _cfg(num_rbs=16, num_cues=96, num_due_pairs=96, obs_fn=SignalPlanesObsFunction), 32, {'reward_per_env': True}
+    auto = VecD2DEnv(dict(cfg), num_envs=b, autoreset=True, **kw)
+    lock = VecD2DEnv(dict(cfg), num_envs=b, **kw)
+    _assert_outputs(_outputs(auto, auto.reset(seed=SEED)), _outputs(lock, lock.reset(seed=SEED)), 'reset')
+    gen = torch.Generator(device=auto.device).manual_seed(1)
+    lock_done = False
+    for t in range(1, 37):
+        a = _actions(auto, gen)
+        obs, rew, dones, info = auto.step(a)
+        got = _outputs(auto, obs)
+        rew, dones, was_reset = rew.clone(), dones.clone(), info['reset'].clone()
+        if lock_done:
+            want = _outputs(lock, lock.reset())
+            assert bool(was_reset.all()), t
+            assert not bool(dones.any()), t
+            assert bool((rew == 0).all()), t
+            assert t % 11 == 0
+            lock_done = False
+        else:
+            lobs, lrew, ldones, _ = lock.step(a)
+            want = _outputs(lock, lobs)
+            assert not bool(was_reset.any()), t
+            _assert_bits(rew, lrew, f'step {t}: reward')
+            assert bool((dones == ldones).all()), t
+            lock_done = bool(ldones.all())
+        _assert_outputs(got, want, f'step {t}')
+    auto.close(); lock.close()
+
+
+def _models():
+    import sys
+    from pathlib import Path
+    from gym_d2d_amd.path_loss import AreaType, CostHataPathLoss, LogDistancePathLoss, ShadowingPathLoss
+    sys.path.insert(0, str(Path(__file__).resolve().parent.parent / 'examples'))
+    from per_step_path_loss import ShadowedCostHata
+
+    class Ple(LogDistancePathLoss):
+        def __init__(self, f):
+            super().__init__(f, ple=3.3)
+
+    class Urban(CostHataPathLoss):
+        def __init__(self, f):
+            super().__init__(f, AreaType.URBAN)
+    return {'log_distance': Ple, 'cost_hata': Urban, 'shadowing': ShadowingPathLoss, 'per_step_array': ShadowedCostHata}
+
+
+@pytest.mark.parametrize('model', ['log_distance', 'cost_hata', 'shadowing', 'per_step_array'])
+def test_staggered_and_requested_resets_match_one_env_each(model):
+    """elapsed = arange(B) % 10 and two request_reset calls: env b equals VecD2DEnv(num_envs=1, first_env=b) fed env b's action rows,
+    calling reset() exactly where env b was reset."""
+    torch = _torch()
+    from gym_d2d_amd.envs import VecD2DEnv
+    b, steps = 8, 26
+    cfg = _cfg(num_rbs=6, num_cues=6, num_due_pairs=7, path_loss_model=_models()[model])
+    env = VecD2DEnv(dict(cfg), num_envs=b, autoreset=True)
+    first = _outputs(env, env.reset(seed=SEED, elapsed=np.arange(b) % 10))
+    gen = torch.Generator(device=env.device).manual_seed(2)
+    rng = np.random.default_rng(3)
+    acts, outs, rews, resets, dones = [], [], [], [], []
+    for t in range(1, steps + 1):
+        if t in (7, 16):
+            env.request_reset(rng.random(b) < 0.5)
+        a = _actions(env, gen)
+        obs, rew, done, info = env.step(a)
+        outs.append(_outputs(env, obs)); rews.append(rew.clone()); resets.append(info['reset'].clone().cpu().numpy())
+        dones.append(done.clone().cpu().numpy()); acts.append(a)
+    env.close()
+    resets, dones = np.array(resets), np.array(dones)
+    for e in range(b):                          # the stagger: env e's first episode is 10 - e % 10 steps (if no request came first)
+        if 10 - e % 10 < 7:
+            assert dones[:, e].argmax() + 1 == 10 - e % 10, e
+    assert resets.sum() > b
+    for e in range(b):
+        one = VecD2DEnv(dict(cfg), num_envs=1, first_env=e)
+        _assert_outputs(first, _outputs(one, one.reset(seed=SEED)), f'{model} env {e} reset', row=e)
+        for t in range(steps):
+            if resets[t, e]:
+                want = _outputs(one, one.reset())
+                assert float(rews[t][e].abs().max()) == 0.0
+            else:
+                obs, rew, _, _ = one.step(acts[t][e:e + 1])
+                want = _outputs(one, obs)
+                _assert_bits(rews[t][e:e + 1], rew, f'{model} env {e} step {t + 1}: reward')
+            _assert_outputs(outs[t], want, f'{model} env {e} step {t + 1}', row=e)
+        one.close()
+
+
+def _handle_sim(b, downlink=False):
+    from gym_d2d_amd.simulator import BASE_STATION_ID, Simulator
+    from gym_d2d_amd.traffic_model import DownlinkTrafficModel
+    cfg = dict(num_rbs=5, num_cues=6, num_due_pairs=9, num_envs=b)
+    if downlink:
+        cfg['traffic_model'] = DownlinkTrafficModel
+    sim = Simulator(cfg, max_links=15)
+    if downlink:
+        sim.set_links([(BASE_STATION_ID, c) for c in sim.devices.cues.keys()] + list(sim.devices.dues.keys()))
+    else:
+        sim.set_links(sim.default_link_keys())
+    return sim
+
+
+def _state(h, native):
+    return [h.download(w) for w in (native.BUF_POS_X, native.BUF_POS_Y, native.BUF_LINK_POS)]
+
+
+@pytest.mark.parametrize('downlink', [False, True])
+def test_masked_reset_at_the_abi(native, downlink):
+    b = 16
+    pending = (np.arange(b) % 3 == 1).astype(np.int32)
+    episode = np.where(np.arange(b) % 2 == 0, 3, 5).astype(np.uint32)
+    sim = _handle_sim(b, downlink)
+    h = sim.handle
+    h.reset_positions(SEED, 0)
+    before = _state(h, native)                  # also brings the link rows up to date: the masked reset keeps them current
+    h.upload(native.BUF_RESET_PENDING, pending)
+    h.upload(native.BUF_EPISODE, episode)
+    h.reset_positions(SEED, native.EPISODE_PER_ENV)
+    after = _state(h, native)
+    ref = _handle_sim(b, downlink)
+    want = {}
+    for ep in (3, 5):
+        ref.handle.reset_positions(SEED, ep)
+        want[ep] = _state(ref.handle, native)
+    for e in range(b):
+        for k in range(3):
+            src = want[int(episode[e])][k] if pending[e] else before[k]
+            np.testing.assert_array_equal(after[k][e].view(np.uint32), src[e].view(np.uint32), err_msg=f'env {e} buffer {k}')
+    # the buffers are read, not changed
+    np.testing.assert_array_equal(h.download(native.BUF_RESET_PENDING), pending)
+    np.testing.assert_array_equal(h.download(native.BUF_EPISODE), episode)
+    sim.handle.close(); ref.handle.close()
+
+
+def test_masked_reset_zeroes_the_low_parts_of_reset_envs_only(native):
+    """After float64 positions, a masked reset leaves the other envs' exact coordinates and makes the reset envs' plain float32:
+    the step equals one on a handle given those coordinates by set_positions_f64."""
+    b = 12
+    pending = (np.arange(b) % 4 == 2).astype(np.int32)
+    sim = _handle_sim(b)
+    h = sim.handle
+    h.reset_positions(SEED, 0)
+    pos = np.stack([h.download(native.BUF_POS_X), h.download(native.BUF_POS_Y)], axis=-1).astype(np.float64)
+    pos += np.random.default_rng(4).uniform(-1e-4, 1e-4, pos.shape)            # low parts float32 cannot hold
+    pos[:, 0] = 0.0
+    sim.set_positions(pos)
+    raw = np.random.default_rng(5).integers(0, 5 * 4, (b, 15)).astype(np.int32)
+    sim.step_arrays(raw)                        # the rows and their low parts are current before the masked reset
+    h.upload(native.BUF_RESET_PENDING, pending)
+    h.upload(native.BUF_EPISODE, np.full(b, 2, dtype=np.uint32))
+    h.reset_positions(SEED, native.EPISODE_PER_ENV)
+    sim.step_arrays(raw)
+    got = [h.download(w) for w in (native.BUF_SINR_DB, native.BUF_SNR_DB, native.BUF_CAPACITY, native.BUF_REWARD)]
+    ref = _handle_sim(b)
+    ref.handle.reset_positions(SEED, 2)
+    fresh = np.stack([ref.handle.download(native.BUF_POS_X), ref.handle.download(native.BUF_POS_Y)], axis=-1).astype(np.float64)
+    expect = np.where(pending[:, None, None].astype(bool), fresh, pos)
+    ref.set_positions(expect)
+    ref.step_arrays(raw)
+    want = [ref.handle.download(w) for w in (native.BUF_SINR_DB, native.BUF_SNR_DB, native.BUF_CAPACITY, native.BUF_REWARD)]
+    for g, w in zip(got, want):
+        np.testing.assert_array_equal(g.view(np.uint32), w.view(np.uint32))
+    sim.handle.close(); ref.handle.close()
+
+
+def test_two_shards_equal_one_batch():
+    torch = _torch()
+    from gym_d2d_amd.envs import VecD2DEnv
+    b = 16
+    cfg = _cfg(num_rbs=8, num_cues=8, num_due_pairs=8)
+    whole = VecD2DEnv(dict(cfg), num_envs=b, autoreset=True)
+    halves = [VecD2DEnv(dict(cfg), num_envs=b // 2, first_env=k * b // 2, autoreset=True) for k in range(2)]
+    stagger = np.arange(b) * 3 % 10
+    outs = [_outputs(whole, whole.reset(seed=SEED, elapsed=stagger))]
+    parts = [[_outputs(e, e.reset(seed=SEED, elapsed=stagger[k * b // 2:(k + 1) * b // 2]))] for k, e in enumerate(halves)]
+    gen = torch.Generator(device=whole.device).manual_seed(6)
+    for t in range(24):
+        a = _actions(whole, gen)
+        obs, rew, done, info = whole.step(a)
+        outs.append(dict(_outputs(whole, obs), rew=rew.clone(), done=done.clone(), reset=info['reset'].clone()))
+        for k, e in enumerate(halves):
+            obs, rew, done, info = e.step(a[k * b // 2:(k + 1) * b // 2].contiguous())
+            parts[k].append(dict(_outputs(e, obs), rew=rew.clone(), done=done.clone(), reset=info['reset'].clone()))
+    for t, o in enumerate(outs):
+        joined = {k: torch.cat([parts[0][t][k], parts[1][t][k]]) for k in o}
+        _assert_outputs(o, joined, f'step {t}')
+    for e in [whole] + halves:
+        e.close()
+
+
+def test_refusals(native, tmp_path):
+    import json
+    from gym_d2d_amd.envs import VecD2DEnv
+    from gym_d2d_amd.path_loss import ArrayPathLoss
+
+    class OncePerReset(ArrayPathLoss):
+        def compute(self, view):
+            return 20.0 * view.xp.log10(view.distance())
+    with pytest.raises(ValueError, match='torch'):
+        VecD2DEnv(_cfg(), num_envs=4, use_torch=False, autoreset=True)
+    with pytest.raises(ValueError, match="'array'"):
+        VecD2DEnv(_cfg(path_loss_model=OncePerReset), num_envs=4, autoreset=True)
+    path = tmp_path / 'devices.json'
+    path.write_text(json.dumps({'cue01': {'position': [120.1, -40.3]}}))         # not float32 values
+    with pytest.raises(ValueError, match='float32'):
+        VecD2DEnv(_cfg(device_config_file=path), num_envs=4, autoreset=True)
+    sim = _handle_sim(4)
+    sim.handle.reset_positions(SEED, 0)
+    d = sim.handle.num_devices
+    with pytest.raises(native.NativeError) as err:
+        sim.handle.reset_positions(SEED, native.EPISODE_PER_ENV, np.zeros(d, np.uint8), np.zeros((d, 2), np.float32))
+    assert err.value.code == native.ERR_INVALID
+    sim.handle.close()
