@@ -26,11 +26,11 @@ EPISODE_PATH = LIB_DIR / 'libd2d_episode.so'
 INCLUDE = PKG.parent / 'include'
 ARCH = 'gfx950'
 
-SOURCES = ['d2d_step.hip', 'd2d_rollout.hip', 'd2d_obs.hip', 'd2d_reset.hip', 'd2d_gain.hip', 'd2d_capi.hip']
+SOURCES = ['d2d_step.hip', 'd2d_rollout.hip', 'd2d_obs.hip', 'd2d_reset.hip', 'd2d_gain.hip', 'd2d_plan.hip', 'd2d_capi.hip']
 PROBE_SOURCES = ['d2d_probe.hip']
 PLUGIN_SOURCES = ['d2d_plugin.hip']
 EPISODE_SOURCES = ['d2d_episode.hip']
-HEADERS = [CSRC / 'd2d_internal.h', CSRC / 'd2d_step_device.h', CSRC / 'd2d_store.h', INCLUDE / 'd2d_hip.h', INCLUDE / 'd2d_hip_diag.h',
+HEADERS = [CSRC / 'd2d_internal.h', CSRC / 'd2d_plan.h', CSRC / 'd2d_step_device.h', CSRC / 'd2d_store.h', INCLUDE / 'd2d_hip.h', INCLUDE / 'd2d_hip_diag.h',
            INCLUDE / 'd2d_plugin.h', INCLUDE / 'd2d_episode.h']
 FLAGS = ['-O3', '-std=c++17', '-fPIC', f'--offload-arch={ARCH}', '-fno-gpu-rdc', '-Wall', '-Wno-unused-function', '-Wno-unused-value',
          # the kernels already issue their uniform-address LDS atomics from one lane (or on rare paths): LLVM's atomic optimizer

@@ -3,6 +3,7 @@
 // if HIP is unusable every call fails with D2D_ERR_HIP.
 #include "../../include/d2d_hip_diag.h"
 #include "d2d_internal.h"
+#include "d2d_plan.h"
 
 #include <dlfcn.h>
 
@@ -111,12 +112,9 @@ struct d2d_handle {
     int pow_k = 0;                                   // PL_POWK: the integer every link transmitter's exponent lies within 1/2 of (refresh_tables)
     int obs_f64 = 0;                                 // D2D_BUF_OBS holds float64 (d2d_set_obs_dtype)
     int reward_layout = D2D_REWARD_PER_AGENT;        // SystemCapacity: [B,N] rows or one scalar per env (D2D_BUF_REWARD_ENV)
-    int tune_rows = 0, tune_nt = 1, tune_xcd = 1, tune_block = 0, tune_variant = 0, tune_step_threads = 0, tune_stagger = 0;
+    d2d::ObsTuning tune_obs;                         // D2D_TUNE_OBS_*
+    d2d::StepTuning tune_step;                       // D2D_TUNE_STEP_*
     int num_cus = 0;
-    int tune_step_prefetch = -1;                     // action prefetch distance in envs: -1 auto, 0 off
-    int tune_step_obs_rotate = -1;                   // fused expansion start-phase multiplier: -1 auto (29), 0 off
-    int tune_step_nt = -1, tune_step_srec = -1;      // nontemporal result stores / scalar record loads: -1 auto, 0 off, 1 on (if legal)
-    int tune_step_epw = 0, tune_step_block = 0, tune_step_fuse = -1, tune_step_ablate = 0, tune_step_walk = -1, tune_step_lpt = -1;
     // d2d_step_host: packed device block + pinned host mirrors
     void* host_out_dev = nullptr; size_t host_out_bytes = 0;
     void* host_out_pinned = nullptr;
@@ -391,74 +389,6 @@ struct OutPtrs {
     int* env_flags = nullptr;
 };
 
-// LinearObs expansion launch geometry for a [B, N, 6] table (shared by the step path and d2d_expand_table).
-void make_obs_args(const d2d_handle* h, int B, int N, const float* table, float* obs, int out_f64, d2d::ObsArgs* out) {
-    d2d::ObsArgs o;
-    std::memset(&o, 0, sizeof(o));
-    o.B = B; o.N = N;
-    o.out_f64 = out_f64;
-    if (out_f64 && h->tune_variant != 3) {
-        // float64 block (d2d_set_obs_dtype): flat slabs of double2 pieces - one aligned float2 of T each, 3N per row, any N
-        o.vec = 2;
-        o.q_per_row = (unsigned)(3 * N);
-        o.q_magic = ((1ull << 40) + o.q_per_row - 1) / o.q_per_row;
-        o.block = h->tune_block > 0 ? h->tune_block : 1024;
-        int passes = h->tune_rows > 0 ? h->tune_rows : 2;
-        if (passes > 4) passes = 4;
-        o.rows_per_wg = passes;
-        const unsigned total = (unsigned)N * o.q_per_row, slab = (unsigned)passes * (unsigned)o.block;
-        o.chunks = (int)((total + slab - 1) / slab);
-        o.xcd_remap = (h->tune_xcd > 0 && B % 8 == 0) ? 1 : 0;
-        o.nontemporal = h->tune_nt;
-        o.variant = 2;
-        o.table = table; o.obs = obs;
-        *out = o;
-        return;
-    }
-    o.vec = (6 * N) % 4 == 0 ? 4 : 2;
-    o.q_per_row = (unsigned)(6 * N / o.vec);
-    o.q_magic = ((1ull << 40) + o.q_per_row - 1) / o.q_per_row;
-    // Launch geometry.  Round 4 (tools/probes/obs_policy_geometry.py, MI355X, N = 512): FLAT slabs - the env's [N][6N] block as one
-    // flat array of float4, a 1024-thread workgroup writing two consecutive 16 KB pieces of it whatever the row length - the
-    // shape of the fastest fill of the probe family: 7.21 TB/s against 7.01 for the row-aligned shape of rounds 1-3 (768 threads
-    // = one row's float4 count, two 12 KB rows per workgroup) in interleaved rounds on one box; 3 or 4 pieces, 768- or 512-thread
-    // slabs and every scope-bit store policy are slower.  Rounds 1-3 (tools/tune_obs.py): among row-aligned shapes the fastest
-    // is the one where every thread issues exactly TWO 16-B stores (6.96 TB/s vs 5.9 for 96-KiB slabs and 5.6 for 786-KiB slabs):
-    // small slabs dispatched in order keep the chip-wide write front nearly sequential in address, and a workgroup never
-    // outlives its neighbours.  D2D_TUNE_OBS_VARIANT = 3 keeps the row-aligned kernel (A/B, and 8-byte rows when 6N % 4 != 0).
-    const bool flat = o.vec == 4 && (h->tune_variant == 0 || h->tune_variant == 2) && !out_f64;
-    int block = h->tune_block;
-    if (block <= 0) {
-        block = flat ? 1024 : (int)((o.q_per_row + 63) / 64) * 64;
-        if (block < 256) block = 256;
-        if (block > 1024) block = 1024;
-    }
-    int rows = h->tune_rows;
-    if (rows <= 0) {
-        rows = flat ? 2 : (int)((2u * (unsigned)block + o.q_per_row / 2) / o.q_per_row);
-        if (rows < 1) rows = 1;
-    }
-    if (rows > N && !flat) rows = N;
-    o.rows_per_wg = rows;
-    o.chunks = (N + rows - 1) / rows;
-    if (flat) {                                          // `rows` = consecutive pieces of `block` float4 per workgroup (at most 4)
-        if (rows > 4) rows = 4;
-        o.rows_per_wg = rows;
-        const unsigned total = (unsigned)N * o.q_per_row, slab = (unsigned)rows * (unsigned)block;
-        o.chunks = (int)((total + slab - 1) / slab);
-    }
-    o.xcd_remap = (h->tune_xcd > 0 && B % (8 * h->tune_xcd) == 0) ? h->tune_xcd : 0;   // envs interleaved per XCD
-    o.nontemporal = h->tune_nt;
-    o.block = block;
-    // tune_variant 2 names the flat kernel, whose grid is sized in flat chunks: when the flat shape does not apply (8-byte rows, a
-    // float64 block's float32 consumers) the row-aligned default runs on the row-aligned geometry computed above
-    o.variant = flat ? 2 : (h->tune_variant == 2 ? 0 : h->tune_variant);
-    o.stagger = h->tune_stagger;
-    o.table = table;
-    o.obs = obs;
-    *out = o;
-}
-
 int run_step(d2d_handle* h, int action_mode, const int32_t* a0, const int32_t* a1, const OutPtrs* redirect) {
     if (!h->have_links) return fail(D2D_ERR_STATE, "d2d_set_links has not been called");
     if (!h->have_pos) return fail(D2D_ERR_STATE, "positions not set (d2d_set_positions / upload POS_X,POS_Y)");
@@ -466,6 +396,15 @@ int run_step(d2d_handle* h, int action_mode, const int32_t* a0, const int32_t* a
     if (rc) return rc;
     const int N = h->N, D = h->D;
     if (N == 0) return fail(D2D_ERR_INVALID, "no links: the reference divides by len(actions) (reward_fn.py:42)");
+    // float64 positions uploaded as (hi, lo) pairs (d2d_set_positions_f64) with a non-zero low part somewhere
+    const int xpos = h->have_lo ? 1 : 0;
+
+    const d2d::StepInputs in{h->B, N, h->cfg.num_rbs, h->num_cus, action_mode, h->n_fixed, h->col_mode, h->reward_fn, h->mode,
+                             h->obs_mode, h->obs_f64, h->bucketing, h->rec_uniform, h->rec_uniform128, xpos, h->tune_step};
+    d2d::StepPlan plan;
+    const char* why = nullptr;
+    rc = d2d::plan_step(in, &plan, &why);
+    if (rc) return fail(rc, why);
 
     d2d::StepArgs s;
     std::memset(&s, 0, sizeof(s));
@@ -474,141 +413,20 @@ int run_step(d2d_handle* h, int action_mode, const int32_t* a0, const int32_t* a
     s.act_stride = action_mode == 0 ? N - h->n_fixed : N;
     s.col_mode = h->col_mode; s.n_fixed = h->n_fixed;
     s.inv_n = 1.0f / (float)N;
-    if ((size_t)h->B * (size_t)N * 24 >= (1ull << 32))
-        return fail(D2D_ERR_UNSUPPORTED, "envs x links per GPU must stay below 2^32 / 24 (32-bit byte offsets in the step kernel)");
     s.reward_fn = h->reward_fn; s.reward_param = h->reward_param;
     s.write_table = h->obs_mode != D2D_OBS_NONE;
-    // nontemporal result stores: never with LinearObs (the expansion kernel reads the table right behind this launch).  In the
-    // generic kernels no consistent gain (profiles/r3_ab_*): off unless asked for.  The rollout kernel takes them by itself
-    // (below): interleaved in one process at 4096 x 512, obs-less 17.98 -> 17.51 us, compact table 25.11 -> 24.76
-    // (profiles/r5_rollout_nt_and_links_per_thread.jsonl)
-    s.nt_results = h->tune_step_nt > 0 && h->obs_mode != D2D_OBS_LINEAR;
-    s.rec_uniform = h->rec_uniform && h->tune_step_srec != 0;
     s.pow_k = h->pow_k;
-    s.ablate = h->tune_step_ablate;
-    s.dbg = nullptr;
+    s.ablate = h->tune_step.ablate;
+    s.lpt = plan.lpt; s.tpe = plan.tpe; s.tpe_magic = plan.tpe_magic; s.epw = plan.epw; s.mask_words = plan.mask_words;
+    s.walk = plan.walk; s.fuse_obs = plan.fuse_obs; s.obs_rotate = plan.obs_rotate; s.obs_q_per_row = plan.obs_q_per_row;
+    s.obs_q_magic = plan.obs_q_magic; s.lds = plan.lds; s.rollout = plan.rollout; s.rec_uniform = plan.rec_uniform;
+    s.nt_results = plan.nt_results; s.prefetch_envs = plan.prefetch_envs;
 #if defined(D2D_STEP_ABLATE) && D2D_STEP_ABLATE
-    if (h->tune_step_ablate & 8192) {          // phase stamps: [B workgroups][16 waves][16] u64 (tools/phase_times.py)
+    if (h->tune_step.ablate & 8192) {          // phase stamps: [B workgroups][16 waves][16] u64 (tools/phase_times.py)
         if (!h->dbg) HIP_TRY(hipMalloc(&h->dbg, (size_t)h->B * 16 * 16 * 8));
         s.dbg = h->dbg;
     }
 #endif
-    // masks cover N <= 1024; beyond that the member lists (eight slots per RB) - but only where they can hold the env: with more
-    // than four links per RB on average a ninth link on some RB is the rule, the list build is wasted and the workgroup
-    // sweeps all pairs anyway (N > 8 R: by pigeonhole), so those shapes go straight to the sweep
-    const bool lists_can_help = (long long)N <= 4ll * h->cfg.num_rbs;
-    // float64 positions uploaded as (hi, lo) pairs (d2d_set_positions_f64) with a non-zero low part somewhere: the OPT_XPOS kernels
-    const int xpos = h->have_lo ? 1 : 0;
-    // The rollout kernel (d2d_rollout.hip) serves: raw agent actions for every link or for all but a prefix with fixed actions, any of
-    // the three rewards, one env per workgroup (64 ... 1024 links: a multiple of 64, or padded to the next one; no
-    // fused expansion), a power-law path loss.  Round 5: it is the faster one in every obs mode (same box, 4096 x 512, r4 HEAD ->
-    // rollout: obs-less 21.3 -> 19.3 us, compact table 27.7 -> 25.8, with the decoded planes 28.3 -> 27.3,
-    // profiles/r5_ab_rollout_kernel.jsonl; further since), so wherever it applies the lists are the default.
-    const bool will_fuse = h->obs_mode == D2D_OBS_LINEAR && !h->obs_f64 && (h->tune_step_fuse >= 0 ? h->tune_step_fuse != 0 : N <= 128);
-    const bool rollout_cfg = action_mode == 0 && (h->n_fixed == 0 || (h->n_fixed < N && h->col_mode == 0)) && h->bucketing &&   // fixed links: a prefix
-                             (h->reward_fn == D2D_REWARD_SYSTEM_CAPACITY || h->reward_fn == D2D_REWARD_SHANNON ||
-                              h->reward_fn == D2D_REWARD_CUE_SINR_SHANNON) &&
-                             !will_fuse && (h->mode == d2d::PL_INV_SQUARE || h->mode == d2d::PL_POWER || h->mode == d2d::PL_POWK) && (h->tune_step_ablate & ~8192) == 0 &&
-                             h->tune_step_prefetch != 0 && h->tune_step_threads == 0 && h->tune_step_epw <= 1 && h->tune_step_block == 0 &&
-                             (N % 64 == 0 || N > 64) && N <= 1024;       // (no multiple of 64: padded; measured from 80 links up)
-    const bool lists_pay = lists_can_help && (N > 1024 || h->obs_mode == D2D_OBS_NONE || rollout_cfg);
-    s.walk = h->tune_step_walk >= 0 ? h->tune_step_walk : (lists_pay ? 2 : 0);
-
-    // ---- launch geometry.  tpe threads per env (one per link up to 1024), epw envs per workgroup: small envs share a
-    // workgroup (N = 50: four 64-thread envs in 256 threads), and for small N the LinearObs expansion runs inside the
-    // same launch, streamed by all threads of the workgroup - two launches of a few microseconds each are bound by
-    // launch latency, not by HBM.
-    // lpt = links per thread held in registers (1 or 2; 0 = strided beyond 2 x 1024 links); tpe = threads per env
-    int lpt = h->tune_step_lpt > 0 ? h->tune_step_lpt : 1;
-    int tpe;
-    if (h->tune_step_threads > 0) {
-        tpe = h->tune_step_threads;
-        lpt = N <= tpe ? 1 : (N <= 2 * tpe ? 2 : 0);
-    } else {
-        tpe = (((N + lpt - 1) / lpt + 63) / 64) * 64;
-        if (tpe > 1024) { lpt = 2; tpe = (((N + 1) / 2 + 63) / 64) * 64; }
-        if (tpe > 1024) { lpt = 0; tpe = 1024; }
-    }
-    if (tpe > 1024) tpe = 1024;
-    if (tpe < 64) tpe = 64;
-    int fuse = 0;
-    if (h->obs_mode == D2D_OBS_LINEAR) {
-        const bool want = h->tune_step_fuse >= 0 ? h->tune_step_fuse != 0 : N <= 128;
-        if (want && !h->obs_f64) fuse = (6 * N) % 4 == 0 ? 4 : 2;       // the fused expansion writes float32 only
-    }
-    // per-RB membership masks: u32 words, every link of the env in some thread's registers, N <= 1024 (the 32-bit summary
-    // word names up to 32 mask words)
-    // per-RB member lists (walk 2): any N whose links sit in registers; an env that overflows a list falls back to the masks
-    // when they exist, else to the all-pairs sweep
-    int lists = h->bucketing && s.walk == 2 && lpt > 0 && s.reward_fn != D2D_REWARD_CUE_SINR_SHANNON;
-    // (the rollout kernel has its own way with CueSinrShannon; the generic kernels' lists have none)
-    const bool rollout_wanted = h->bucketing && s.walk == 2 && rollout_cfg && h->col_mode == 0;
-    if (s.walk == 2 && !lists && !rollout_wanted) s.walk = 0;
-    int W = 0;
-    if (h->bucketing && lpt > 0 && N <= 1024) {
-        W = (N + 31) / 32;
-        if (d2d::step_lds_bytes_per_env(N, s.R, W, fuse, lpt, s.reward_fn, (int)h->mode, lists, xpos) > 96 * 1024) W = 0;
-    }
-    // masks that do not fit (thousands of RBs): the lists are 20 bytes per RB instead of 4 per RB and 32 links - take them when
-    // nobody chose a search variant
-    if (W == 0 && !lists && lists_can_help && h->tune_step_walk < 0 && h->bucketing && lpt > 0 && s.reward_fn != D2D_REWARD_CUE_SINR_SHANNON) { lists = 1; s.walk = 2; }
-    if (lists && d2d::step_lds_bytes_per_env(N, s.R, W, fuse, lpt, s.reward_fn, (int)h->mode, lists, xpos) > 96 * 1024) { lists = 0; s.walk = 0; }
-    s.lpt = lpt;
-    d2d::step_lds_layout(N, s.R, W, fuse, lpt, s.reward_fn, (int)h->mode, lists, xpos, &s.lds);
-    // The rollout kernel (d2d_rollout.hip): raw agent actions for every link, SystemCapacity, one env per workgroup, a power-law
-    // path loss, member lists wanted.  Its own LDS layout: no masks, 17 KB per env at 512 links on 256 RBs.
-    if (rollout_wanted) {
-        // One link per thread, or two ADJACENT ones (links 2t and 2t + 1, N / 2 threads per env): every per-wave instruction - the
-        // scalar record load, barriers, ballots, the wave reduction, the ticket - is paid once per 128 links, half as many waves are
-        // launched, and a thread's two results are one 8-byte element of every plane and 48 contiguous bytes of the table.  Two
-        // wherever the device classes fill aligned groups of 128 links (one scalar record load serves the wave; per-lane records
-        // for two links push the kernel past 64 VGPRs).  Same box, 4096 x 512: obs-less 20.2 -> 19.0 us, compact table 26.7 -> 24.5
-        // (profiles/r5_table_rows_through_lds.jsonl).
-        // (Other exponents - the power-law kernel, twice the arithmetic per pair - gain nothing from two: COST-Hata obs-less 32.0 us
-        // with one link per thread, 33.4 with two; table 37.3 / 37.8.)
-        int rl = h->tune_step_lpt > 0 ? h->tune_step_lpt : (h->rec_uniform128 && s.rec_uniform && h->mode == d2d::PL_INV_SQUARE ? 2 : 1);
-        if (rl != 2 || N % 128 != 0) rl = 1;
-        if (rl == 2 && !h->rec_uniform128) s.rec_uniform = false;     // forced by the tuning key on other records: per-lane records
-        if (h->n_fixed > 0) { s.rec_uniform = false; rl = 1; }         // fixed actions live in per-link records: one link per thread
-        if (s.reward_fn == D2D_REWARD_CUE_SINR_SHANNON) rl = 1;        // its second look at the RB's members: one link per thread
-        if (xpos) rl = 1;                                              // exact positions: one link per thread (a fourth 16-byte row per link)
-        {
-            d2d::StepLds rlds;
-            d2d::rollout_lds_layout(N, s.R, (int)h->mode, s.reward_fn, xpos, &rlds);
-            if (rlds.env_bytes <= 64 * 1024) {
-                s.rollout = 1; s.lds = rlds;
-                lpt = rl; tpe = ((N / rl + 63) / 64) * 64; W = 0; s.lpt = lpt;
-                if (h->tune_step_nt < 0 && h->obs_mode != D2D_OBS_LINEAR) s.nt_results = 1;      // auto: on, see above
-            }
-        }
-    }
-    const size_t env_lds = s.lds.env_bytes;
-    if (env_lds > 160 * 1024) return fail(D2D_ERR_UNSUPPORTED, "links per env exceed the LDS staging capacity");
-    int epw = s.rollout ? 1 : h->tune_step_epw;
-    if (epw <= 0) epw = tpe >= 256 ? 1 : 256 / tpe;
-    if (epw > h->B) epw = h->B;
-    while (epw > 1 && ((size_t)epw * env_lds > 64 * 1024 || epw * tpe > 1024)) --epw;
-    int block = h->tune_step_block > 0 ? h->tune_step_block : epw * tpe;
-    if (fuse && h->tune_step_block <= 0 && block < 256) block = 256;      // more store streams per env for the obs phase
-    if (block < epw * tpe) block = epw * tpe;
-    if (block > 1024) return fail(D2D_ERR_INVALID, "step workgroup exceeds 1024 threads");
-    s.tpe = tpe; s.epw = epw; s.mask_words = W; s.fuse_obs = fuse;
-    {
-        // action prefetch distance = the envs resident on the chip at once (LDS: 160 KB / CU, threads: 2048 / CU), as a
-        // multiple of 8 workgroups so that the prefetching and the consuming workgroup share an XCD (and its L2)
-        int per_cu = (int)((160 * 1024) / ((size_t)epw * env_lds ? (size_t)epw * env_lds : 1));
-        if (per_cu > 2048 / block) per_cu = 2048 / block;
-        if (per_cu < 1) per_cu = 1;
-        int dist = h->tune_step_prefetch >= 0 ? h->tune_step_prefetch : per_cu * h->num_cus * epw;
-        dist -= dist % (8 * epw);
-        s.prefetch_envs = dist;
-    }
-    s.tpe_magic = ((1u << 20) + (unsigned)tpe - 1) / (unsigned)tpe;
-    if (fuse) {
-        s.obs_rotate = h->tune_step_obs_rotate >= 0 ? h->tune_step_obs_rotate : 29;
-        s.obs_q_per_row = (unsigned)(6 * N / fuse);
-        s.obs_q_magic = ((1ull << 40) + s.obs_q_per_row - 1) / s.obs_q_per_row;
-    }
 
     void* p = nullptr;
 #define GET(which, field, type)                                  \
@@ -687,12 +505,12 @@ int run_step(d2d_handle* h, int action_mode, const int32_t* a0, const int32_t* a
     EventPair* ep = nullptr;
     rc = record_start(h, 0, &ep);
     if (rc) return rc;
-    HIP_TRY(d2d::launch_step(s, h->mode, block, h->stream));
+    HIP_TRY(d2d::launch_step(s, plan, h->stream));
     if (ep) HIP_TRY(hipEventRecord(ep->stop, h->stream));
 
-    if (h->obs_mode == D2D_OBS_LINEAR && !fuse) {
-        d2d::ObsArgs o;
-        make_obs_args(h, h->B, N, s.table, s.obs, redirect ? 0 : h->obs_f64, &o);      // d2d_step_host's packed block is float32
+    if (plan.obs_expand) {
+        d2d::ObsArgs o = d2d::plan_obs(h->tune_obs, h->B, N, redirect ? 0 : h->obs_f64);      // d2d_step_host's packed block is float32
+        o.table = s.table; o.obs = s.obs;
         rc = record_start(h, 1, &ep);
         if (rc) return rc;
         HIP_TRY(d2d::launch_obs_expand(o, h->stream));
@@ -1162,48 +980,48 @@ int d2d_set_tuning(d2d_handle* h, int32_t key, int32_t value) try {
         return fail(D2D_ERR_UNSUPPORTED, "this tuning key / value needs the diagnostic build (D2D_BUILD_DIAG=1 python -m gym_d2d_amd.build; include/d2d_hip_diag.h)");
 #endif
     switch (key) {
-        case D2D_TUNE_OBS_ROWS_PER_WG: h->tune_rows = value; break;
+        case D2D_TUNE_OBS_ROWS_PER_WG: h->tune_obs.rows = value; break;
         case D2D_TUNE_OBS_NONTEMPORAL:
             if (value < 0 || value > 5) return fail(D2D_ERR_INVALID, "obs store policy must be in [0, 5]");
-            h->tune_nt = value;
+            h->tune_obs.nt = value;
             break;
-        case D2D_TUNE_OBS_XCD_REMAP: h->tune_xcd = value < 0 ? 0 : value; break;
-        case D2D_TUNE_OBS_VARIANT: h->tune_variant = value; break;
+        case D2D_TUNE_OBS_XCD_REMAP: h->tune_obs.xcd = value < 0 ? 0 : value; break;
+        case D2D_TUNE_OBS_VARIANT: h->tune_obs.variant = value; break;
         case D2D_TUNE_OBS_STAGGER:
             if (value < 0 || value > 64) return fail(D2D_ERR_INVALID, "stagger must be in [0, 64]");
-            h->tune_stagger = value;
+            h->tune_obs.stagger = value;
             break;
         case D2D_TUNE_STEP_THREADS:
             if (value != 0 && (value < 64 || value > 1024 || value % 64)) return fail(D2D_ERR_INVALID, "threads must be a multiple of 64 in [64,1024]");
-            h->tune_step_threads = value;
+            h->tune_step.threads = value;
             break;
         case D2D_TUNE_OBS_BLOCK:
             if (value != 0 && (value < 64 || value > 1024 || value % 64)) return fail(D2D_ERR_INVALID, "block must be a multiple of 64 in [64,1024]");
-            h->tune_block = value;
+            h->tune_obs.block = value;
             break;
         case D2D_TUNE_STEP_ENVS_PER_WG:
             if (value < 0 || value > 16) return fail(D2D_ERR_INVALID, "envs per workgroup must be in [0,16]");
-            h->tune_step_epw = value;
+            h->tune_step.epw = value;
             break;
         case D2D_TUNE_STEP_BLOCK:
             if (value != 0 && (value < 64 || value > 1024 || value % 64)) return fail(D2D_ERR_INVALID, "block must be a multiple of 64 in [64,1024]");
-            h->tune_step_block = value;
+            h->tune_step.block = value;
             break;
         case D2D_TUNE_STEP_PREFETCH:
             if (value < -1) return fail(D2D_ERR_INVALID, "prefetch distance must be >= -1");
-            h->tune_step_prefetch = value;
+            h->tune_step.prefetch = value;
             break;
         case D2D_TUNE_STEP_LPT:
             if (value != -1 && value != 1 && value != 2) return fail(D2D_ERR_INVALID, "links per thread must be -1 (auto), 1 or 2");
-            h->tune_step_lpt = value;
+            h->tune_step.lpt = value;
             break;
         case D2D_TUNE_STEP_WALK:
             if (value < -1 || value > 2) return fail(D2D_ERR_INVALID, "walk must be -1, 0, 1 or 2");
-            h->tune_step_walk = value;
+            h->tune_step.walk = value;
             break;
         case D2D_TUNE_STEP_ABLATE:
 #if defined(D2D_STEP_ABLATE) && D2D_STEP_ABLATE
-            h->tune_step_ablate = value;
+            h->tune_step.ablate = value;
             break;
 #else
             if (value != 0) return fail(D2D_ERR_UNSUPPORTED, "D2D_TUNE_STEP_ABLATE needs the diagnostic build (D2D_BUILD_DIAG=1 python -m gym_d2d_amd.build)");
@@ -1211,19 +1029,19 @@ int d2d_set_tuning(d2d_handle* h, int32_t key, int32_t value) try {
 #endif
         case D2D_TUNE_STEP_OBS_ROTATE:
             if (value < -1 || value > 65535) return fail(D2D_ERR_INVALID, "obs_rotate must be in [-1, 65535]");
-            h->tune_step_obs_rotate = value;
+            h->tune_step.obs_rotate = value;
             break;
         case D2D_TUNE_STEP_NT_RESULTS:
             if (value < -1 || value > 1) return fail(D2D_ERR_INVALID, "nt_results must be -1, 0 or 1");
-            h->tune_step_nt = value;
+            h->tune_step.nt = value;
             break;
         case D2D_TUNE_STEP_SCALAR_RECORDS:
             if (value < -1 || value > 1) return fail(D2D_ERR_INVALID, "scalar_records must be -1, 0 or 1");
-            h->tune_step_srec = value;
+            h->tune_step.srec = value;
             break;
         case D2D_TUNE_STEP_FUSE_OBS:
             if (value < -1 || value > 1) return fail(D2D_ERR_INVALID, "fuse_obs must be -1, 0 or 1");
-            h->tune_step_fuse = value;
+            h->tune_step.fuse = value;
             break;
         default: return fail(D2D_ERR_INVALID, "unknown tuning key");
     }
@@ -1456,8 +1274,8 @@ int d2d_expand_table(d2d_handle* h, const float* table_dev, int32_t n_envs, int3
     if (!h || !table_dev || !obs_dev) return fail(D2D_ERR_INVALID, "null argument");
     if (n_envs < 1 || n_links < 1 || n_links > D2D_MAX_LINKS) return fail(D2D_ERR_INVALID, "n_envs >= 1 and 1 <= n_links <= D2D_MAX_LINKS");
     USE_DEVICE(h);
-    d2d::ObsArgs o;
-    make_obs_args(h, n_envs, n_links, table_dev, obs_dev, 0, &o);
+    d2d::ObsArgs o = d2d::plan_obs(h->tune_obs, n_envs, n_links, 0);
+    o.table = table_dev; o.obs = obs_dev;
     EventPair* ep = nullptr;
     int rc = record_start(h, 1, &ep);
     if (rc) return rc;

@@ -36,7 +36,16 @@ __host__ __device__ constexpr bool pl_is_table(int mode) { return mode == PL_TAB
 #define D2D_REC_TYPE_MASK 0xF
 #define D2D_REC_FIXED_BIT (1 << 28)
 
-// Byte offsets of one env's LDS arrays (step_lds_layout): only what the configuration reads back is allocated.
+// kernel options (template parameter OPT of step_kernel / rollout_kernel)
+#define OPT_LISTS 1      /* generic kernels: per-RB member lists instead of the masks (StepArgs::walk == 2) */
+#define OPT_SREC 2       /* rollout kernel: link records by scalar loads (StepArgs::rec_uniform) */
+#define OPT_NT 4         /* rollout kernel: nontemporal result stores (StepArgs::nt_results) */
+#define OPT_PAD 8        /* rollout kernel: N is no multiple of 64 (threads beyond the last link shadow it) */
+#define OPT_XPOS 16      /* exact positions: every coordinate is a (hi, lo) float pair (StepArgs::lpos_lo, d2d_set_positions_f64) */
+
+// Byte offsets of one env's LDS arrays (d2d_plan.hip): only what the configuration reads back is allocated.  Every layout
+// starts with an 80-byte head: wave partial sums and flags (d2d_step_device.h, d2d_rollout.hip).
+#define LDS_HEAD_BYTES 80u
 struct StepLds {
     unsigned aux, rx, sinr, sh, expo, tflat, mask, lists, pool, env_bytes;
     unsigned lo;             // exact positions (StepArgs::lpos_lo): float2 per link (+ stand-in), the low parts of (tx_x, tx_y)
@@ -47,7 +56,7 @@ struct StepArgs {
     int B, N, R, D;
     int mask_words;          // ceil(N/32): u32 words per RB membership mask (0 -> all-pairs path)
     int lpt;                 // links per thread held in registers: 1, 2, or 0 = strided
-    int rollout;             // the rollout kernel (d2d_rollout.hip) serves this launch; lds = rollout_lds_layout
+    int rollout;             // the rollout kernel (d2d_rollout.hip) serves this launch; lds is its layout
     StepLds lds;             // LDS layout of one env
     int action_mode;         // 0: raw int actions (a // P, a % P)   1: explicit rb / pwr
     int act_stride;          // columns of the action array(s): N - n_fixed in mode 0, N in mode 1
@@ -133,12 +142,11 @@ struct ObsArgs {
     float* obs;              // [B,N,6N]
 };
 
-hipError_t launch_step(const StepArgs& a, PlMode mode, int block_threads, hipStream_t stream);
-hipError_t launch_rollout(const StepArgs& a, PlMode mode, int opt, int block_threads, hipStream_t stream);
-void rollout_lds_layout(int N, int R, int mode, int reward_fn, int xpos, StepLds* out);
+struct StepPlan;             // d2d_plan.h
+// the step as plan_step chose it: the kernel it names, in its grid, block and dynamic LDS
+hipError_t launch_step(const StepArgs& a, const StepPlan& p, hipStream_t stream);
+hipError_t launch_rollout(const StepArgs& a, const StepPlan& p, hipStream_t stream);
 hipError_t launch_obs_expand(const ObsArgs& a, hipStream_t stream);
-size_t step_lds_bytes_per_env(int N, int R, int mask_words, int fuse_obs, int lpt, int reward_fn, int mode, int lists, int xpos);
-void step_lds_layout(int N, int R, int mask_words, int fuse_obs, int lpt, int reward_fn, int mode, int lists, int xpos, StepLds* out);
 hipError_t launch_flags_or(const int* env_flags, int B, unsigned* status, hipStream_t stream);
 hipError_t launch_link_positions(const float* pos_x, const float* pos_y, const float* lo_x, const float* lo_y, const int4* rec_a,
                                  int B, int N, int D, float4* lpos, float4* lpos_lo, hipStream_t stream);

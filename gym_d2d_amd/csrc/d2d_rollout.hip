@@ -44,8 +44,7 @@
 // few hundred lanes per launch at BASELINE config 3, each outliving the launch - 47 us median against a 16 us minimum.)  A
 // workload that lives there (N > 4 R on average) is not given this kernel (run_step), and D2D_TUNE_STEP_WALK = 0 keeps the mask
 // walk for any other.
-#include <cstring>
-
+#include "d2d_plan.h"
 #include "d2d_step_device.h"
 
 namespace d2d {
@@ -65,26 +64,6 @@ namespace d2d {
 #define RO_STAMP(k) do { } while (0)
 #endif
 #define RO_ST(ptr, val) do { if (NT) __builtin_nontemporal_store((val), (ptr)); else *(ptr) = (val); } while (0)
-
-// LDS of one env (byte offsets; StepLds): 0 ... 59 unused, 60 dump (u16) | 64 flags[4]: env flags, reward bits, ticket, pool count
-// | 80 link[N + 1] tuples | expo[N + 1] (power law) | lo[N + 1] (exact positions) | slots[R + 1] (8 x u16) | cnt[R + 1] | pool[N] (rb, link) | 16 wave sums
-// (the reward's group sums) | low[N + 1] (CueSinrShannon).  With two links per thread the region from 80 on becomes the env's table image.
-void rollout_lds_layout(int N, int R, int mode, int reward_fn, int xpos, StepLds* out) {
-    std::memset(out, 0, sizeof(*out));
-    unsigned off = LDS_HEAD_BYTES + ((unsigned)N + 1u) * 16u;
-    out->expo = off;
-    if (mode == PL_POWER) off += ((unsigned)N + 1u) * 8u;
-    else if (mode == PL_POWK) off += (((unsigned)N + 1u) * 4u + 7u) & ~7u;       // PL_POWK: the links' RBs (the tuple's fourth word holds phi)
-    out->lo = off; if (xpos) off += ((unsigned)N + 1u) * 8u;      // exact positions: low parts of (tx_x, tx_y), + one for the stand-in
-    off = (off + 15u) & ~15u;
-    out->lists = off; off += ((unsigned)R + 1u) * 16u + (((unsigned)R + 1u + 3u) & ~3u) * 4u;
-    out->pool = off; off += (unsigned)N * 8u;
-    off = (off + 15u) & ~15u;
-    out->aux = off; off += 64u;                                   // padded link counts: the waves' capacity sums (16 floats)
-    out->rx = off;                                                // CueSinrShannon: per link "a non-D2D link below the threshold" (+ one for the stand-in)
-    if (reward_fn == 3) off += ((unsigned)N + 1u) * 4u;
-    out->env_bytes = (off + 15u) & ~15u;
-}
 
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
@@ -736,13 +715,15 @@ __global__ __launch_bounds__(1024) void rollout_kernel(const StepArgs a) {
     RO_STAMP(8);
 }
 
-hipError_t launch_rollout(const StepArgs& a, PlMode mode, int opt, int block_threads, hipStream_t stream) {
-    dim3 grid((unsigned)a.B), block(block_threads);
-    const size_t lds = a.lds.env_bytes;
-    hipError_t err = hipSuccess;
+hipError_t launch_rollout(const StepArgs& a, const StepPlan& p, hipStream_t stream) {
+    const StepKernel& k = p.kernel;
+    const dim3 grid(p.grid), block(p.block);
+    const size_t lds = p.lds_bytes;
+    hipError_t err = hipErrorInvalidDeviceFunction;           // a kernel identity that names no instantiation
 #define D2D_RO_1(M, O, L)                                                                                \
     do {                                                                                                 \
         static int checked = 0;                                                                          \
+        err = hipSuccess;                                                                                \
         if (!checked) {                                 /* raw LDS addressing: the dynamic block must start at LDS address 0 */ \
             hipFuncAttributes fa;                                                                        \
             err = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&rollout_kernel<M, O, L>));    \
@@ -758,29 +739,26 @@ hipError_t launch_rollout(const StepArgs& a, PlMode mode, int opt, int block_thr
         }                                                                                                \
     } while (0)
 #define D2D_RO_L(M, L)                                                                                   \
-    switch (opt & (OPT_SREC | OPT_NT)) {                                                                 \
+    switch (k.opt) {                                                                                     \
         case 0: D2D_RO_1(M, 0, L); break;                                                                \
         case OPT_SREC: D2D_RO_1(M, OPT_SREC, L); break;                                                  \
         case OPT_NT: D2D_RO_1(M, OPT_NT, L); break;                                                      \
-        default: D2D_RO_1(M, OPT_SREC | OPT_NT, L); break;                                               \
+        case OPT_SREC | OPT_NT: D2D_RO_1(M, OPT_SREC | OPT_NT, L); break;                                \
     }
-#define D2D_RO_X(M)                                     /* exact positions: one link per thread */         \
-    switch (opt & (OPT_SREC | OPT_NT | OPT_PAD)) {                                                       \
-        case 0: D2D_RO_1(M, OPT_XPOS, 1); break;                                                         \
-        case OPT_SREC: D2D_RO_1(M, OPT_XPOS | OPT_SREC, 1); break;                                       \
-        case OPT_NT: D2D_RO_1(M, OPT_XPOS | OPT_NT, 1); break;                                           \
-        case OPT_SREC | OPT_NT: D2D_RO_1(M, OPT_XPOS | OPT_SREC | OPT_NT, 1); break;                     \
-        case OPT_PAD: D2D_RO_1(M, OPT_XPOS | OPT_PAD, 1); break;                                         \
-        default: D2D_RO_1(M, OPT_XPOS | OPT_PAD | OPT_NT, 1); break;                                     \
+#define D2D_RO(M)                                       /* exact positions, padded link counts: one link per thread */ \
+    switch (k.opt) {                                                                                     \
+        case OPT_XPOS: D2D_RO_1(M, OPT_XPOS, 1); break;                                                  \
+        case OPT_XPOS | OPT_SREC: D2D_RO_1(M, OPT_XPOS | OPT_SREC, 1); break;                             \
+        case OPT_XPOS | OPT_NT: D2D_RO_1(M, OPT_XPOS | OPT_NT, 1); break;                                 \
+        case OPT_XPOS | OPT_SREC | OPT_NT: D2D_RO_1(M, OPT_XPOS | OPT_SREC | OPT_NT, 1); break;           \
+        case OPT_XPOS | OPT_PAD: D2D_RO_1(M, OPT_XPOS | OPT_PAD, 1); break;                               \
+        case OPT_XPOS | OPT_PAD | OPT_NT: D2D_RO_1(M, OPT_XPOS | OPT_PAD | OPT_NT, 1); break;             \
+        case OPT_PAD | OPT_NT: D2D_RO_1(M, OPT_PAD | OPT_NT, 1); break;                                   \
+        case OPT_PAD: D2D_RO_1(M, OPT_PAD, 1); break;                                                    \
+        default: if (k.lpt == 2) { D2D_RO_L(M, 2) } else if (k.lpt == 1) { D2D_RO_L(M, 1) }              \
     }
-#define D2D_RO(M) do {                                                                                   \
-        if (opt & OPT_XPOS) { D2D_RO_X(M) }                                                              \
-        else if (opt & OPT_PAD) { if (opt & OPT_NT) D2D_RO_1(M, OPT_PAD | OPT_NT, 1); else D2D_RO_1(M, OPT_PAD, 1); }  \
-        else if (a.lpt == 2) { D2D_RO_L(M, 2) } else { D2D_RO_L(M, 1) }                                  \
-    } while (0)
-    if (mode == PL_INV_SQUARE) D2D_RO(PL_INV_SQUARE); else if (mode == PL_POWK) D2D_RO(PL_POWK); else D2D_RO(PL_POWER);
+    if (k.mode == PL_INV_SQUARE) { D2D_RO(PL_INV_SQUARE) } else if (k.mode == PL_POWK) { D2D_RO(PL_POWK) } else if (k.mode == PL_POWER) { D2D_RO(PL_POWER) }
 #undef D2D_RO
-#undef D2D_RO_X
 #undef D2D_RO_L
 #undef D2D_RO_1
     return err;

@@ -46,38 +46,10 @@
 //     1024 x 50 on one box, profiles/r4_ab_builds_default_r2head_r3head_r4.jsonl);
 //   * what a learner does not read is not written: D2D_OBS_NONE (no table), D2D_REWARD_PER_ENV (SystemCapacity's scalar once per
 //     env), d2d_set_export_actions(0) (no decoded rb / pwr planes) take the rollout kernel from 64 + 8 to 36 bytes per link.
+#include "d2d_plan.h"
 #include "d2d_step_device.h"
 
 namespace d2d {
-
-void step_lds_layout(int N, int R, int mask_words, int fuse_obs, int lpt, int reward_fn, int mode, int lists, int xpos, StepLds* out) {
-    // lists: one more tuple (and exponent) behind the last link - the far-away, zero-power stand-in an empty list slot reads
-    const unsigned NL = (unsigned)N + (lists ? 1u : 0u);
-    unsigned off = LDS_HEAD_BYTES + NL * 16u;
-    out->aux = off; off += (unsigned)N * 4u;
-    out->rx = off; if (lpt == 0) off += (unsigned)N * 8u;
-    out->sinr = off; out->sh = off + (unsigned)N * 4u; if (reward_fn >= 2) off += (unsigned)N * 8u;
-    off = (off + 7u) & ~7u;
-    out->expo = off; if (mode == PL_POWER || mode == PL_SHADOW || mode == PL_POWK) off += NL * 8u;   // (head, tail) of -exponent / 2 per link (PL_POWK: (phi, 0))
-    off = (off + 7u) & ~7u;
-    out->lo = off; if (xpos) off += NL * 8u;                                         // low parts of (tx_x, tx_y) per link (exact positions)
-    out->tflat = off; if (fuse_obs) off += (unsigned)N * 24u;
-    off = (off + 15u) & ~15u;                            // the mask region is cleared with 16-byte stores
-    out->mask = off;
-    if (mask_words > 0) off += ((unsigned)R * mask_words + mask_words + (unsigned)R) * 4u;
-    off = (off + 15u) & ~15u;
-    // member lists: slots[R] (eight u16 link indices per RB, 0xFFFF = empty) then cnt[R] u32 (padded to 16 bytes) -
-    // one contiguous region, (re)initialised with one 16-byte store per lane
-    out->lists = off;
-    if (lists) off += (unsigned)R * 16u + (((unsigned)R + 3u) & ~3u) * 4u;
-    out->env_bytes = (off + 15u) & ~15u;
-}
-
-size_t step_lds_bytes_per_env(int N, int R, int mask_words, int fuse_obs, int lpt, int reward_fn, int mode, int lists, int xpos) {
-    StepLds l;
-    step_lds_layout(N, R, mask_words, fuse_obs, lpt, reward_fn, mode, lists, xpos, &l);
-    return l.env_bytes;
-}
 
 // LPT  = links per thread held in registers: 1 (thread = link, N <= tpe), 2 (links lt and lt + tpe: half the waves per
 //        env, two independent dependency chains per wave), 0 = strided (N > 2 * 1024: records re-read per link).
@@ -870,28 +842,15 @@ hipError_t launch_link_positions(const float* pos_x, const float* pos_y, const f
     return hipGetLastError();
 }
 
-hipError_t launch_step(const StepArgs& a, PlMode mode, int block_threads, hipStream_t stream) {
-    const size_t lds = (size_t)a.lds.env_bytes * (size_t)a.epw;
-    dim3 grid((unsigned)((a.B + a.epw - 1) / a.epw)), block(block_threads);
-    hipError_t err = hipSuccess;
-    const int lpt = a.lpt;
-    const bool full = lpt > 0 && a.epw == 1 && a.N == lpt * a.tpe && block_threads == a.tpe && !a.fuse_obs;
-    const bool lists = a.walk == 2 && lpt > 0 && a.reward_fn != 3;
-    const bool hot = a.action_mode == 0 && a.col_mode == 0 && a.n_fixed == 0 && a.act_stride == a.N && a.reward_fn == 1 &&
-                     (a.walk == 0 || lists) && a.prefetch_envs > 0 && (a.ablate & 8191) == 0 &&
-                     a.mask_words > 0 && (mode == PL_INV_SQUARE || mode == PL_POWER || mode == PL_POWK) && !a.lpos_lo;
-    const int hot_opt = (a.rec_uniform ? OPT_SREC : 0) | (a.nt_results ? OPT_NT : 0);
-    const int xp = a.lpos_lo ? OPT_XPOS : 0;                   // float64 positions (d2d_set_positions_f64): the coord_diff kernels
-    if (a.rollout) return launch_rollout(a, mode, (a.N % 64 ? (hot_opt & OPT_NT) | OPT_PAD : hot_opt) | xp, block_threads, stream);
-    // the rollout configuration with member lists has a kernel of its own (d2d_rollout.hip; chosen by run_step)
-    // level 2: several small envs per workgroup with the LinearObs expansion fused (BASELINE config 2), a fixed prefix
-    // (traffic-model CUEs) allowed
-    const bool hot2 = a.action_mode == 0 && a.col_mode == 0 && a.act_stride > 0 && a.reward_fn == 1 && a.write_table &&
-                      a.walk == 0 && a.prefetch_envs > 0 && (a.ablate & 8191) == 0 && a.mask_words > 0 &&
-                      a.fuse_obs == 4 && a.obs_q_per_row > 0 && !a.lpos_lo &&
-                      (mode == PL_INV_SQUARE || mode == PL_POWER || mode == PL_POWK);
+hipError_t launch_step(const StepArgs& a, const StepPlan& p, hipStream_t stream) {
+    const StepKernel& k = p.kernel;
+    if (k.rollout) return launch_rollout(a, p, stream);
+    const dim3 grid(p.grid), block(p.block);
+    const size_t lds = p.lds_bytes;
+    hipError_t err = hipErrorInvalidDeviceFunction;           // a kernel identity that names no instantiation
 #define D2D_LAUNCH_1(...)                                                                                \
     do {                                                                                                 \
+        err = hipSuccess;                                                                                \
         if (lds > 48 * 1024)                                                                             \
             err = hipFuncSetAttribute(reinterpret_cast<const void*>(&step_kernel<__VA_ARGS__>),          \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);             \
@@ -900,46 +859,41 @@ hipError_t launch_step(const StepArgs& a, PlMode mode, int block_threads, hipStr
             err = hipGetLastError();                                                                     \
         }                                                                                                \
     } while (0)
-#define D2D_LAUNCH_HOT1(M)                                                                               \
+#define D2D_LAUNCH_L(M, L)                              /* (the strided kernels take no member lists) */   \
     do {                                                                                                 \
-        switch (hot_opt) {                                                                               \
-            case 0: D2D_LAUNCH_1(M, 1, true, 1, 0); break;                                               \
-            case OPT_SREC: D2D_LAUNCH_1(M, 1, true, 1, OPT_SREC); break;                                 \
-            case OPT_NT: D2D_LAUNCH_1(M, 1, true, 1, OPT_NT); break;                                     \
-            default: D2D_LAUNCH_1(M, 1, true, 1, OPT_SREC | OPT_NT); break;                              \
-        }                                                                                                \
-    } while (0)
-#define D2D_LAUNCH_L(M, L)                                                                               \
-    do {                                                                                                 \
-        if (lpt == 2 && full) D2D_LAUNCH_1(M, 2, true, 0, L);                                            \
-        else if (lpt == 2) D2D_LAUNCH_1(M, 2, false, 0, L);                                              \
-        else if (lpt == 1 && full) D2D_LAUNCH_1(M, 1, true, 0, L);                                       \
-        else if (lpt == 1) D2D_LAUNCH_1(M, 1, false, 0, L);                                              \
+        if (k.lpt == 2 && k.full) D2D_LAUNCH_1(M, 2, true, 0, L);                                        \
+        else if (k.lpt == 2) D2D_LAUNCH_1(M, 2, false, 0, L);                                            \
+        else if (k.lpt == 1 && k.full) D2D_LAUNCH_1(M, 1, true, 0, L);                                   \
+        else if (k.lpt == 1) D2D_LAUNCH_1(M, 1, false, 0, L);                                            \
         else D2D_LAUNCH_1(M, 0, false, 0, (L) & OPT_XPOS);                                               \
     } while (0)
 #define D2D_LAUNCH_COLD(M)                                                                               \
-    do {                                                                                                 \
-        if (xp) { if (lists) D2D_LAUNCH_L(M, OPT_LISTS | OPT_XPOS); else D2D_LAUNCH_L(M, OPT_XPOS); }    \
-        else if (lists) D2D_LAUNCH_L(M, OPT_LISTS);                                                      \
-        else D2D_LAUNCH_L(M, 0);                                                                         \
-    } while (0)
-#define D2D_LAUNCH(M)                                                                                    \
-    do {                                                                                                 \
-        if (lpt == 1 && full && hot) D2D_LAUNCH_HOT1(M);                                                 \
-        else if (lpt == 1 && !full && hot2) D2D_LAUNCH_1(M, 1, false, 2, 0);                             \
-        else D2D_LAUNCH_COLD(M);                                                                         \
-    } while (0)
-    switch (mode) {
+    switch (k.opt) {                                                                                     \
+        case OPT_LISTS | OPT_XPOS: D2D_LAUNCH_L(M, OPT_LISTS | OPT_XPOS); break;                         \
+        case OPT_XPOS: D2D_LAUNCH_L(M, OPT_XPOS); break;                                                 \
+        case OPT_LISTS: D2D_LAUNCH_L(M, OPT_LISTS); break;                                               \
+        case 0: D2D_LAUNCH_L(M, 0); break;                                                               \
+    }
+#define D2D_LAUNCH(M)                                   /* the power laws: HOT levels 1 and 2 as well */   \
+    if (k.hot == 1) {                                                                                    \
+        switch (k.opt) {                                                                                 \
+            case 0: D2D_LAUNCH_1(M, 1, true, 1, 0); break;                                               \
+            case OPT_SREC: D2D_LAUNCH_1(M, 1, true, 1, OPT_SREC); break;                                 \
+            case OPT_NT: D2D_LAUNCH_1(M, 1, true, 1, OPT_NT); break;                                     \
+            case OPT_SREC | OPT_NT: D2D_LAUNCH_1(M, 1, true, 1, OPT_SREC | OPT_NT); break;               \
+        }                                                                                                \
+    } else if (k.hot == 2) D2D_LAUNCH_1(M, 1, false, 2, 0);                                              \
+    else { D2D_LAUNCH_COLD(M) }
+    switch (k.mode) {
         case PL_INV_SQUARE: D2D_LAUNCH(PL_INV_SQUARE); break;
         case PL_POWER: D2D_LAUNCH(PL_POWER); break;
         case PL_POWK: D2D_LAUNCH(PL_POWK); break;
-        case PL_TABLE: D2D_LAUNCH_COLD(PL_TABLE); break;          // the rollout specialisations exist for the power laws only
+        case PL_TABLE: D2D_LAUNCH_COLD(PL_TABLE); break;
         case PL_SHADOW: D2D_LAUNCH_COLD(PL_SHADOW); break;
-        case PL_TABLE_DB: D2D_LAUNCH_COLD(PL_TABLE_DB); break;    // the live dB table (D2D_PL_TABLE_LIVE)
+        case PL_TABLE_DB: D2D_LAUNCH_COLD(PL_TABLE_DB); break;
     }
 #undef D2D_LAUNCH
 #undef D2D_LAUNCH_COLD
-#undef D2D_LAUNCH_HOT1
 #undef D2D_LAUNCH_L
 #undef D2D_LAUNCH_1
     return err;

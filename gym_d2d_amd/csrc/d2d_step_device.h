@@ -218,7 +218,7 @@ __device__ __forceinline__ float table_gain_db(const StepArgs& a, const void* en
     return (float)exp2(-0.33219280948873623478703194294894 * x);
 }
 
-// LDS layout of ONE env (byte offsets, all computed on the host by step_lds_layout and passed in StepArgs::lds):
+// LDS layout of ONE env (byte offsets, all computed on the host by plan_step and passed in StepArgs::lds):
 //   0    red[16] f32   wave partial sums            64   flags[4] i32   0: env flags  1: reward violated  2: ticket
 //   80   link[N] float4  tx_x, tx_y, effective tx power (mW, incl. tx side of the PL constant), rb bits
 //   then ONLY what the configuration reads back from LDS:
@@ -231,7 +231,6 @@ __device__ __forceinline__ float table_gain_db(const StepArgs& a, const void* en
 //   off_mask: mask[W][R] u32 per-RB membership, word-major (lanes with different RBs hit different banks),
 //             side[W] u32 sidelink membership, summ[R] u32 (bit w set <=> mask[w][rb] != 0)
 // At N = 512, R = 256, inverse-square path loss, SystemCapacity: 10.3 KB + 17.4 KB masks = 27.7 KB per env.
-#define LDS_HEAD_BYTES 80u
 
 struct Smem {
     float* red; int* flags; float4* link; float2* rx; float* sinr; float* sh; float2* expo; float2* lo; int* aux; float* tflat;
@@ -447,12 +446,5 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 // branch weights: block placement moves the rare arms (invalid actions, all-pairs sweep, flag reporting) behind the hot path
 // rare arms (a reward rule's search when it fires, the sweep fallbacks): LLVM's loop vectoriser otherwise unrolls and widens
 // them into hundreds of instructions whose live values spill the hot path's scalars
-
-// kernel options (template parameter OPT of step_kernel / rollout_kernel)
-#define OPT_LISTS 1      /* generic kernels: per-RB member lists instead of the masks (StepArgs::walk == 2) */
-#define OPT_SREC 2       /* rollout kernel: link records by scalar loads (StepArgs::rec_uniform) */
-#define OPT_NT 4         /* rollout kernel: nontemporal result stores (StepArgs::nt_results) */
-#define OPT_PAD 8        /* rollout kernel: N is no multiple of 64 (threads beyond the last link shadow it) */
-#define OPT_XPOS 16      /* exact positions: every coordinate is a (hi, lo) float pair (StepArgs::lpos_lo, d2d_set_positions_f64) */
 
 }  // namespace d2d
