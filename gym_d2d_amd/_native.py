@@ -1,5 +1,5 @@
-"""ctypes binding of libd2d_hip.so (include/d2d_hip.h), libd2d_plugin.so (include/d2d_plugin.h) and libd2d_episode.so
-(include/d2d_episode.h).  There is no CPU fallback: if a library or a gfx950 GPU is missing, the calls below raise."""
+"""ctypes binding of libd2d_hip.so (include/d2d_hip.h), libd2d_plugin.so (include/d2d_plugin.h), libd2d_episode.so
+(include/d2d_episode.h) and libd2d_sense.so (include/d2d_sense.h).  There is no CPU fallback: if a library or a gfx950 GPU is missing, the calls below raise."""
 from __future__ import annotations
 
 import ctypes as C
@@ -11,6 +11,7 @@ import numpy as np
 LIB_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_hip.so'
 PLUGIN_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_plugin.so'
 EPISODE_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_episode.so'
+SENSE_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_sense.so'
 ABI_VERSION = 7
 MAX_LINKS = 2048
 
@@ -41,6 +42,10 @@ REWARD_PER_AGENT, REWARD_PER_ENV = 0, 1
 # d2d_dtype
 F32, F64 = 0, 1
 UNIQUE_ID_BYTES = 128
+# d2d_sense_rb's what / law (include/d2d_sense.h)
+SENSE_SINR_DB, SENSE_INTERFERENCE_MW = 0, 1
+SENSE_LAW_INV_SQUARE, SENSE_LAW_POWER, SENSE_LAW_POW_K = 0, 1, 2
+SENSE_MAX_RBS = 8192
 
 BUFFER_DTYPES = {BUF_ACTIONS: np.int32, BUF_RB: np.int32, BUF_PWR: np.int32, BUF_ENV_FLAGS: np.int32, BUF_RESET_PENDING: np.int32,
                  BUF_EPISODE: np.uint32}
@@ -134,9 +139,17 @@ EPISODE_SIGNATURES = {
     'd2d_episode_last_error': (C.c_char_p, []),
 }
 
+# every symbol include/d2d_sense.h declares
+SENSE_SIGNATURES = {
+    'd2d_sense_rb': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, C.c_int64, _I, _I, _I, _I, _P, _P]),
+    'd2d_sense_last_error': (C.c_char_p, []),
+}
+
 _lib: Optional[C.CDLL] = None
 _plugin: Optional[C.CDLL] = None
 _episode: Optional[C.CDLL] = None
+_sense: Optional[C.CDLL] = None
+sense_launches = 0                  # d2d_sense_rb calls made through sense_rb() in this process
 
 
 def load_library() -> C.CDLL:
@@ -219,6 +232,35 @@ def episode_advance(pending_ptr: int, episode_ptr: int, elapsed_ptr: int, done_p
     _check_episode(load_episode_library().d2d_episode_advance(
         _P(pending_ptr), _P(episode_ptr), _P(elapsed_ptr), _P(done_ptr), _P(reset_ptr), _P(reward_ptr or None), reward_cols, n_envs,
         episode_length, _P(stream_ptr or None)))
+
+
+def load_sense_library() -> C.CDLL:
+    """dlopen libd2d_sense.so and type its entry points.  Raises if it has not been built."""
+    global _sense
+    if _sense is not None:
+        return _sense
+    if not SENSE_PATH.exists():
+        raise ImportError(f'{SENSE_PATH} is missing - build it with `python -m gym_d2d_amd.build`')
+    lib = C.CDLL(str(SENSE_PATH))
+    for name, (res, args) in SENSE_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    _sense = lib
+    return lib
+
+
+def sense_rb(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, link_tx_ptr: int, link_rx_ptr: int, cols_ptr: int, law: int,
+             pow_k: int, n_envs: int, n_dev: int, n_links: int, n_rbs: int, what: int, out_ptr: int, stream_ptr: int = 0) -> None:
+    """d2d_sense_rb: every link's SINR (dB) or interference (mW) on every RB into out [n_envs, n_links, n_rbs] (device pointers)."""
+    global sense_launches
+    lib = load_sense_library()
+    rc = lib.d2d_sense_rb(_P(pos_x_ptr or None), _P(pos_y_ptr or None), _P(rb_ptr or None), _P(pwr_ptr or None), _P(link_tx_ptr or None),
+                          _P(link_rx_ptr or None), _P(cols_ptr or None), law, pow_k, n_envs, n_dev, n_links, n_rbs, what,
+                          _P(out_ptr or None), _P(stream_ptr or None))
+    if rc != 0:
+        raise NativeError(rc, lib.d2d_sense_last_error().decode(errors='replace'))
+    sense_launches += 1
 
 
 def _check(rc: int) -> None:

@@ -2,7 +2,7 @@
 `gym_d2d_amd.envs.env_config` without dragging in d2d_env (which imports the simulator) - the reference has exactly
 this cycle and fails on `import gym_d2d.simulator` first."""
 
-__all__ = ['D2DEnv', 'VecD2DEnv']
+__all__ = ['D2DEnv', 'VecD2DEnv', 'RbSensingObsFunction']
 
 
 def __getattr__(name):
@@ -12,4 +12,7 @@ def __getattr__(name):
     if name == 'VecD2DEnv':
         from .vec_env import VecD2DEnv
         return VecD2DEnv
+    if name == 'RbSensingObsFunction':
+        from .obs_fn import RbSensingObsFunction
+        return RbSensingObsFunction
     raise AttributeError(name)

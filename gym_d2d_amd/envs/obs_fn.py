@@ -51,8 +51,11 @@ class LinearObsFunction(ObsFunction):
 
 class ArrayObsFunction(ABC):
     """Batched plugin: compute(view) -> [B, N, width] array/tensor.  `view` has pos_x/pos_y [B,D], rb, pwr, sinr_db,
-    snr_db, rate_bps, capacity_mbps [B,N], table [B,N,6], link_tx/link_rx/link_type [N]."""
+    snr_db, rate_bps, capacity_mbps [B,N], table [B,N,6], link_tx/link_rx/link_type [N].  A subclass that sets
+    `needs_rb_sensing = True` also gets rb_sinr_db [B,N,R]: VecD2DEnv runs the sensing kernel (VecD2DEnv.sense) after every step
+    for it; without the attribute nothing is launched or allocated."""
     native_mode = _native.OBS_TABLE
+    needs_rb_sensing = False
 
     @abstractmethod
     def get_obs_space(self, env_config) -> Space:
@@ -87,3 +90,18 @@ class SignalPlanesObsFunction(ArrayObsFunction):
 
     def compute(self, view):
         return view.sinr_db, view.snr_db
+
+
+class RbSensingObsFunction(ArrayObsFunction):
+    """Each agent observes the SINR (dB) it would get on every resource block at its current power, everything else as the last
+    step left it: [B, N, R] = VecD2DEnv.sense('sinr_db'), evaluated by csrc/d2d_sense.hip after every step.  Column rb[b, i] is the
+    step's own sinr_db; an RB nobody else uses shows the link's SNR.  Width R instead of LinearObs's 6N.  The tensor is the env's
+    own sensing block, rewritten by every step (clone it to keep a step's values)."""
+    native_mode = _native.OBS_NONE
+    needs_rb_sensing = True
+
+    def get_obs_space(self, env_config) -> Space:
+        return Box(low=-np.inf, high=np.inf, shape=(env_config.num_rbs,))
+
+    def compute(self, view):
+        return view.rb_sinr_db

@@ -22,7 +22,7 @@ from typing import Optional
 
 import numpy as np
 
-from .. import _native
+from .. import _native, sensing
 from ..path_loss_table import NATIVE, PER_STEP
 from ..simulator import BASE_STATION_ID, Simulator
 from ..traffic_model import DownlinkTrafficModel
@@ -175,6 +175,11 @@ class VecD2DEnv:
         self.autoreset = bool(autoreset)
         if self.autoreset:
             self._setup_autoreset()
+        # per-RB sensing (sense()): nothing is built, allocated or launched unless sense() is called or the obs function asks
+        self._sensor = None
+        self._senses = bool(getattr(self.obs_fn, 'needs_rb_sensing', False))
+        if self._senses:
+            self._rb_sensor()                      # refusals surface here, not inside the first step
 
     def _setup_autoreset(self) -> None:
         """Refuse what a device-side per-env reset cannot serve, then allocate the per-env bookkeeping: pending / episode are bound
@@ -487,7 +492,45 @@ class VecD2DEnv:
         self._follow_torch_stream()
         self._t['pending'].masked_fill_(m, 1)
 
+    # ------------------------------------------------------------------ per-RB sensing
+    def _rb_sensor(self):
+        if self._sensor is None:
+            why = sensing.refusal(self.simulator, self.export_actions)
+            if why:
+                raise ValueError(why)
+            self._sensor = sensing.RbSensor(self.simulator, self.num_links, torch if self.use_torch else None,
+                                            self.device if self.use_torch else None)
+        return self._sensor
+
+    def sense(self, what: str = 'sinr_db', out=None):
+        """What every link would see on every resource block, with everything else as the last step left it: float32 [B, N, R].
+
+        what='sinr_db': sense[b, i, r] is the SINR (dB) link i would get if it alone moved to RB r at its current power - column
+        rb[b, i] is the step's own sinr_db, an RB nobody else uses gives the link's SNR.  what='interference_mw': the sum, in mW, of
+        what the other links on RB r put into link i's receiver (0.0 exactly on an RB nobody else uses).  One kernel launch
+        (csrc/d2d_sense.hip).  Valid after reset() and after every step(), autoreset steps included: an env that was reset inside
+        the step is sensed at its new positions and its reset's random actions.
+
+        torch path: enqueued on torch's current stream, nothing is synchronised; the result is ONE tensor the env owns and
+        rewrites on every call (clone it to keep it), or `out` (contiguous float32 [B, N, R] on the env's device) if given.
+        NumPy path: a fresh array, or `out`.
+
+        Serves the native power-law models (LogDistance with any exponent, FreeSpace, COST-Hata, per-device overrides, uplink
+        and downlink CUE links).  ValueError for what it cannot serve: export_actions=False (it reads the decoded planes),
+        ShadowingPathLoss, every table route (device_table, link_table, array, per_step), pinned device_config coordinates
+        float32 cannot hold."""
+        if what not in sensing.WHAT:
+            raise ValueError("what must be 'sinr_db' or 'interference_mw'")
+        sensor = self._rb_sensor()
+        if self.use_torch:
+            self._follow_torch_stream()
+            return sensor.sense_torch(self._t, sensing.WHAT[what], out, self._stream_ptr)
+        return sensor.sense_numpy(sensing.WHAT[what], out)
+
     def _observe(self, view):
+        if self._senses:
+            # a namespace of its own: the cached view stays what every other consumer sees
+            view = SimpleNamespace(**vars(view), rb_sinr_db=self.sense('sinr_db'))
         obs = self.obs_fn.compute(view) if self._array_obs else view.obs
         if self._obs64 and not self._native_obs64 and not isinstance(obs, tuple):   # the reference's dtype (obs_fn.py:51) for a custom array obs: cast here
             obs = obs.double() if self.use_torch else np.asarray(obs, dtype=np.float64)
@@ -517,4 +560,7 @@ class VecD2DEnv:
         return self.simulator.handle.status_flags()
 
     def close(self) -> None:
+        if self._sensor is not None:
+            self._sensor.close()
+            self._sensor = None
         self.simulator.handle.close()

@@ -1,0 +1,162 @@
+"""Per-RB interference sensing: the host side of libd2d_sense.so (include/d2d_sense.h, csrc/d2d_sense.hip).
+
+`fold_columns` lowers the per-device link-budget and power-law columns to the float32 block the kernel reads, in double precision
+and by the rules the step's own records follow (csrc/d2d_capi.hip, refresh_tables), so that the sensed column of a link's own RB is
+the step's sinr_db.  `RbSensor` owns the device-side constants of one env object (link lists, columns) and launches the kernel on
+device pointers: torch tensors on the torch path, plain HIP allocations on the NumPy path.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Tuple
+
+import numpy as np
+
+from . import _native
+from .path_loss_table import NATIVE
+
+WHAT = {'sinr_db': _native.SENSE_SINR_DB, 'interference_mw': _native.SENSE_INTERFERENCE_MW}
+
+
+def fold_columns(budget: dict, law: dict, link_tx: np.ndarray) -> Tuple[np.ndarray, int, int]:
+    """(cols float32 [6, D], law id, pow_k) of d2d_sense_rb from link_budget_columns() and PathLoss.power_law_columns()."""
+    a_tx, a_rx, expo = (np.asarray(law[k], dtype=np.float64) for k in ('a_tx_db', 'a_rx_db', 'exponent'))
+    d = len(a_tx)
+    cols = np.zeros((6, d), dtype=np.float32)
+    with np.errstate(over='ignore'):
+        cols[0] = 10.0 ** ((np.asarray(budget['eirp_off_db'], dtype=np.float64) - a_tx) / 10.0)
+        cols[1] = 10.0 ** (-a_rx / 10.0)
+        cols[2] = 10.0 ** (np.asarray(budget['rx_off_db'], dtype=np.float64) / 10.0)
+        cols[3] = 10.0 ** (np.asarray(budget['noise_dbm'], dtype=np.float64) / 10.0)
+    if not ((cols[:4] >= 1.0e-30) & (cols[:4] <= 1.0e30)).all():
+        raise ValueError('a link-budget constant is outside the float32 linear range 1e-30 .. 1e30 (a term beyond +-300 dB)')
+    if (expo == 2.0).all():
+        return cols, _native.SENSE_LAW_INV_SQUARE, 0
+    # every link transmitter's exponent within 1/2 of one integer k in 1 .. 8: (d^2)^(-k/2) by reciprocals times (d^2)^phi
+    tx_expo = expo[np.asarray(link_tx, dtype=np.int64)]
+    k0 = int(np.floor(tx_expo[0] + 0.5)) if len(tx_expo) else 0        # lround: half away from zero for the positive exponents here
+    for k in (k0, k0 + 1, k0 - 1):
+        if 1 <= k <= 8 and len(tx_expo) and (np.abs(tx_expo - k) <= 0.5).all():
+            cols[4] = -0.5 * (expo - k)
+            return cols, _native.SENSE_LAW_POW_K, k
+    # the general split: -exponent / 2 as a head with 12 leading mantissa bits and the rest of the double as the tail
+    hd = -0.5 * expo
+    head = (hd.astype(np.float32).view(np.uint32) & np.uint32(0xFFFFF000)).view(np.float32)
+    cols[4] = head
+    cols[5] = hd - head.astype(np.float64)
+    return cols, _native.SENSE_LAW_POWER, 0
+
+
+def refusal(sim, export_actions: bool) -> Optional[str]:
+    """Why this env cannot be sensed (None: it can).  Each text names the route or the switch."""
+    if not export_actions:
+        return ('sense() reads the decoded (rb, tx power) planes, which export_actions=False does not write: build the env with '
+                'export_actions=True')
+    route = sim.path_loss_table.route
+    if route != NATIVE:
+        return (f"sense() does not serve the '{route}' path-loss route (a table, not a law the sensing kernel can evaluate for the "
+                'pairs no step reads); it serves the native power-law models')
+    if sim.path_loss_table.law.get('shadowing'):
+        return ('sense() does not serve ShadowingPathLoss: a fresh draw per evaluation has no counterfactual (what another RB '
+                'would have given is another draw)')
+    mask, xy = sim.fixed_positions()
+    if mask.any() and (xy != xy.astype(np.float32)).any():
+        return ('sense() does not serve pinned device_config coordinates that float32 cannot hold: their low parts live inside '
+                'the handle (float64 positions)')
+    return None
+
+
+class _HipMemory:
+    """The few HIP runtime calls the NumPy path needs for memory of its own (the torch path allocates through torch)."""
+
+    def __init__(self) -> None:
+        self.hip = C.CDLL('libamdhip64.so')
+        self.hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+        self.hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+        self.hip.hipFree.argtypes = [C.c_void_p]
+        self.blocks = []
+
+    def _ok(self, rc: int, what: str) -> None:
+        if rc != 0:
+            raise _native.NativeError(rc, f'{what} failed (hipError_t {rc})')
+
+    def alloc(self, nbytes: int) -> int:
+        p = C.c_void_p()
+        self._ok(self.hip.hipMalloc(C.byref(p), max(int(nbytes), 4)), 'hipMalloc')
+        self.blocks.append(p.value)
+        return p.value
+
+    def upload(self, array: np.ndarray) -> int:
+        a = np.ascontiguousarray(array)
+        p = self.alloc(a.nbytes)
+        self._ok(self.hip.hipMemcpy(p, a.ctypes.data, a.nbytes, 1), 'hipMemcpy')          # hipMemcpyHostToDevice; synchronous
+        return p
+
+    def download(self, ptr: int, out: np.ndarray) -> None:
+        self._ok(self.hip.hipMemcpy(out.ctypes.data, ptr, out.nbytes, 2), 'hipMemcpy')    # hipMemcpyDeviceToHost; synchronous
+
+    def free(self, ptr: int) -> None:
+        self.blocks.remove(ptr)
+        self._ok(self.hip.hipFree(ptr), 'hipFree')
+
+    def close(self) -> None:
+        for p in list(self.blocks):
+            self.free(p)
+
+
+class RbSensor:
+    """The sensing kernel bound to one env object: constants uploaded once, one launch per call."""
+
+    def __init__(self, sim, num_links: int, torch=None, device=None) -> None:
+        from .device import link_budget_columns
+        self.sim, self.torch, self.device = sim, torch, device
+        h = sim.handle
+        self.b, self.d, self.n, self.r = sim.num_envs, h.num_devices, int(num_links), int(sim.config.num_rbs)
+        if self.r > _native.SENSE_MAX_RBS:
+            raise ValueError(f'sense() serves at most {_native.SENSE_MAX_RBS} RBs (num_rbs = {self.r})')
+        tx, rx = np.asarray(sim.link_tx, dtype=np.int32), np.asarray(sim.link_rx, dtype=np.int32)
+        if len(tx) != self.n or tx.min() < 0 or tx.max() >= self.d or rx.min() < 0 or rx.max() >= self.d:
+            raise ValueError('the link list does not match the env')
+        cols, self.law, self.pow_k = fold_columns(link_budget_columns(sim._dev_list), sim.path_loss_table.law, tx)
+        self.own = None                              # the result block this object owns, allocated by the first call without out=
+        if torch is not None:
+            self.tx, self.rx, self.cols = (torch.as_tensor(a, device=device) for a in (tx, rx, cols))
+            self.ptrs = tuple(t.data_ptr() for t in (self.tx, self.rx, self.cols))
+        else:
+            self.mem = _HipMemory()
+            self.ptrs = tuple(self.mem.upload(a) for a in (tx, rx, cols))
+
+    def launch(self, pos_x: int, pos_y: int, rb: int, pwr: int, what: int, out: int, stream: int = 0) -> None:
+        _native.sense_rb(pos_x, pos_y, rb, pwr, *self.ptrs, self.law, self.pow_k, self.b, self.d, self.n, self.r, what, out, stream)
+
+    def sense_torch(self, t: dict, what: int, out, stream: int):
+        torch = self.torch
+        shape = (self.b, self.n, self.r)
+        if out is None:
+            if self.own is None:
+                self.own = torch.empty(shape, dtype=torch.float32, device=self.device)
+            out = self.own
+        elif not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() \
+                or out.device != self.device:
+            raise ValueError(f'out must be a contiguous float32 tensor {list(shape)} on {self.device}')
+        self.launch(t['pos_x'].data_ptr(), t['pos_y'].data_ptr(), t['rb'].data_ptr(), t['pwr'].data_ptr(), what, out.data_ptr(), stream)
+        return out
+
+    def sense_numpy(self, what: int, out):
+        h = self.sim.handle
+        shape = (self.b, self.n, self.r)
+        if out is not None and (not isinstance(out, np.ndarray) or out.shape != shape or out.dtype != np.float32
+                                or not out.flags.c_contiguous):
+            raise ValueError(f'out must be a C-contiguous float32 ndarray {list(shape)}')
+        h.synchronize()                               # the planes are the last step's; the kernel runs on the null stream
+        ptr = {w: h.get_buffer(w)[0] for w in (_native.BUF_POS_X, _native.BUF_POS_Y, _native.BUF_RB, _native.BUF_PWR)}
+        if self.own is None:
+            self.own = self.mem.alloc(self.b * self.n * self.r * 4)
+        self.launch(ptr[_native.BUF_POS_X], ptr[_native.BUF_POS_Y], ptr[_native.BUF_RB], ptr[_native.BUF_PWR], what, self.own)
+        res = out if out is not None else np.empty(shape, dtype=np.float32)
+        self.mem.download(self.own, res)              # synchronous on the null stream: behind the kernel
+        return res
+
+    def close(self) -> None:
+        if self.torch is None:
+            self.mem.close()

@@ -1,0 +1,395 @@
+"""Per-RB interference sensing on the GPU (VecD2DEnv.sense, RbSensingObsFunction, csrc/d2d_sense.hip) against the oracle.
+
+The yardstick is the oracle's own step on the B0 * N * R envs in which one link moved (rb_sensing_util.counterfactual), which
+test_rb_sensing_cpu.py ties to the reference at 1e-9; the bar is the project's 1e-5 on dB quantities (golden_util.rel_err).  Every
+entry is compared: the layouts come from sim_util.random_layout, which never places two interacting devices on one point."""
+import json
+import runpy
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import rb_sensing_util as rbs
+from golden_util import GOLDEN_DIR, load_case, rel_err
+from oracle import d2d_oracle as orc
+from sim_util import env_config_for, oracle_spec, random_layout
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip('torch')
+ROOT = Path(__file__).resolve().parent.parent
+BAR = 1e-5
+
+
+def _models():
+    from gym_d2d_amd.path_loss import AreaType, CostHataPathLoss, LogDistancePathLoss
+
+    class Ple35(LogDistancePathLoss):
+        def __init__(self, f):
+            super().__init__(f, ple=3.5)
+
+    class Urban(CostHataPathLoss):
+        def __init__(self, f):
+            super().__init__(f, AreaType.URBAN)
+
+    class Suburban(CostHataPathLoss):
+        def __init__(self, f):
+            super().__init__(f, AreaType.SUBURBAN)
+    return {'ld2': (LogDistancePathLoss, orc.PathLossSpec('log_distance', 2.1, ple=2.0)),
+            'ld35': (Ple35, orc.PathLossSpec('log_distance', 2.1, ple=3.5)),
+            'urban': (Urban, orc.PathLossSpec('cost_hata', 2.1, area='urban')),
+            'suburban': (Suburban, orc.PathLossSpec('cost_hata', 2.1, area='suburban'))}
+
+
+# name: (B0, cues, due pairs, RBs, model, cue_actions, downlink traffic model)
+CASES = {
+    'small_ld2_agent': (3, 8, 8, 5, 'ld2', 'agent', False),
+    'mid_ld35_agent': (2, 64, 96, 24, 'ld35', 'agent', False),
+    'crowded_urban_traffic_up': (2, 64, 64, 8, 'urban', 'traffic', False),          # 16 links per RB
+    'empty_suburban_traffic_down': (2, 6, 6, 40, 'suburban', 'traffic', True),      # 12 links on 40 RBs
+    'mid_ld2_traffic_down': (2, 24, 40, 16, 'ld2', 'traffic', True),
+    'small_urban_agent': (3, 8, 8, 5, 'urban', 'agent', False),
+    'small_suburban_traffic_up': (3, 8, 8, 5, 'suburban', 'traffic', False),
+    'case07_device_config': None,                                                    # golden case07's per-device overrides
+}
+_cache = {}
+
+
+def _state(env):
+    t = env._t
+    torch.cuda.synchronize()
+    pos = np.stack([t['pos_x'].cpu().numpy(), t['pos_y'].cpu().numpy()], axis=-1).astype(np.float64)
+    return pos, t['rb'].cpu().numpy().astype(np.int64), t['pwr'].cpu().numpy().astype(np.int64)
+
+
+def _build(name):
+    """An env stepped once on a random_layout, its sensed blocks, the step's planes and the oracle's side - computed once per case."""
+    if name in _cache:
+        return _cache[name]
+    from gym_d2d_amd.envs import VecD2DEnv
+    from gym_d2d_amd.traffic_model import DownlinkTrafficModel
+    rng = np.random.default_rng(sum(map(ord, name)))
+    if CASES[name] is None:
+        case = load_case('case07_device_config')
+        b0, cue_actions = 2, 'agent'
+        cfg = env_config_for(case)
+        cues, dues, r = case.meta['num_cues'], case.meta['num_due_pairs'], case.meta['num_rbs']
+        spec = oracle_spec(case)
+        cols = orc.device_columns(case.cfgs, case.is_bs)
+    else:
+        b0, cues, dues, r, model, cue_actions, down = CASES[name]
+        cls, spec = _models()[model]
+        cfg = {'num_rbs': r, 'num_cues': cues, 'num_due_pairs': dues, 'path_loss_model': cls}
+        if down:
+            cfg['traffic_model'] = DownlinkTrafficModel
+        cols = orc.device_columns(*orc.device_configs(cues, dues)[1:])
+    env = VecD2DEnv(cfg, num_envs=b0, cue_actions=cue_actions)
+    env.reset(seed=3)
+    if CASES[name] is not None:              # (case07 pins devices: the layout its reset drew around them stays)
+        env.simulator.set_positions(random_layout(rng, b0, cues, dues))
+    p = env.num_pwr_actions
+    highs = ([r * p[env._cue_kind]] * cues if cue_actions == 'agent' else []) + [r * p['due']] * dues
+    actions = torch.as_tensor(rng.integers(0, highs, (b0, len(highs))).astype(np.int32), device=env.device)
+    _, _, _, info = env.step(actions)
+    sinr = env.sense('sinr_db').cpu().numpy()
+    ix = env.sense('interference_mw').cpu().numpy()
+    pos, rb, pwr = _state(env)
+    tx, rx = env.simulator.link_tx, env.simulator.link_rx
+    out = dict(env=env, sinr=sinr, ix=ix, pos=pos, rb=rb, pwr=pwr, tx=tx, rx=rx, cols=cols, spec=spec, r=r,
+               step_sinr=info['sinr_db'].cpu().numpy(), step_snr=info['snr_db'].cpu().numpy(),
+               ref_ix=rbs.interference_mw(pos, tx, rx, rb, pwr, cols, spec, r))
+    assert env.status_flags() == 0
+    _cache[name] = out
+    return out
+
+
+@pytest.fixture(scope='module', autouse=True)
+def _close_envs():
+    yield
+    for c in _cache.values():
+        c['env'].close()
+    _cache.clear()
+
+
+@pytest.mark.parametrize('name', list(CASES))
+def test_counterfactual_against_the_oracle(name):
+    c = _build(name)
+    ref = rbs.counterfactual(c['pos'], c['tx'], c['rx'], c['rb'], c['pwr'], c['cols'], c['spec'], c['r'])
+    assert ref.shape == c['sinr'].shape and np.isfinite(ref).all()
+    e = rel_err(c['sinr'], ref)
+    print(f'{name}: sense(sinr_db) vs oracle counterfactual rel_err {e:.3e} over {ref.size} entries')
+    assert e <= BAR
+
+
+@pytest.mark.parametrize('name', list(CASES))
+def test_interference_against_the_fp64_sum(name):
+    c = _build(name)
+    ref, got = c['ref_ix'], c['ix']
+    empty = ref == 0.0
+    assert (got[empty] == 0.0).all() and (got[~empty] > 0.0).all()
+    e = rel_err(10 * np.log10(got[~empty].astype(np.float64)), 10 * np.log10(ref[~empty]))
+    print(f'{name}: sense(interference_mw) rel_err {e:.3e} in dB, {empty.mean():.2%} of the entries empty')
+    assert e <= BAR
+    if name.startswith('empty'):
+        assert empty.mean() > 0.5
+    if name.startswith('crowded'):
+        assert not empty.any()
+
+
+@pytest.mark.parametrize('name', list(CASES))
+def test_own_rb_column_is_the_step_and_an_empty_rb_gives_the_snr(name):
+    c = _build(name)
+    b, n = c['rb'].shape
+    diag = np.take_along_axis(c['sinr'], c['rb'][:, :, None], axis=2)[:, :, 0]
+    same_bits = np.array_equal(diag.view(np.uint32), c['step_sinr'].view(np.uint32))
+    e = rel_err(diag, c['step_sinr'])
+    print(f'{name}: sense[b, i, rb] vs the step sinr_db: rel_err {e:.3e}, bit-identical {same_bits}')
+    assert e <= BAR
+    assert same_bits                 # measured 0.0 in every case and at full size: the same operations in the same order
+    empty = c['ref_ix'] == 0.0
+    snr = np.broadcast_to(c['step_snr'][:, :, None], empty.shape)
+    e2 = rel_err(c['sinr'][empty], snr[empty])
+    print(f'{name}: on empty RBs vs the step snr_db: rel_err {e2:.3e} over {int(empty.sum())} entries')
+    assert e2 <= BAR
+
+
+def test_full_size_once():
+    """4096 envs x 512 links x 256 RBs (2.1 GB out): finite everywhere, the own-RB column against the step on all 2.1 M links, and
+    all N * R entries of 4 random envs against the fp64 formula."""
+    free, _ = torch.cuda.mem_get_info()
+    if free < 8 << 30:
+        pytest.skip(f'{free >> 20} MiB free: the full-size block and its check need 8 GiB')
+    from gym_d2d_amd.envs import VecD2DEnv
+    from gym_d2d_amd.envs.obs_fn import SignalPlanesObsFunction
+    b, cues, dues, r = 4096, 256, 256, 256
+    env = VecD2DEnv({'num_rbs': r, 'num_cues': cues, 'num_due_pairs': dues, 'obs_fn': SignalPlanesObsFunction}, num_envs=b)
+    try:
+        rng = np.random.default_rng(11)
+        env.reset(seed=5)             # the device-side sampler's layout (reset() raises on a zero distance); random actions
+        _, _, _, info = env.step(env.action_buffer().clone())
+        s = env.sense('sinr_db')
+        assert tuple(s.shape) == (b, cues + dues, r) and bool(torch.isfinite(s).all())
+        diag = torch.gather(s, 2, info['rb'].long().unsqueeze(-1)).squeeze(-1)
+        e = float(((diag - info['sinr_db']).abs() / info['sinr_db'].abs().clamp(min=1.0)).max())
+        print(f'full size: own-RB column vs the step over {diag.numel()} links: rel_err {e:.3e}, '
+              f'bit-identical {bool(torch.equal(diag, info["sinr_db"]))}')
+        assert e <= BAR and torch.equal(diag, info['sinr_db'])
+        picks = np.sort(rng.choice(b, 4, replace=False))
+        pos, rb, pwr = _state(env)
+        cols = orc.device_columns(*orc.device_configs(cues, dues)[1:])
+        tx, rx, spec = env.simulator.link_tx, env.simulator.link_rx, orc.PathLossSpec()
+        ix = rbs.interference_mw(pos[picks], tx, rx, rb[picks], pwr[picks], cols, spec, r)
+        ref = rbs.sinr_from_interference(pos[picks], tx, rx, pwr[picks], cols, spec, ix)
+        e = rel_err(s[torch.as_tensor(picks, device=s.device)].cpu().numpy(), ref)
+        print(f'full size: envs {picks.tolist()} vs the fp64 formula: rel_err {e:.3e}')
+        assert e <= BAR
+        assert env.status_flags() == 0
+    finally:
+        env.close()
+
+
+def test_two_calls_are_bit_identical_and_out_is_honoured_inside_guard_words():
+    c = _build('mid_ld35_agent')
+    env = c['env']
+    b, n, r = c['sinr'].shape
+    again = env.sense('sinr_db').cpu().numpy()
+    assert np.array_equal(again.view(np.uint32), c['sinr'].view(np.uint32))
+    assert np.array_equal(env.sense('interference_mw').cpu().numpy().view(np.uint32), c['ix'].view(np.uint32))
+    own = env.sense('sinr_db')
+    assert env.sense('sinr_db') is own                                   # the env's one block, reused
+    guard, pad, words = 0x5AFEC0DE, 64, b * n * r
+    arena = torch.full((words + 2 * pad,), guard, dtype=torch.int32, device=env.device)
+    out = arena[pad:pad + words].view(torch.float32).view(b, n, r)
+    got = env.sense('sinr_db', out=out)
+    assert got is out
+    host = arena.cpu().numpy()
+    assert (host[:pad] == guard).all() and (host[pad + words:] == guard).all()
+    assert np.array_equal(host[pad:pad + words].view(np.uint32), c['sinr'].reshape(-1).view(np.uint32))
+    with pytest.raises(ValueError, match='out must be'):
+        env.sense('sinr_db', out=torch.empty((b, n, r + 1), device=env.device))
+    with pytest.raises(ValueError, match='what must be'):
+        env.sense('sinr')
+
+
+@pytest.mark.parametrize('n_rbs', [5, 32, 36])
+def test_rb_values_out_of_range_write_nothing_out_of_bounds(n_rbs):
+    """Through the raw entry point: links whose rb is outside [0, R) are on no RB - they interfere with nobody, their own rows are
+    still sensed - and the words around `out` stay as they were."""
+    from gym_d2d_amd import _native
+    dev = torch.device('cuda', 0)
+    rng = np.random.default_rng(n_rbs)
+    b, cues, dues = 3, 7, 30
+    n, d = cues + dues, 1 + cues + 2 * dues
+    pos = random_layout(rng, b, cues, dues)
+    tx = np.array(list(range(1, 1 + cues)) + [1 + cues + 2 * k for k in range(dues)], dtype=np.int32)
+    rx = np.array([0] * cues + [2 + cues + 2 * k for k in range(dues)], dtype=np.int32)
+    rb = rng.integers(0, n_rbs, (b, n)).astype(np.int32)
+    bad = rng.random((b, n)) < 0.3
+    rb[bad] = rng.choice([-1, -7, n_rbs, n_rbs + 1, 2 ** 31 - 1, -2 ** 31], int(bad.sum()))
+    pwr = rng.integers(0, 20, (b, n)).astype(np.int32)
+    ocols = orc.device_columns(*orc.device_configs(cues, dues)[1:])
+    from gym_d2d_amd.sensing import fold_columns
+    law = {'a_tx_db': np.full(d, orc.pl_constant_db(2.1, 2.0)), 'a_rx_db': np.zeros(d), 'exponent': np.full(d, 2.0)}
+    cols, kind, k = fold_columns({'eirp_off_db': ocols.eirp_off_db, 'rx_off_db': ocols.rx_off_db, 'noise_dbm': ocols.noise_dbm}, law, tx)
+    t = [torch.as_tensor(np.ascontiguousarray(a), device=dev) for a in (pos[..., 0], pos[..., 1], rb, pwr, tx, rx, cols)]
+    guard, pad, words = 0x5AFEC0DE, 64, b * n * n_rbs
+    arena = torch.full((words + 2 * pad,), guard, dtype=torch.int32, device=dev)
+    _native.sense_rb(*(x.data_ptr() for x in t), kind, k, b, d, n, n_rbs, _native.SENSE_INTERFERENCE_MW,
+                     arena.data_ptr() + 4 * pad, torch.cuda.current_stream(dev).cuda_stream)
+    torch.cuda.synchronize()                                            # raises if the device faulted
+    host = arena.cpu().numpy()
+    assert (host[:pad] == guard).all() and (host[pad + words:] == guard).all()
+    got = host[pad:pad + words].view(np.float32).reshape(b, n, n_rbs)
+    ref = rbs.interference_mw(pos, tx, rx, rb, pwr, ocols, orc.PathLossSpec(), n_rbs)    # a bad rb matches no column of the one-hot
+    empty = ref == 0.0
+    assert (got[empty] == 0.0).all()
+    assert rel_err(10 * np.log10(got[~empty].astype(np.float64)), 10 * np.log10(ref[~empty])) <= BAR
+
+
+def test_unsupported_routes_are_refused_by_name(tmp_path):
+    from gym_d2d_amd.envs import RbSensingObsFunction, VecD2DEnv
+    from gym_d2d_amd.path_loss import ArrayPathLoss, PathLoss, ShadowingPathLoss
+    small = {'num_rbs': 4, 'num_cues': 3, 'num_due_pairs': 3}
+
+    class Foo(PathLoss):
+        def __call__(self, tx, rx):
+            return 20 * np.log10(tx.position.distance(rx.position)) + 40.0
+
+    class Arr(ArrayPathLoss):
+        def compute(self, view):
+            return 20 * view.xp.log10(view.distance()) + 40.0
+
+    class PerStep(Arr):
+        per_step = True
+
+    def refused(text, cfg=None, **kw):
+        env = VecD2DEnv(dict(small, **(cfg or {})), num_envs=2, **kw)
+        try:
+            env.reset(seed=1)
+            with pytest.raises(ValueError, match=text):
+                env.sense()
+        finally:
+            env.close()
+    refused('export_actions', export_actions=False)
+    refused('ShadowingPathLoss', {'path_loss_model': ShadowingPathLoss})
+    refused("'link_table'", {'path_loss_model': Foo})
+    refused("'array'", {'path_loss_model': Arr})
+    refused("'per_step'", {'path_loss_model': PerStep})
+    pinned = tmp_path / 'pinned.json'
+    pinned.write_text(json.dumps({'cue00': {'position': [100.1, -20.3], 'config': {'max_tx_power_dBm': 23}}}))
+    refused('float32 cannot hold', {'device_config_file': pinned})
+    with pytest.raises(ValueError, match='export_actions'):
+        VecD2DEnv(dict(small, obs_fn=RbSensingObsFunction), num_envs=2, export_actions=False)
+    # one env: the per-object route of a single env
+    env = VecD2DEnv(dict(small, path_loss_model=Foo), num_envs=1)
+    try:
+        env.reset(seed=1)
+        with pytest.raises(ValueError, match="'device_table'"):
+            env.sense()
+    finally:
+        env.close()
+
+
+@pytest.mark.parametrize('autoreset', [False, True])
+def test_rb_sensing_obs_function_returns_the_sensed_block(autoreset):
+    from gym_d2d_amd.envs import RbSensingObsFunction, VecD2DEnv
+    b, cues, dues, r = 16, 6, 10, 7
+    cfg = {'num_rbs': r, 'num_cues': cues, 'num_due_pairs': dues, 'obs_fn': RbSensingObsFunction}
+    env = VecD2DEnv(cfg, num_envs=b, autoreset=autoreset)
+    try:
+        assert env.observation_space.shape == (r,)
+        kw = {'elapsed': np.arange(b) % 10} if autoreset else {}
+        obs = env.reset(seed=9, **kw)
+        assert tuple(obs.shape) == (b, cues + dues, r) and obs.dtype == torch.float32
+        by_hand = torch.empty_like(obs)
+        assert torch.equal(obs.clone(), env.sense('sinr_db', out=by_hand))
+        rng = np.random.default_rng(2)
+        resets = 0
+        for step in range(12):
+            a = torch.as_tensor(rng.integers(0, r * 21, (b, cues + dues)).astype(np.int32), device=env.device)
+            before = env._t['pos_x'].clone()
+            obs, _, _, info = env.step(a)
+            assert tuple(obs.shape) == (b, cues + dues, r)
+            assert torch.equal(obs.clone(), env.sense('sinr_db', out=by_hand))
+            diag = torch.gather(obs, 2, info['rb'].long().unsqueeze(-1)).squeeze(-1)
+            assert rel_err(diag.cpu().numpy(), info['sinr_db'].cpu().numpy()) <= BAR
+            if autoreset:
+                was_reset = info['reset'].cpu().numpy()
+                moved = (env._t['pos_x'] != before).any(dim=1).cpu().numpy()
+                assert np.array_equal(moved, was_reset)          # an env reset inside the step shows its new episode
+                resets += int(was_reset.sum())
+        assert not autoreset or resets >= b
+    finally:
+        env.close()
+
+
+def test_existing_obs_functions_launch_no_sensing_kernel():
+    from gym_d2d_amd import _native
+    from gym_d2d_amd.envs import RbSensingObsFunction, VecD2DEnv
+    from gym_d2d_amd.envs.obs_fn import LinearObsFunction, OwnLinkObsFunction, SignalPlanesObsFunction
+    small = {'num_rbs': 4, 'num_cues': 3, 'num_due_pairs': 3}
+
+    def launches(obs_fn, **kw):
+        before = _native.sense_launches
+        env = VecD2DEnv(dict(small, obs_fn=obs_fn), num_envs=4, **kw)
+        try:
+            env.reset(seed=1)
+            for _ in range(3):
+                env.step(env.action_buffer().clone())
+            assert (env._sensor is None) == (obs_fn is not RbSensingObsFunction)
+        finally:
+            env.close()
+        return _native.sense_launches - before
+    for fn in (LinearObsFunction, OwnLinkObsFunction, SignalPlanesObsFunction):
+        assert launches(fn) == 0
+        assert launches(fn, autoreset=True) == 0
+    assert launches(RbSensingObsFunction) == 4                          # the reset's step and three steps
+
+
+def test_user_array_obs_function_sees_rb_sinr_db():
+    from gym_d2d_amd import _native
+    from gym_d2d_amd.envs import VecD2DEnv
+    from gym_d2d_amd.envs.obs_fn import ArrayObsFunction
+    from gym_d2d_amd.spaces import Box
+
+    class BestRb(ArrayObsFunction):
+        native_mode = _native.OBS_NONE
+        needs_rb_sensing = True
+
+        def get_obs_space(self, env_config):
+            return Box(low=0, high=env_config.num_rbs, shape=(1,))
+
+        def compute(self, view):
+            return view.rb_sinr_db.argmax(dim=2, keepdim=True)
+    env = VecD2DEnv({'num_rbs': 6, 'num_cues': 4, 'num_due_pairs': 4, 'obs_fn': BestRb}, num_envs=5)
+    try:
+        obs = env.reset(seed=2)
+        assert tuple(obs.shape) == (5, 8, 1)
+        assert torch.equal(obs, env.sense().argmax(dim=2, keepdim=True))
+    finally:
+        env.close()
+
+
+def test_numpy_path_matches_the_torch_path():
+    from gym_d2d_amd.envs import VecD2DEnv
+    cfg = {'num_rbs': 6, 'num_cues': 5, 'num_due_pairs': 7}
+    a = VecD2DEnv(dict(cfg), num_envs=4, use_torch=True)
+    b = VecD2DEnv(dict(cfg), num_envs=4, use_torch=False)
+    try:
+        a.reset(seed=4); b.reset(seed=4)
+        sa, sb = a.sense('sinr_db').cpu().numpy(), b.sense('sinr_db')
+        assert isinstance(sb, np.ndarray) and sb.shape == (4, 12, 6)
+        assert np.array_equal(sa.view(np.uint32), sb.view(np.uint32))
+        out = np.empty((4, 12, 6), dtype=np.float32)
+        assert b.sense('interference_mw', out=out) is out
+        assert np.array_equal(out.view(np.uint32), a.sense('interference_mw').cpu().numpy().view(np.uint32))
+    finally:
+        a.close(); b.close()
+
+
+def test_greedy_rb_example_beats_random(capsys):
+    res = runpy.run_path(str(ROOT / 'examples' / 'greedy_rb.py'), run_name='__main__')
+    out = capsys.readouterr().out
+    print(out)
+    assert res['greedy_capacity'] >= res['random_capacity'] > 0.0
+    assert 'greedy' in out and 'random' in out
