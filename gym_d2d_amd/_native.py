@@ -1,5 +1,5 @@
 """ctypes binding of libd2d_hip.so (include/d2d_hip.h), libd2d_plugin.so (include/d2d_plugin.h), libd2d_episode.so
-(include/d2d_episode.h) and libd2d_sense.so (include/d2d_sense.h).  There is no CPU fallback: if a library or a gfx950 GPU is missing, the calls below raise."""
+(include/d2d_episode.h), libd2d_sense.so (include/d2d_sense.h) and libd2d_graph.so (include/d2d_graph.h).  There is no CPU fallback: if a library or a gfx950 GPU is missing, the calls below raise."""
 from __future__ import annotations
 
 import ctypes as C
@@ -12,6 +12,7 @@ LIB_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_hip.so'
 PLUGIN_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_plugin.so'
 EPISODE_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_episode.so'
 SENSE_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_sense.so'
+GRAPH_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_graph.so'
 ABI_VERSION = 7
 MAX_LINKS = 2048
 
@@ -46,6 +47,8 @@ UNIQUE_ID_BYTES = 128
 SENSE_SINR_DB, SENSE_INTERFERENCE_MW = 0, 1
 SENSE_LAW_INV_SQUARE, SENSE_LAW_POWER, SENSE_LAW_POW_K = 0, 1, 2
 SENSE_MAX_RBS = 8192
+# d2d_graph_neighbors's largest k (include/d2d_graph.h)
+GRAPH_MAX_K = 64
 
 BUFFER_DTYPES = {BUF_ACTIONS: np.int32, BUF_RB: np.int32, BUF_PWR: np.int32, BUF_ENV_FLAGS: np.int32, BUF_RESET_PENDING: np.int32,
                  BUF_EPISODE: np.uint32}
@@ -145,11 +148,21 @@ SENSE_SIGNATURES = {
     'd2d_sense_last_error': (C.c_char_p, []),
 }
 
+# every symbol include/d2d_graph.h declares
+GRAPH_SIGNATURES = {
+    'd2d_graph_coupling': (C.c_int, [_P, _P, _P, _P, _P, _I, _I, C.c_int64, _I, _I, _P, _P]),
+    'd2d_graph_neighbors': (C.c_int, [_P, _P, _P, _P, _P, _I, _I, C.c_int64, _I, _I, _I, _P, _P, _P, _P]),
+    'd2d_graph_neighbor_obs': (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int64, _I, _I, _P, _P]),
+    'd2d_graph_last_error': (C.c_char_p, []),
+}
+
 _lib: Optional[C.CDLL] = None
 _plugin: Optional[C.CDLL] = None
 _episode: Optional[C.CDLL] = None
 _sense: Optional[C.CDLL] = None
 sense_launches = 0                  # d2d_sense_rb calls made through sense_rb() in this process
+_graph: Optional[C.CDLL] = None
+graph_launches = {'coupling': 0, 'neighbors': 0, 'neighbor_obs': 0}     # launches made through the graph_*() wrappers in this process
 
 
 def load_library() -> C.CDLL:
@@ -261,6 +274,55 @@ def sense_rb(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, link_tx_
     if rc != 0:
         raise NativeError(rc, lib.d2d_sense_last_error().decode(errors='replace'))
     sense_launches += 1
+
+
+def load_graph_library() -> C.CDLL:
+    """dlopen libd2d_graph.so and type its entry points.  Raises if it has not been built."""
+    global _graph
+    if _graph is not None:
+        return _graph
+    if not GRAPH_PATH.exists():
+        raise ImportError(f'{GRAPH_PATH} is missing - build it with `python -m gym_d2d_amd.build`')
+    lib = C.CDLL(str(GRAPH_PATH))
+    for name, (res, args) in GRAPH_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    _graph = lib
+    return lib
+
+
+def _graph_call(which: str, rc: int) -> None:
+    if rc != 0:
+        raise NativeError(rc, load_graph_library().d2d_graph_last_error().decode(errors='replace'))
+    graph_launches[which] += 1
+
+
+def graph_coupling(pos_x_ptr: int, pos_y_ptr: int, link_tx_ptr: int, link_rx_ptr: int, cols_ptr: int, law: int, pow_k: int,
+                   n_envs: int, n_dev: int, n_links: int, out_ptr: int, stream_ptr: int = 0) -> None:
+    """d2d_graph_coupling: coupling_db [n_envs, n_links (receiver i), n_links (transmitter j)] into out (device pointers)."""
+    _graph_call('coupling', load_graph_library().d2d_graph_coupling(
+        _P(pos_x_ptr or None), _P(pos_y_ptr or None), _P(link_tx_ptr or None), _P(link_rx_ptr or None), _P(cols_ptr or None), law,
+        pow_k, n_envs, n_dev, n_links, _P(out_ptr or None), _P(stream_ptr or None)))
+
+
+def graph_neighbors(pos_x_ptr: int, pos_y_ptr: int, link_tx_ptr: int, link_rx_ptr: int, cols_ptr: int, law: int, pow_k: int,
+                    n_envs: int, n_dev: int, n_links: int, k: int, env_mask_ptr: int, idx_ptr: int, coupling_ptr: int,
+                    stream_ptr: int = 0) -> None:
+    """d2d_graph_neighbors: every receiver's k strongest interferers, idx / coupling_db [n_envs, n_links (receiver i), k] (device
+    pointers; env_mask_ptr 0: every env, else uint8 [n_envs] and the envs whose byte is 0 keep their rows)."""
+    _graph_call('neighbors', load_graph_library().d2d_graph_neighbors(
+        _P(pos_x_ptr or None), _P(pos_y_ptr or None), _P(link_tx_ptr or None), _P(link_rx_ptr or None), _P(cols_ptr or None), law,
+        pow_k, n_envs, n_dev, n_links, k, _P(env_mask_ptr or None), _P(idx_ptr or None), _P(coupling_ptr or None),
+        _P(stream_ptr or None)))
+
+
+def graph_neighbor_obs(idx_ptr: int, coupling_ptr: int, rb_ptr: int, pwr_ptr: int, sinr_ptr: int, snr_ptr: int, n_envs: int,
+                       n_links: int, k: int, out_ptr: int, stream_ptr: int = 0) -> None:
+    """d2d_graph_neighbor_obs: the per-step gather, out [n_envs, n_links (receiver i), k + 1, 4] (device pointers)."""
+    _graph_call('neighbor_obs', load_graph_library().d2d_graph_neighbor_obs(
+        _P(idx_ptr or None), _P(coupling_ptr or None), _P(rb_ptr or None), _P(pwr_ptr or None), _P(sinr_ptr or None),
+        _P(snr_ptr or None), n_envs, n_links, k, _P(out_ptr or None), _P(stream_ptr or None)))
 
 
 def _check(rc: int) -> None:

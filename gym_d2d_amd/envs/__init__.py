@@ -2,7 +2,7 @@
 `gym_d2d_amd.envs.env_config` without dragging in d2d_env (which imports the simulator) - the reference has exactly
 this cycle and fails on `import gym_d2d.simulator` first."""
 
-__all__ = ['D2DEnv', 'VecD2DEnv', 'RbSensingObsFunction']
+__all__ = ['D2DEnv', 'VecD2DEnv', 'RbSensingObsFunction', 'NeighborObsFunction']
 
 
 def __getattr__(name):
@@ -15,4 +15,7 @@ def __getattr__(name):
     if name == 'RbSensingObsFunction':
         from .obs_fn import RbSensingObsFunction
         return RbSensingObsFunction
+    if name == 'NeighborObsFunction':
+        from .obs_fn import NeighborObsFunction
+        return NeighborObsFunction
     raise AttributeError(name)

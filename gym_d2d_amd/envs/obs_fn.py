@@ -53,9 +53,13 @@ class ArrayObsFunction(ABC):
     """Batched plugin: compute(view) -> [B, N, width] array/tensor.  `view` has pos_x/pos_y [B,D], rb, pwr, sinr_db,
     snr_db, rate_bps, capacity_mbps [B,N], table [B,N,6], link_tx/link_rx/link_type [N].  A subclass that sets
     `needs_rb_sensing = True` also gets rb_sinr_db [B,N,R]: VecD2DEnv runs the sensing kernel (VecD2DEnv.sense) after every step
-    for it; without the attribute nothing is launched or allocated."""
+    for it; without the attribute nothing is launched or allocated.  A subclass that sets `needs_neighbors = k` (1 .. min(N - 1, 64))
+    also gets neighbor_idx int32 [B,N,k] and neighbor_coupling_db float32 [B,N,k], every link's k strongest interferers
+    (VecD2DEnv.neighbors: receiver-major, row [b, i] belongs to the RECEIVING link i, strongest first): selected at reset() and for
+    the envs an autoreset step reset, never per step; without the attribute nothing is built, allocated or launched."""
     native_mode = _native.OBS_TABLE
     needs_rb_sensing = False
+    needs_neighbors = 0
 
     @abstractmethod
     def get_obs_space(self, env_config) -> Space:
@@ -105,3 +109,26 @@ class RbSensingObsFunction(ArrayObsFunction):
 
     def compute(self, view):
         return view.rb_sinr_db
+
+
+class NeighborObsFunction(ArrayObsFunction):
+    """Each agent observes its own link and its k strongest interferers - the interference graph, width 4 (k + 1) whatever N is:
+    [B, N, 4 (k + 1)] float32 = own (rb, pwr_dBm, sinr_dB, snr_dB), then for each neighbour in rank order (coupling_dB, rb_j, pwr_dBm_j,
+    sinr_dB_j).  The neighbours of link i are the k links j != i whose transmitters couple most strongly into link i's RECEIVER
+    (VecD2DEnv.neighbors(k): receiver-major [b, i, m]; the path-loss tables elsewhere are [b, j, i]), strongest first, ties in
+    ascending j.  The lists depend on positions only: the env selects them at reset() and, under autoreset=True, for the envs a step
+    reset; every step is one gather kernel (csrc/d2d_graph.hip).  A subclass sets another `k` (1 .. min(N - 1, 64)).  The tensor is
+    the env's own block, rewritten by every step (clone it to keep a step's values)."""
+    native_mode = _native.OBS_NONE
+    native_neighbor_obs = True          # the env runs d2d_graph_neighbor_obs and hands the block over as view.neighbor_obs
+    k = 8
+
+    @property
+    def needs_neighbors(self) -> int:
+        return self.k
+
+    def get_obs_space(self, env_config) -> Space:
+        return Box(low=-np.inf, high=np.inf, shape=(4 * (self.k + 1),))
+
+    def compute(self, view):
+        return view.neighbor_obs

@@ -22,7 +22,7 @@ from typing import Optional
 
 import numpy as np
 
-from .. import _native, sensing
+from .. import _native, graph, sensing
 from ..path_loss_table import NATIVE, PER_STEP
 from ..simulator import BASE_STATION_ID, Simulator
 from ..traffic_model import DownlinkTrafficModel
@@ -180,6 +180,13 @@ class VecD2DEnv:
         self._senses = bool(getattr(self.obs_fn, 'needs_rb_sensing', False))
         if self._senses:
             self._rb_sensor()                      # refusals surface here, not inside the first step
+        # the neighbour graph (coupling(), neighbors()): likewise nothing unless one of them is called or the obs function asks
+        self._graph = None
+        self._neighbors = None                     # (idx, coupling_db) of the obs function's k: selected at reset, constant between
+        k = getattr(self.obs_fn, 'needs_neighbors', 0)
+        self._neighbors_k = graph.check_k(k, self.num_links) if k is not False and k != 0 else 0
+        if self._neighbors_k:
+            self._neighbor_graph()
 
     def _setup_autoreset(self) -> None:
         """Refuse what a device-side per-env reset cannot serve, then allocate the per-env bookkeeping: pending / episode are bound
@@ -337,6 +344,8 @@ class VecD2DEnv:
         self.simulator.check_flags()
         if self._placement_trials > 1 and self.placement is None:
             self._choose_obs_placement(self._placement_trials)
+        if self._neighbors_k:
+            self._select_neighbors()
         return self._observe(self._view())
 
     def _choose_obs_placement(self, trials: int, warm_ms: float = 15.0, steps: int = 256) -> None:
@@ -470,6 +479,8 @@ class VecD2DEnv:
         _native.episode_advance(t['pending'].data_ptr(), t['episode'].data_ptr(), t['elapsed'].data_ptr(), t['done'].data_ptr(),
                                 t['reset'].data_ptr(), reward.data_ptr() if native else 0,
                                 1 if self.reward_per_env else self.num_links, self.num_envs, EPISODE_LENGTH, stream)
+        if self._neighbors_k:
+            self._select_neighbors(t['reset'])                # the envs this step reset stand at new positions
         obs = self._observe(view)
         if native:
             rewards = view.reward
@@ -527,10 +538,73 @@ class VecD2DEnv:
             return sensor.sense_torch(self._t, sensing.WHAT[what], out, self._stream_ptr)
         return sensor.sense_numpy(sensing.WHAT[what], out)
 
+    # ------------------------------------------------------------------ the neighbour graph
+    def _neighbor_graph(self):
+        if self._graph is None:
+            why = graph.refusal(self.simulator, self.export_actions)
+            if why:
+                raise ValueError(why)
+            self._graph = graph.NeighborGraph(self.simulator, self.num_links, torch if self.use_torch else None,
+                                              self.device if self.use_torch else None)
+        return self._graph
+
+    def coupling(self, out=None):
+        """The dense interference graph, float32 [B, N, N]: coupling[b, i, j] = eirp_off_db[tx_j] - PL(tx_j -> rx_i), the dBm link
+        i's receiver gets per 0 dBm of link j's tx power, so that the step's interference on link i is the sum over j != i with
+        rb_j == rb_i of lin(pwr_j + coupling[b, i, j]).  INDEX ORDER: [b, i, j] is receiver-major - i receives, j transmits, one
+        agent's row contiguous; the path-loss tables elsewhere in the project are [b, j, i].  The diagonal holds the same formula
+        (own transmitter into own receiver, no receiver gains).  Positions and the model only: constant between resets.  One kernel
+        launch (csrc/d2d_graph.hip); 4 B N^2 bytes - 4.3 GB at 4096 x 512.
+
+        torch path: enqueued on torch's current stream, nothing is synchronised; ONE tensor the env owns and rewrites on every call,
+        or `out` (contiguous float32 [B, N, N] on the env's device).  NumPy path: a fresh array, or `out`.  Valid after reset() and
+        after every step(), autoreset steps included.  ValueError for what sense() refuses too: export_actions=False,
+        ShadowingPathLoss, every table route, pinned device_config coordinates float32 cannot hold."""
+        g = self._neighbor_graph()
+        if self.use_torch:
+            self._follow_torch_stream()
+            return g.coupling_torch(self._t, out, self._stream_ptr)
+        return g.coupling_numpy(out)
+
+    def neighbors(self, k: int, out=None):
+        """Every link's k strongest interferers: (idx int32 [B, N, k], coupling_db float32 [B, N, k]).  Row [b, i] lists the k links
+        j != i with the largest coupling()[b, i, j] - i is the RECEIVING link, receiver-major as coupling() ([b, i, j]; the path-loss
+        tables elsewhere are [b, j, i]) - strongest first, equal values (a downlink base station transmits every CUE link) in
+        ascending j; coupling_db[b, i, m] is coupling()[b, i, idx[b, i, m]] bit for bit.  1 <= k <= min(N - 1, 64).  Positions and
+        the model only, never actions: constant between resets.  One kernel launch, no [B, N, N] cube.
+
+        torch path: on torch's current stream, nothing is synchronised; the pair of tensors the env owns for this k, rewritten by
+        every call, or `out` = (idx, coupling_db), contiguous int32 / float32 [B, N, k] on the env's device.  NumPy path: fresh
+        arrays, or `out`.  Valid and refused as coupling() is."""
+        k = graph.check_k(k, self.num_links)
+        g = self._neighbor_graph()
+        if self.use_torch:
+            self._follow_torch_stream()
+            return g.neighbors_torch(self._t, k, out, self._stream_ptr)
+        return g.neighbors_numpy(k, out)
+
+    def _select_neighbors(self, env_mask=None) -> None:
+        """The obs function's neighbour lists: all envs (reset()), or the envs env_mask marks (bool [B]: the envs an autoreset step
+        reset; the others keep their rows)."""
+        g, k = self._graph, self._neighbors_k
+        if self.use_torch:
+            self._neighbors = g.neighbors_torch(self._t, k, None, self._stream_ptr, env_mask)
+        else:
+            self._neighbors = g.neighbors_numpy(k, None)
+
     def _observe(self, view):
+        extra = {}
         if self._senses:
+            extra['rb_sinr_db'] = self.sense('sinr_db')
+        if self._neighbors_k:
+            idx, cdb = self._neighbors
+            extra.update(neighbor_idx=idx, neighbor_coupling_db=cdb)
+            if getattr(self.obs_fn, 'native_neighbor_obs', False):
+                g, k = self._graph, self._neighbors_k
+                extra['neighbor_obs'] = g.obs_torch(self._t, k, idx, cdb, self._stream_ptr) if self.use_torch else g.obs_numpy(k)
+        if extra:
             # a namespace of its own: the cached view stays what every other consumer sees
-            view = SimpleNamespace(**vars(view), rb_sinr_db=self.sense('sinr_db'))
+            view = SimpleNamespace(**vars(view), **extra)
         obs = self.obs_fn.compute(view) if self._array_obs else view.obs
         if self._obs64 and not self._native_obs64 and not isinstance(obs, tuple):   # the reference's dtype (obs_fn.py:51) for a custom array obs: cast here
             obs = obs.double() if self.use_torch else np.asarray(obs, dtype=np.float64)
@@ -563,4 +637,7 @@ class VecD2DEnv:
         if self._sensor is not None:
             self._sensor.close()
             self._sensor = None
+        if self._graph is not None:
+            self._graph.close()
+            self._graph = None
         self.simulator.handle.close()

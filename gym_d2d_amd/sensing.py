@@ -47,23 +47,38 @@ def fold_columns(budget: dict, law: dict, link_tx: np.ndarray) -> Tuple[np.ndarr
     return cols, _native.SENSE_LAW_POWER, 0
 
 
-def refusal(sim, export_actions: bool) -> Optional[str]:
-    """Why this env cannot be sensed (None: it can).  Each text names the route or the switch."""
+def unserved(sim, export_actions: bool) -> Optional[Tuple[str, str]]:
+    """What about this env the stateless pair kernels (sensing, the neighbour graph) cannot serve, as (kind, detail), or None:
+    'export_actions', 'route' (detail: the route's name), 'shadowing', 'pinned'.  The one predicate behind every refusal text."""
     if not export_actions:
-        return ('sense() reads the decoded (rb, tx power) planes, which export_actions=False does not write: build the env with '
-                'export_actions=True')
+        return 'export_actions', ''
     route = sim.path_loss_table.route
     if route != NATIVE:
-        return (f"sense() does not serve the '{route}' path-loss route (a table, not a law the sensing kernel can evaluate for the "
-                'pairs no step reads); it serves the native power-law models')
+        return 'route', route
     if sim.path_loss_table.law.get('shadowing'):
-        return ('sense() does not serve ShadowingPathLoss: a fresh draw per evaluation has no counterfactual (what another RB '
-                'would have given is another draw)')
+        return 'shadowing', ''
     mask, xy = sim.fixed_positions()
     if mask.any() and (xy != xy.astype(np.float32)).any():
-        return ('sense() does not serve pinned device_config coordinates that float32 cannot hold: their low parts live inside '
-                'the handle (float64 positions)')
+        return 'pinned', ''
     return None
+
+
+def refusal(sim, export_actions: bool) -> Optional[str]:
+    """Why this env cannot be sensed (None: it can).  Each text names the route or the switch."""
+    why = unserved(sim, export_actions)
+    if why is None:
+        return None
+    kind, route = why
+    return {
+        'export_actions': 'sense() reads the decoded (rb, tx power) planes, which export_actions=False does not write: build the env '
+                          'with export_actions=True',
+        'route': f"sense() does not serve the '{route}' path-loss route (a table, not a law the sensing kernel can evaluate for the "
+                 'pairs no step reads); it serves the native power-law models',
+        'shadowing': 'sense() does not serve ShadowingPathLoss: a fresh draw per evaluation has no counterfactual (what another RB '
+                     'would have given is another draw)',
+        'pinned': 'sense() does not serve pinned device_config coordinates that float32 cannot hold: their low parts live inside '
+                  'the handle (float64 positions)',
+    }[kind]
 
 
 class _HipMemory:
