@@ -1,5 +1,5 @@
 """ctypes binding of libd2d_hip.so (include/d2d_hip.h), libd2d_plugin.so (include/d2d_plugin.h), libd2d_episode.so
-(include/d2d_episode.h), libd2d_sense.so (include/d2d_sense.h) and libd2d_graph.so (include/d2d_graph.h).  There is no CPU fallback: if a library or a gfx950 GPU is missing, the calls below raise."""
+(include/d2d_episode.h), libd2d_sense.so (include/d2d_sense.h), libd2d_graph.so (include/d2d_graph.h) and libd2d_marginal.so (include/d2d_marginal.h).  There is no CPU fallback: if a library or a gfx950 GPU is missing, the calls below raise."""
 from __future__ import annotations
 
 import ctypes as C
@@ -13,6 +13,7 @@ PLUGIN_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_plugin.so'
 EPISODE_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_episode.so'
 SENSE_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_sense.so'
 GRAPH_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_graph.so'
+MARGINAL_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_marginal.so'
 ABI_VERSION = 7
 MAX_LINKS = 2048
 
@@ -49,6 +50,9 @@ SENSE_LAW_INV_SQUARE, SENSE_LAW_POWER, SENSE_LAW_POW_K = 0, 1, 2
 SENSE_MAX_RBS = 8192
 # d2d_graph_neighbors's largest k (include/d2d_graph.h)
 GRAPH_MAX_K = 64
+# d2d_marginal_capacity's law / limits (include/d2d_marginal.h): the sensing kernel's
+MARGINAL_LAW_INV_SQUARE, MARGINAL_LAW_POWER, MARGINAL_LAW_POW_K = 0, 1, 2
+MARGINAL_MAX_RBS = 8192
 
 BUFFER_DTYPES = {BUF_ACTIONS: np.int32, BUF_RB: np.int32, BUF_PWR: np.int32, BUF_ENV_FLAGS: np.int32, BUF_RESET_PENDING: np.int32,
                  BUF_EPISODE: np.uint32}
@@ -156,6 +160,12 @@ GRAPH_SIGNATURES = {
     'd2d_graph_last_error': (C.c_char_p, []),
 }
 
+# every symbol include/d2d_marginal.h declares
+MARGINAL_SIGNATURES = {
+    'd2d_marginal_capacity': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, C.c_int64, _I, _I, _I, _P, _P, _P]),
+    'd2d_marginal_last_error': (C.c_char_p, []),
+}
+
 _lib: Optional[C.CDLL] = None
 _plugin: Optional[C.CDLL] = None
 _episode: Optional[C.CDLL] = None
@@ -163,6 +173,8 @@ _sense: Optional[C.CDLL] = None
 sense_launches = 0                  # d2d_sense_rb calls made through sense_rb() in this process
 _graph: Optional[C.CDLL] = None
 graph_launches = {'coupling': 0, 'neighbors': 0, 'neighbor_obs': 0}     # launches made through the graph_*() wrappers in this process
+_marginal: Optional[C.CDLL] = None
+marginal_launches = 0               # d2d_marginal_capacity calls made through marginal_capacity() in this process
 
 
 def load_library() -> C.CDLL:
@@ -323,6 +335,37 @@ def graph_neighbor_obs(idx_ptr: int, coupling_ptr: int, rb_ptr: int, pwr_ptr: in
     _graph_call('neighbor_obs', load_graph_library().d2d_graph_neighbor_obs(
         _P(idx_ptr or None), _P(coupling_ptr or None), _P(rb_ptr or None), _P(pwr_ptr or None), _P(sinr_ptr or None),
         _P(snr_ptr or None), n_envs, n_links, k, _P(out_ptr or None), _P(stream_ptr or None)))
+
+
+def load_marginal_library() -> C.CDLL:
+    """dlopen libd2d_marginal.so and type its entry points.  Raises if it has not been built."""
+    global _marginal
+    if _marginal is not None:
+        return _marginal
+    if not MARGINAL_PATH.exists():
+        raise ImportError(f'{MARGINAL_PATH} is missing - build it with `python -m gym_d2d_amd.build`')
+    lib = C.CDLL(str(MARGINAL_PATH))
+    for name, (res, args) in MARGINAL_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    _marginal = lib
+    return lib
+
+
+def marginal_capacity(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, link_tx_ptr: int, link_rx_ptr: int, cols_ptr: int,
+                      cap_cols_ptr: int, law: int, pow_k: int, n_envs: int, n_dev: int, n_links: int, n_rbs: int, harm_ptr: int,
+                      diff_ptr: int, stream_ptr: int = 0) -> None:
+    """d2d_marginal_capacity: every link's harm and difference reward (Mbps) into two planes [n_envs, n_links] (device pointers)."""
+    global marginal_launches
+    lib = load_marginal_library()
+    rc = lib.d2d_marginal_capacity(_P(pos_x_ptr or None), _P(pos_y_ptr or None), _P(rb_ptr or None), _P(pwr_ptr or None),
+                                   _P(link_tx_ptr or None), _P(link_rx_ptr or None), _P(cols_ptr or None), _P(cap_cols_ptr or None),
+                                   law, pow_k, n_envs, n_dev, n_links, n_rbs, _P(harm_ptr or None), _P(diff_ptr or None),
+                                   _P(stream_ptr or None))
+    if rc != 0:
+        raise NativeError(rc, lib.d2d_marginal_last_error().decode(errors='replace'))
+    marginal_launches += 1
 
 
 def _check(rc: int) -> None:

@@ -2,7 +2,7 @@
 `gym_d2d_amd.envs.env_config` without dragging in d2d_env (which imports the simulator) - the reference has exactly
 this cycle and fails on `import gym_d2d.simulator` first."""
 
-__all__ = ['D2DEnv', 'VecD2DEnv', 'RbSensingObsFunction', 'NeighborObsFunction']
+__all__ = ['D2DEnv', 'VecD2DEnv', 'RbSensingObsFunction', 'NeighborObsFunction', 'DifferenceRewardFunction']
 
 
 def __getattr__(name):
@@ -18,4 +18,7 @@ def __getattr__(name):
     if name == 'NeighborObsFunction':
         from .obs_fn import NeighborObsFunction
         return NeighborObsFunction
+    if name == 'DifferenceRewardFunction':
+        from .reward_fn import DifferenceRewardFunction
+        return DifferenceRewardFunction
     raise AttributeError(name)

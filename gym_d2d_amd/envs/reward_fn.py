@@ -1,6 +1,7 @@
 """Reward plugins (mirrors gym_d2d/envs/reward_fn.py).  The three built-ins are evaluated inside the HIP step
 kernel (csrc/d2d_step.hip, pass 3); `native_id` / `native_param` select the branch.  Calling a built-in with a
-NativeState just re-keys the kernel's per-agent output.  A user subclass that overrides __call__ runs as Python."""
+NativeState just re-keys the kernel's per-agent output.  A user subclass that overrides __call__ runs as Python.
+DifferenceRewardFunction is the array-native one: VecD2DEnv hands it the planes of csrc/d2d_marginal.hip."""
 from __future__ import annotations
 
 from abc import ABC, abstractmethod
@@ -72,3 +73,18 @@ class CueSinrShannonRewardFunction(RewardFunction):
 
     def __call__(self, actions, state):
         return self._from_kernel(actions, state)
+
+
+class DifferenceRewardFunction(RewardFunction):
+    """Difference reward D_i = G(a) - G(a without link i), G the total capacity in Mbps: link i's own capacity minus the capacity
+    its transmitter costs the other links of its RB (csrc/d2d_marginal.hip).  VecD2DEnv only: `needs_marginal` asks the env for
+    view.difference_mbps / view.harm_mbps [B, N], one extra kernel launch per step; it is not one of the step kernel's rewards."""
+    native_id = _native.REWARD_NONE
+    needs_marginal = True
+
+    def compute(self, view):
+        return view.difference_mbps
+
+    def __call__(self, actions, state):
+        raise RuntimeError('DifferenceRewardFunction is computed from the batched planes of VecD2DEnv (marginal_capacity()); the '
+                           'single-env dict D2DEnv does not serve it')

@@ -22,7 +22,7 @@ from typing import Optional
 
 import numpy as np
 
-from .. import _native, graph, sensing
+from .. import _native, graph, marginal, sensing
 from ..path_loss_table import NATIVE, PER_STEP
 from ..simulator import BASE_STATION_ID, Simulator
 from ..traffic_model import DownlinkTrafficModel
@@ -187,6 +187,12 @@ class VecD2DEnv:
         self._neighbors_k = graph.check_k(k, self.num_links) if k is not False and k != 0 else 0
         if self._neighbors_k:
             self._neighbor_graph()
+        # difference rewards (marginal_capacity()): likewise nothing unless it is called or the reward / obs function asks
+        self._marginal = None
+        self._obs_marginal = bool(getattr(self.obs_fn, 'needs_marginal', False)) and self._array_obs
+        self._wants_marginal = self._obs_marginal or bool(getattr(self.reward_fn, 'needs_marginal', False))
+        if self._wants_marginal:
+            self._marginal_kernel()                # refusals surface here, not inside the first step
 
     def _setup_autoreset(self) -> None:
         """Refuse what a device-side per-env reset cannot serve, then allocate the per-env bookkeeping: pending / episode are bound
@@ -346,7 +352,8 @@ class VecD2DEnv:
             self._choose_obs_placement(self._placement_trials)
         if self._neighbors_k:
             self._select_neighbors()
-        return self._observe(self._view())
+        view = self._view()
+        return self._observe(self._with_marginal(view) if self._obs_marginal else view)
 
     def _choose_obs_placement(self, trials: int, warm_ms: float = 15.0, steps: int = 256) -> None:
         """Time the step on up to `trials` candidate blocks for the dominant output (all held until the choice, hence distinct
@@ -444,6 +451,8 @@ class VecD2DEnv:
             sim.step_arrays(src)
         self.num_steps += 1
         view = self._view()
+        if self._wants_marginal:
+            view = self._with_marginal(view)
         obs = self._observe(view)
         rewards = view.reward if self._native_reward else self.reward_fn.compute(view)
         done = self.num_steps >= EPISODE_LENGTH
@@ -481,6 +490,8 @@ class VecD2DEnv:
                                 1 if self.reward_per_env else self.num_links, self.num_envs, EPISODE_LENGTH, stream)
         if self._neighbors_k:
             self._select_neighbors(t['reset'])                # the envs this step reset stand at new positions
+        if self._wants_marginal:
+            view = self._with_marginal(view)                  # after the step: the envs it reset at their new positions and actions
         obs = self._observe(view)
         if native:
             rewards = view.reward
@@ -592,6 +603,43 @@ class VecD2DEnv:
         else:
             self._neighbors = g.neighbors_numpy(k, None)
 
+    # ------------------------------------------------------------------ difference rewards
+    def _marginal_kernel(self):
+        if self._marginal is None:
+            why = marginal.refusal(self.simulator, self.export_actions)
+            if why:
+                raise ValueError(why)
+            self._marginal = marginal.MarginalCapacity(self.simulator, self.num_links, torch if self.use_torch else None,
+                                                       self.device if self.use_torch else None)
+        return self._marginal
+
+    def marginal_capacity(self, out=None):
+        """What every link costs the others, with everything as the last step left it: (difference_mbps, harm_mbps), float32 [B, N].
+
+        harm_mbps[b, i] is the capacity the OTHER links of link i's RB would gain if link i alone went off the air - the sum over
+        them of cap_j without i's transmitter minus cap_j with it, the `sinr > rx_sensitivity` threshold of the step included -
+        and difference_mbps[b, i] = capacity_mbps[b, i] - harm_mbps[b, i] is the difference reward G(a) - G(a without link i) of
+        the total capacity G.  harm >= 0; a link alone on its RB has harm == 0.0 and difference == capacity exactly.  One kernel
+        launch (csrc/d2d_marginal.hip), no [B, N, N] cube.  Valid after reset() and after every step(), autoreset steps included:
+        an env that was reset inside the step is evaluated at its new positions and its reset's random actions.
+
+        torch path: enqueued on torch's current stream, nothing is synchronised; the pair of tensors the env owns, rewritten by
+        every call (clone them to keep them), or `out` = (difference_mbps, harm_mbps), two contiguous float32 [B, N] tensors on the
+        env's device.  NumPy path: fresh arrays, or `out`.
+
+        Serves what sense() serves; ValueError for export_actions=False, ShadowingPathLoss, every table route, pinned device_config
+        coordinates float32 cannot hold."""
+        m = self._marginal_kernel()
+        if self.use_torch:
+            self._follow_torch_stream()
+            return m.torch_planes(self._t, out, self._stream_ptr)
+        return m.numpy_planes(out)
+
+    def _with_marginal(self, view):
+        """The view plus difference_mbps / harm_mbps, as a namespace of its own: the cached view stays what every other consumer sees."""
+        diff, harm = self.marginal_capacity()
+        return SimpleNamespace(**vars(view), difference_mbps=diff, harm_mbps=harm)
+
     def _observe(self, view):
         extra = {}
         if self._senses:
@@ -640,4 +688,7 @@ class VecD2DEnv:
         if self._graph is not None:
             self._graph.close()
             self._graph = None
+        if self._marginal is not None:
+            self._marginal.close()
+            self._marginal = None
         self.simulator.handle.close()
