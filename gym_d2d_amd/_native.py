@@ -1,5 +1,6 @@
 """ctypes binding of libd2d_hip.so (include/d2d_hip.h), libd2d_plugin.so (include/d2d_plugin.h), libd2d_episode.so
-(include/d2d_episode.h), libd2d_sense.so (include/d2d_sense.h), libd2d_graph.so (include/d2d_graph.h) and libd2d_marginal.so (include/d2d_marginal.h).  There is no CPU fallback: if a library or a gfx950 GPU is missing, the calls below raise."""
+(include/d2d_episode.h), libd2d_sense.so (include/d2d_sense.h), libd2d_graph.so (include/d2d_graph.h), libd2d_marginal.so (include/d2d_marginal.h) and libd2d_mobility.so
+(include/d2d_mobility.h).  There is no CPU fallback: if a library or a gfx950 GPU is missing, the calls below raise."""
 from __future__ import annotations
 
 import ctypes as C
@@ -14,6 +15,7 @@ EPISODE_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_episode.so'
 SENSE_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_sense.so'
 GRAPH_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_graph.so'
 MARGINAL_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_marginal.so'
+MOBILITY_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_mobility.so'
 ABI_VERSION = 7
 MAX_LINKS = 2048
 
@@ -166,6 +168,13 @@ MARGINAL_SIGNATURES = {
     'd2d_marginal_last_error': (C.c_char_p, []),
 }
 
+# every symbol include/d2d_mobility.h declares
+MOBILITY_SIGNATURES = {
+    'd2d_mobility_move': (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, _I, _I, C.c_uint64, C.c_uint64, C.c_float, C.c_float, C.c_float,
+                                    C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P]),
+    'd2d_mobility_last_error': (C.c_char_p, []),
+}
+
 _lib: Optional[C.CDLL] = None
 _plugin: Optional[C.CDLL] = None
 _episode: Optional[C.CDLL] = None
@@ -175,6 +184,8 @@ _graph: Optional[C.CDLL] = None
 graph_launches = {'coupling': 0, 'neighbors': 0, 'neighbor_obs': 0}     # launches made through the graph_*() wrappers in this process
 _marginal: Optional[C.CDLL] = None
 marginal_launches = 0               # d2d_marginal_capacity calls made through marginal_capacity() in this process
+_mobility: Optional[C.CDLL] = None
+mobility_launches = 0               # d2d_mobility_move calls made through mobility_move() in this process
 
 
 def load_library() -> C.CDLL:
@@ -366,6 +377,40 @@ def marginal_capacity(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int,
     if rc != 0:
         raise NativeError(rc, lib.d2d_marginal_last_error().decode(errors='replace'))
     marginal_launches += 1
+
+
+def load_mobility_library() -> C.CDLL:
+    """dlopen libd2d_mobility.so and type its entry points.  Raises if it has not been built."""
+    global _mobility
+    if _mobility is not None:
+        return _mobility
+    if not MOBILITY_PATH.exists():
+        raise ImportError(f'{MOBILITY_PATH} is missing - build it with `python -m gym_d2d_amd.build`')
+    lib = C.CDLL(str(MOBILITY_PATH))
+    for name, (res, args) in MOBILITY_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    _mobility = lib
+    return lib
+
+
+def mobility_move(pos_x_ptr: int, pos_y_ptr: int, vel_x_ptr: int, vel_y_ptr: int, fixed_mask_ptr: int, n_envs: int, n_cues: int,
+                  n_due_pairs: int, first_env: int, seed: int, memory: float, noise_scale: float, speed_std: float, dt_s: float,
+                  cell_radius_m: float, d2d_radius_m: float, step: int = 0, episode: int = 0, elapsed_ptr: int = 0, start_ptr: int = 0,
+                  episode_ptr: int = 0, reset_ptr: int = 0, stream_ptr: int = 0) -> None:
+    """d2d_mobility_move: one Gauss-Markov move of the position / velocity planes [n_envs, n_dev] in place (device pointers), or the
+    start-of-episode velocities (step 0); reset_ptr != 0: the per-env clock of the four [n_envs] arrays."""
+    global mobility_launches
+    lib = load_mobility_library()
+    rc = lib.d2d_mobility_move(_P(pos_x_ptr or None), _P(pos_y_ptr or None), _P(vel_x_ptr or None), _P(vel_y_ptr or None),
+                               _P(fixed_mask_ptr or None), n_envs, n_cues, n_due_pairs, C.c_uint64(first_env),
+                               C.c_uint64(seed & (2 ** 64 - 1)), memory, noise_scale, speed_std, dt_s, cell_radius_m, d2d_radius_m,
+                               step & 0xFFFFFFFF, episode & 0xFFFFFFFF, _P(elapsed_ptr or None), _P(start_ptr or None),
+                               _P(episode_ptr or None), _P(reset_ptr or None), _P(stream_ptr or None))
+    if rc != 0:
+        raise NativeError(rc, lib.d2d_mobility_last_error().decode(errors='replace'))
+    mobility_launches += 1
 
 
 def _check(rc: int) -> None:

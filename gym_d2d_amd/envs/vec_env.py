@@ -23,7 +23,8 @@ from typing import Optional
 import numpy as np
 
 from .. import _native, graph, marginal, sensing
-from ..path_loss_table import NATIVE, PER_STEP
+from .. import mobility as mobility_mod
+from ..path_loss_table import PER_STEP, positions_move_unserved
 from ..simulator import BASE_STATION_ID, Simulator
 from ..traffic_model import DownlinkTrafficModel
 from . import _rng
@@ -44,7 +45,8 @@ class VecD2DEnv:
     def __init__(self, env_config: Optional[dict] = None, num_envs: Optional[int] = None, *,
                  cue_actions: str = 'agent', use_torch: Optional[bool] = None, first_env: int = 0,
                  export_actions: bool = True, reward_per_env: bool = False, placement_trials: int = 0,
-                 placement_budget_bytes: int = 1 << 30, autoreset: bool = False) -> None:
+                 placement_budget_bytes: int = 1 << 30, autoreset: bool = False, mobility=None,
+                 neighbor_refresh: int = 1) -> None:
         """cue_actions: 'agent' - step() takes actions for CUEs and DUEs [B, C+P] (reference behaviour);
         'traffic' - CUE links follow the env's traffic model (round-robin RB at max power,
         traffic_model.py:15-22): their (rb, pwr) are constants of the kernel's link records
@@ -86,6 +88,19 @@ class VecD2DEnv:
         the first episodes; request_reset(mask) resets chosen envs at the next step.  Needs the torch path and a path-loss model
         the kernels evaluate per step (the native laws, ShadowingPathLoss, a per-step ArrayPathLoss): a table evaluated once per
         reset, or pinned device_config coordinates float32 cannot hold, would need the host between steps (ValueError).
+
+        mobility: a gym_d2d_amd.mobility.GaussMarkovMobility - devices move before every step (csrc/d2d_mobility.hip, one launch):
+        reset() draws start-of-episode velocities behind the sampler (its positions, obs and planes are those of a mobility-less env
+        with the same seed, bit for bit), step() moves every device, tells the handle (d2d_positions_changed) and then steps, so the
+        step, the obs table's columns 0 - 3, link_positions(), sense(), coupling() and marginal_capacity() all see the new positions.
+        Under autoreset=True an env that is reset inside a step is not moved in that step and gets its new episode's velocities.  The
+        draws are keyed by (global env index, episode, step in the episode, device, axis): sharding and autoreset reproduce the
+        lockstep single-GPU trajectories.  velocities() returns the planes; the view carries them as vel_x / vel_y.  None (default):
+        nothing is loaded, allocated or launched.  Needs the torch path and what autoreset needs of the path-loss model (ValueError).
+        neighbor_refresh: with mobility, an obs function's neighbour lists (needs_neighbors) are selected again after the move of
+        every neighbor_refresh-th step() call since reset() (default 1: every step; between refreshes the lists are the last
+        refresh's, and under autoreset the envs a step reset still get theirs at once).
+        One d2d_graph_neighbors launch per refresh - profiles/mobility_cost.jsonl has its cost.
 
         env_config['obs_dtype'] = 'float64' returns observations in the reference's dtype (obs_fn.py:51 builds float64
         arrays); the default float32 is the kernels' own block, zero copy.
@@ -155,6 +170,12 @@ class VecD2DEnv:
             h.set_reward_layout(_native.REWARD_PER_ENV)
         self._array_obs = isinstance(self.obs_fn, ArrayObsFunction)
         self.use_torch = (torch is not None and torch.cuda.is_available()) if use_torch is None else use_torch
+        if mobility is not None:                       # refusals surface here, before anything is allocated
+            if not isinstance(mobility, mobility_mod.GaussMarkovMobility):
+                raise TypeError(f'mobility must be a GaussMarkovMobility or None, got {type(mobility).__name__}')
+            why = mobility_mod.refusal(sim, self.use_torch)
+            if why:
+                raise ValueError(why)
         self._t = {}
         if self.use_torch:
             self._bind_torch_buffers()
@@ -175,6 +196,19 @@ class VecD2DEnv:
         self.autoreset = bool(autoreset)
         if self.autoreset:
             self._setup_autoreset()
+        # device mobility: nothing is loaded, allocated or launched unless a model is given
+        self._mobility = None
+        if isinstance(neighbor_refresh, bool) or not isinstance(neighbor_refresh, (int, np.integer)) or neighbor_refresh < 1:
+            raise ValueError(f'neighbor_refresh must be an int >= 1, got {neighbor_refresh!r}')
+        if neighbor_refresh != 1 and mobility is None:
+            raise ValueError('neighbor_refresh needs mobility=: without it the neighbour lists are selected at reset and stay valid '
+                             'until the next one')
+        self._neighbor_refresh = int(neighbor_refresh)
+        if mobility is not None:
+            sim.path_loss_table.device_resets = True           # a per-step ArrayPathLoss gathers the coordinates before every step
+            self._mobility = mobility_mod.Mobility(mobility, sim, torch, self.device, self.first_env, self.autoreset)
+            self._t['vel_x'], self._t['vel_y'] = self._mobility.vel_x, self._mobility.vel_y
+            self._view_cache = None
         # per-RB sensing (sense()): nothing is built, allocated or launched unless sense() is called or the obs function asks
         self._sensor = None
         self._senses = bool(getattr(self.obs_fn, 'needs_rb_sensing', False))
@@ -198,15 +232,14 @@ class VecD2DEnv:
         """Refuse what a device-side per-env reset cannot serve, then allocate the per-env bookkeeping: pending / episode are bound
         into the handle (D2D_BUF_RESET_PENDING / D2D_BUF_EPISODE), elapsed / done / reset belong to libd2d_episode.so's kernels."""
         sim = self.simulator
-        if not self.use_torch:
+        kind, route = positions_move_unserved(sim, self.use_torch) or (None, '')
+        if kind == 'numpy':
             raise ValueError('autoreset=True needs the torch path (use_torch): the per-env bookkeeping lives in device tensors')
-        route = sim.path_loss_table.route
-        if route not in (NATIVE, PER_STEP):
+        if kind == 'route':
             raise ValueError(f"autoreset=True cannot serve the '{route}' path-loss route: its table is evaluated once per reset, "
                              'which a device-side reset inside step() cannot follow without the host (use a per-step ArrayPathLoss '
                              'or a native model)')
-        mask, xy = sim.fixed_positions()
-        if mask.any() and (xy != xy.astype(np.float32)).any():
+        if kind == 'pinned':
             raise ValueError('autoreset=True cannot pin device_config coordinates that float32 cannot hold: they need the host '
                              'upload of a full reset')
         sim.path_loss_table.device_resets = True
@@ -347,6 +380,8 @@ class VecD2DEnv:
                 self._t['elapsed'].zero_()
             else:
                 self._t['elapsed'].copy_(torch.as_tensor(elapsed.astype(np.int32), device=self.device))
+        if self._mobility is not None:                        # behind the sampler; the reset's own step did not see a move
+            self._mobility.start_episode(self._t, self._seed, self._episode - 1, self._stream_ptr)
         self.simulator.check_flags()
         if self._placement_trials > 1 and self.placement is None:
             self._choose_obs_placement(self._placement_trials)
@@ -438,6 +473,8 @@ class VecD2DEnv:
             src = actions if torch.is_tensor(actions) else torch.as_tensor(np.asarray(actions), device=self.device)
             if tuple(src.shape) != (self.num_envs, self.num_agents):
                 raise ValueError(f'actions must be [{self.num_envs},{self.num_agents}], got {tuple(src.shape)}')
+            if self._mobility is not None:
+                self._move_devices()
             sim.prepare_step()                                # a per-step ArrayPathLoss: this step's table
             if src.dtype == torch.int32 and src.is_contiguous() and src.device == self.device:
                 sim.handle.step(src.data_ptr())               # zero copy: the kernel reads the caller's tensor
@@ -450,6 +487,8 @@ class VecD2DEnv:
                 raise ValueError(f'actions must be [{self.num_envs},{self.num_agents}], got {src.shape}')
             sim.step_arrays(src)
         self.num_steps += 1
+        if self._mobility is not None and self._neighbors_k and self.num_steps % self._neighbor_refresh == 0:
+            self._select_neighbors()                          # the lists of the moved positions
         view = self._view()
         if self._wants_marginal:
             view = self._with_marginal(view)
@@ -476,6 +515,8 @@ class VecD2DEnv:
             src = src.to(device=self.device, dtype=torch.int32).contiguous()
         stream = self._stream_ptr
         h.reset_positions(self._seed, _native.EPISODE_PER_ENV)
+        if self._mobility is not None:
+            self._move_devices()                              # the envs that are not pending; the pending ones get new velocities
         sim.prepare_step()                                    # a per-step ArrayPathLoss: this step's table, at the new positions
         if self.num_agents:
             _native.episode_merge_actions(src.data_ptr(), t['actions'].data_ptr(), t['pending'].data_ptr(), t['episode'].data_ptr(),
@@ -489,7 +530,8 @@ class VecD2DEnv:
                                 t['reset'].data_ptr(), reward.data_ptr() if native else 0,
                                 1 if self.reward_per_env else self.num_links, self.num_envs, EPISODE_LENGTH, stream)
         if self._neighbors_k:
-            self._select_neighbors(t['reset'])                # the envs this step reset stand at new positions
+            refresh = self._mobility is not None and self.num_steps % self._neighbor_refresh == 0
+            self._select_neighbors(None if refresh else t['reset'])   # the envs this step reset stand at new positions; moved: all
         if self._wants_marginal:
             view = self._with_marginal(view)                  # after the step: the envs it reset at their new positions and actions
         obs = self._observe(view)
@@ -502,6 +544,22 @@ class VecD2DEnv:
         info = dict(self._info)
         info['reset'] = t['reset']
         return obs, rewards, t['done'], info
+
+    def _move_devices(self) -> None:
+        """One move of every device before the step about to be enqueued, then the handle's and the path-loss table's notice."""
+        m, sim = self._mobility, self.simulator
+        if self.autoreset:
+            m.move_per_env(self._t, self._seed, self._stream_ptr)
+        else:
+            m.move(self._t, self._seed, self.num_steps + 1, self._episode - 1, self._stream_ptr)
+        sim.handle.positions_changed()
+        sim.path_loss_table.positions_changed()
+
+    def velocities(self):
+        """(vel_x, vel_y), float32 [B, D] in m/s: the env's own planes, updated in place by every step (mobility= only)."""
+        if self._mobility is None:
+            raise ValueError('velocities() needs mobility=: this env\'s devices stand still between resets')
+        return self._mobility.vel_x, self._mobility.vel_y
 
     def request_reset(self, mask) -> None:
         """Reset the envs mask marks (bool [B], tensor or ndarray) at the next step() instead of stepping them - device-side and
@@ -531,7 +589,8 @@ class VecD2DEnv:
         rb[b, i] is the step's own sinr_db, an RB nobody else uses gives the link's SNR.  what='interference_mw': the sum, in mW, of
         what the other links on RB r put into link i's receiver (0.0 exactly on an RB nobody else uses).  One kernel launch
         (csrc/d2d_sense.hip).  Valid after reset() and after every step(), autoreset steps included: an env that was reset inside
-        the step is sensed at its new positions and its reset's random actions.
+        the step is sensed at its new positions and its reset's random actions.  With mobility= the position planes it reads are the
+        moved ones: current after every step.
 
         torch path: enqueued on torch's current stream, nothing is synchronised; the result is ONE tensor the env owns and
         rewrites on every call (clone it to keep it), or `out` (contiguous float32 [B, N, R] on the env's device) if given.
@@ -564,7 +623,8 @@ class VecD2DEnv:
         i's receiver gets per 0 dBm of link j's tx power, so that the step's interference on link i is the sum over j != i with
         rb_j == rb_i of lin(pwr_j + coupling[b, i, j]).  INDEX ORDER: [b, i, j] is receiver-major - i receives, j transmits, one
         agent's row contiguous; the path-loss tables elsewhere in the project are [b, j, i].  The diagonal holds the same formula
-        (own transmitter into own receiver, no receiver gains).  Positions and the model only: constant between resets.  One kernel
+        (own transmitter into own receiver, no receiver gains).  Positions and the model only: constant between resets - unless the
+        env has mobility=, where every call reads the position planes as the last move left them.  One kernel
         launch (csrc/d2d_graph.hip); 4 B N^2 bytes - 4.3 GB at 4096 x 512.
 
         torch path: enqueued on torch's current stream, nothing is synchronised; ONE tensor the env owns and rewrites on every call,
@@ -582,7 +642,8 @@ class VecD2DEnv:
         j != i with the largest coupling()[b, i, j] - i is the RECEIVING link, receiver-major as coupling() ([b, i, j]; the path-loss
         tables elsewhere are [b, j, i]) - strongest first, equal values (a downlink base station transmits every CUE link) in
         ascending j; coupling_db[b, i, m] is coupling()[b, i, idx[b, i, m]] bit for bit.  1 <= k <= min(N - 1, 64).  Positions and
-        the model only, never actions: constant between resets.  One kernel launch, no [B, N, N] cube.
+        the model only, never actions: constant between resets (with mobility=: current after every move; the lists an obs function
+        sees are re-selected every neighbor_refresh-th step).  One kernel launch, no [B, N, N] cube.
 
         torch path: on torch's current stream, nothing is synchronised; the pair of tensors the env owns for this k, rewritten by
         every call, or `out` = (idx, coupling_db), contiguous int32 / float32 [B, N, k] on the env's device.  NumPy path: fresh
@@ -621,7 +682,8 @@ class VecD2DEnv:
         and difference_mbps[b, i] = capacity_mbps[b, i] - harm_mbps[b, i] is the difference reward G(a) - G(a without link i) of
         the total capacity G.  harm >= 0; a link alone on its RB has harm == 0.0 and difference == capacity exactly.  One kernel
         launch (csrc/d2d_marginal.hip), no [B, N, N] cube.  Valid after reset() and after every step(), autoreset steps included:
-        an env that was reset inside the step is evaluated at its new positions and its reset's random actions.
+        an env that was reset inside the step is evaluated at its new positions and its reset's random actions; with mobility= at the
+        positions the step's own move left.
 
         torch path: enqueued on torch's current stream, nothing is synchronised; the pair of tensors the env owns, rewritten by
         every call (clone them to keep them), or `out` = (difference_mbps, harm_mbps), two contiguous float32 [B, N] tensors on the
@@ -660,8 +722,9 @@ class VecD2DEnv:
 
     def link_positions(self):
         """[B, N, 4] float32 (tx_x, tx_y, rx_x, rx_y) of every link = columns 0-3 of the obs table (obs_fn.py:57-59), constant
-        between resets.  torch path: a zero-copy view of the library's own rows (D2D_BUF_LINK_POS) - read-only, valid until
-        close(), refreshed by the library on reset."""
+        between resets (with mobility=: of the last move - call it after the step to bring the rows up to date).  torch path: a
+        zero-copy view of the library's own rows (D2D_BUF_LINK_POS) - read-only, valid until close(), refreshed by the library on
+        reset."""
         h = self.simulator.handle
         if not self.use_torch:
             return h.download(_native.BUF_LINK_POS)

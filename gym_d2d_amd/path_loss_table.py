@@ -43,6 +43,22 @@ def _write_live(torch, live, b0: int, b1: int, pl, snr) -> None:
     live[b0:b1, -1].copy_(snr if snr is not None else torch.diagonal(pl, dim1=1, dim2=2))
 
 
+def positions_move_unserved(sim, use_torch: bool):
+    """What about this env positions that change on the device inside step() cannot serve, as (kind, detail), or None: 'numpy' (the
+    bookkeeping lives in device tensors), 'route' (detail: the route's name - a table evaluated once per reset), 'pinned' (pinned
+    device_config coordinates float32 cannot hold).  The one predicate behind autoreset's and mobility's refusals, each with texts of
+    its own."""
+    if not use_torch:
+        return 'numpy', ''
+    route = sim.path_loss_table.route
+    if route not in (NATIVE, PER_STEP):
+        return 'route', route
+    mask, xy = sim.fixed_positions()
+    if mask.any() and (xy != xy.astype(np.float32)).any():
+        return 'pinned', ''
+    return None
+
+
 class PathLossTable:
     def __init__(self, handle, model: PathLoss, devices, config) -> None:
         self.handle, self.model, self.devices = handle, model, devices      # devices: the Device objects in handle order
