@@ -1,6 +1,6 @@
 """ctypes binding of libd2d_hip.so (include/d2d_hip.h), libd2d_plugin.so (include/d2d_plugin.h), libd2d_episode.so
-(include/d2d_episode.h), libd2d_sense.so (include/d2d_sense.h), libd2d_graph.so (include/d2d_graph.h), libd2d_marginal.so (include/d2d_marginal.h) and libd2d_mobility.so
-(include/d2d_mobility.h).  There is no CPU fallback: if a library or a gfx950 GPU is missing, the calls below raise."""
+(include/d2d_episode.h), libd2d_sense.so (include/d2d_sense.h), libd2d_graph.so (include/d2d_graph.h), libd2d_marginal.so (include/d2d_marginal.h), libd2d_mobility.so
+(include/d2d_mobility.h) and libd2d_channel.so (include/d2d_channel.h).  There is no CPU fallback: if a library or a gfx950 GPU is missing, the calls below raise."""
 from __future__ import annotations
 
 import ctypes as C
@@ -16,6 +16,7 @@ SENSE_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_sense.so'
 GRAPH_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_graph.so'
 MARGINAL_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_marginal.so'
 MOBILITY_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_mobility.so'
+CHANNEL_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_channel.so'
 ABI_VERSION = 7
 MAX_LINKS = 2048
 
@@ -55,6 +56,8 @@ GRAPH_MAX_K = 64
 # d2d_marginal_capacity's law / limits (include/d2d_marginal.h): the sensing kernel's
 MARGINAL_LAW_INV_SQUARE, MARGINAL_LAW_POWER, MARGINAL_LAW_POW_K = 0, 1, 2
 MARGINAL_MAX_RBS = 8192
+# d2d_channel_fill's fading (include/d2d_channel.h)
+CHANNEL_FADING_NONE, CHANNEL_FADING_RAYLEIGH, CHANNEL_FADING_RICIAN = 0, 1, 2
 
 BUFFER_DTYPES = {BUF_ACTIONS: np.int32, BUF_RB: np.int32, BUF_PWR: np.int32, BUF_ENV_FLAGS: np.int32, BUF_RESET_PENDING: np.int32,
                  BUF_EPISODE: np.uint32}
@@ -175,6 +178,13 @@ MOBILITY_SIGNATURES = {
     'd2d_mobility_last_error': (C.c_char_p, []),
 }
 
+# every symbol include/d2d_channel.h declares
+CHANNEL_SIGNATURES = {
+    'd2d_channel_fill': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int64, _I, _I, C.c_uint64, _I, C.c_float, C.c_double, _I, C.c_float,
+                                   C.c_float, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P, _P, _I, _P]),
+    'd2d_channel_last_error': (C.c_char_p, []),
+}
+
 _lib: Optional[C.CDLL] = None
 _plugin: Optional[C.CDLL] = None
 _episode: Optional[C.CDLL] = None
@@ -186,6 +196,8 @@ _marginal: Optional[C.CDLL] = None
 marginal_launches = 0               # d2d_marginal_capacity calls made through marginal_capacity() in this process
 _mobility: Optional[C.CDLL] = None
 mobility_launches = 0               # d2d_mobility_move calls made through mobility_move() in this process
+_channel: Optional[C.CDLL] = None
+channel_launches = 0                # d2d_channel_fill calls made through channel_fill() in this process
 
 
 def load_library() -> C.CDLL:
@@ -411,6 +423,43 @@ def mobility_move(pos_x_ptr: int, pos_y_ptr: int, vel_x_ptr: int, vel_y_ptr: int
     if rc != 0:
         raise NativeError(rc, lib.d2d_mobility_last_error().decode(errors='replace'))
     mobility_launches += 1
+
+
+def load_channel_library() -> C.CDLL:
+    """dlopen libd2d_channel.so and type its entry points.  Raises if it has not been built."""
+    global _channel
+    if _channel is not None:
+        return _channel
+    if not CHANNEL_PATH.exists():
+        raise ImportError(f'{CHANNEL_PATH} is missing - build it with `python -m gym_d2d_amd.build`')
+    lib = C.CDLL(str(CHANNEL_PATH))
+    for name, (res, args) in CHANNEL_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    _channel = lib
+    return lib
+
+
+def channel_fill(pos_x_ptr: int, pos_y_ptr: int, link_tx_ptr: int, link_rx_ptr: int, a_tx_ptr: int, a_rx_ptr: int, exponent_ptr: int,
+                 n_envs: int, n_dev: int, n_links: int, first_env: int, num_sinusoids: int, shadow_amp_db: float, wave_scale: float,
+                 fading: int, rician_mu: float, rician_s: float, shadow_seed: int, fading_seed: int, scratch_ptr: int, table_ptr: int,
+                 table_dtype: int = F64, step: int = 0, episode: int = 0, elapsed_ptr: int = 0, start_ptr: int = 0, episode_ptr: int = 0, reset_ptr: int = 0,
+                 stream_ptr: int = 0) -> None:
+    """d2d_channel_fill: the spatial channel's live dB table [n_envs, n_links + 1, n_links] of table_dtype (F32 / F64; device pointers) at the clock
+    (episode, step); reset_ptr != 0: the per-env clock of the four [n_envs] arrays."""
+    global channel_launches
+    lib = load_channel_library()
+    u64 = 2 ** 64 - 1
+    rc = lib.d2d_channel_fill(_P(pos_x_ptr or None), _P(pos_y_ptr or None), _P(link_tx_ptr or None), _P(link_rx_ptr or None),
+                              _P(a_tx_ptr or None), _P(a_rx_ptr or None), _P(exponent_ptr or None), n_envs, n_dev, n_links,
+                              C.c_uint64(first_env), num_sinusoids, shadow_amp_db, wave_scale, fading, rician_mu, rician_s,
+                              C.c_uint64(shadow_seed & u64), C.c_uint64(fading_seed & u64), step & 0xFFFFFFFF, episode & 0xFFFFFFFF,
+                              _P(elapsed_ptr or None), _P(start_ptr or None), _P(episode_ptr or None), _P(reset_ptr or None),
+                              _P(scratch_ptr or None), _P(table_ptr or None), table_dtype, _P(stream_ptr or None))
+    if rc != 0:
+        raise NativeError(rc, lib.d2d_channel_last_error().decode(errors='replace'))
+    channel_launches += 1
 
 
 def _check(rc: int) -> None:

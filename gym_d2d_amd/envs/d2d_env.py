@@ -38,6 +38,10 @@ class D2DEnv(Env):
         if int(env_config.get('num_envs', 1)) != 1:
             raise ValueError('D2DEnv is the single-env API; use VecD2DEnv for num_envs > 1')
         self.simulator = Simulator(env_config)
+        if self.simulator.path_loss_table.route == 'channel':
+            self.simulator.handle.close()
+            raise ValueError('path_loss_model=SpatialChannelPathLoss needs VecD2DEnv: the single-env D2DEnv keeps no episode clock '
+                             '(episode, step in the episode) for its draws (VecD2DEnv(num_envs=1) is the same env with one)')
         cfg = self.simulator.config
         self.observation_space = self.obs_fn.get_obs_space(cfg)
         self.num_pwr_actions = cfg.num_pwr_actions

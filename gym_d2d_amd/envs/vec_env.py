@@ -24,7 +24,7 @@ import numpy as np
 
 from .. import _native, graph, marginal, sensing
 from .. import mobility as mobility_mod
-from ..path_loss_table import PER_STEP, positions_move_unserved
+from ..path_loss_table import CHANNEL, PER_STEP, positions_move_unserved
 from ..simulator import BASE_STATION_ID, Simulator
 from ..traffic_model import DownlinkTrafficModel
 from . import _rng
@@ -86,7 +86,7 @@ class VecD2DEnv:
         synchronised: `dones` and info['reset'] are bool [B] device tensors the library writes every step - the SAME two tensor
         objects on every call, like the other aliased outputs (clone them to keep a step's values).  reset(elapsed=...) staggers
         the first episodes; request_reset(mask) resets chosen envs at the next step.  Needs the torch path and a path-loss model
-        the kernels evaluate per step (the native laws, ShadowingPathLoss, a per-step ArrayPathLoss): a table evaluated once per
+        the kernels evaluate per step (the native laws, ShadowingPathLoss, SpatialChannelPathLoss, a per-step ArrayPathLoss): a table evaluated once per
         reset, or pinned device_config coordinates float32 cannot hold, would need the host between steps (ValueError).
 
         mobility: a gym_d2d_amd.mobility.GaussMarkovMobility - devices move before every step (csrc/d2d_mobility.hip, one launch):
@@ -170,6 +170,10 @@ class VecD2DEnv:
             h.set_reward_layout(_native.REWARD_PER_ENV)
         self._array_obs = isinstance(self.obs_fn, ArrayObsFunction)
         self.use_torch = (torch is not None and torch.cuda.is_available()) if use_torch is None else use_torch
+        self._channel = sim.path_loss_table.route == CHANNEL      # SpatialChannelPathLoss: the table is filled at this env's clock
+        if self._channel and not self.use_torch:
+            raise ValueError('path_loss_model=SpatialChannelPathLoss needs the torch path (use_torch): its table is filled on the '
+                             "device, on torch's stream, before every step - the NumPy path has no such hook")
         if mobility is not None:                       # refusals surface here, before anything is allocated
             if not isinstance(mobility, mobility_mod.GaussMarkovMobility):
                 raise TypeError(f'mobility must be a GaussMarkovMobility or None, got {type(mobility).__name__}')
@@ -364,6 +368,8 @@ class VecD2DEnv:
             if self.num_agents:
                 self._t['actions'].copy_(_rng.uniform_ints_torch(torch, self._seed, self._episode, self.first_env,
                                                                   self.num_envs, self.num_agents, highs, self.device))
+            if self._channel:
+                self.simulator.path_loss_table.set_channel_clock(self._seed, self._episode, 0)
             self.simulator.prepare_step()
             self.simulator.handle.step()
         else:
@@ -380,6 +386,8 @@ class VecD2DEnv:
                 self._t['elapsed'].zero_()
             else:
                 self._t['elapsed'].copy_(torch.as_tensor(elapsed.astype(np.int32), device=self.device))
+            if self._channel:
+                self.simulator.path_loss_table.channel.start_episode(self._t['elapsed'])
         if self._mobility is not None:                        # behind the sampler; the reset's own step did not see a move
             self._mobility.start_episode(self._t, self._seed, self._episode - 1, self._stream_ptr)
         self.simulator.check_flags()
@@ -402,6 +410,9 @@ class VecD2DEnv:
             return
         if self.simulator.path_loss_table.route == PER_STEP:
             self.placement = {'skipped': 'a per-step ArrayPathLoss is evaluated before every step'}
+            return
+        if self._channel:
+            self.placement = {'skipped': 'SpatialChannelPathLoss is evaluated before every step'}
             return
         key, which = self._placement_target
         base = self._t[key]                                     # a view of the bound allocation (capacity may exceed the active part)
@@ -475,7 +486,9 @@ class VecD2DEnv:
                 raise ValueError(f'actions must be [{self.num_envs},{self.num_agents}], got {tuple(src.shape)}')
             if self._mobility is not None:
                 self._move_devices()
-            sim.prepare_step()                                # a per-step ArrayPathLoss: this step's table
+            if self._channel:
+                sim.path_loss_table.set_channel_clock(self._seed, self._episode - 1, self.num_steps + 1)
+            sim.prepare_step()                                # a per-step ArrayPathLoss or the spatial channel: this step's table
             if src.dtype == torch.int32 and src.is_contiguous() and src.device == self.device:
                 sim.handle.step(src.data_ptr())               # zero copy: the kernel reads the caller's tensor
             else:
@@ -517,6 +530,8 @@ class VecD2DEnv:
         h.reset_positions(self._seed, _native.EPISODE_PER_ENV)
         if self._mobility is not None:
             self._move_devices()                              # the envs that are not pending; the pending ones get new velocities
+        if self._channel:
+            sim.path_loss_table.set_channel_clock(self._seed, per_env=t)
         sim.prepare_step()                                    # a per-step ArrayPathLoss: this step's table, at the new positions
         if self.num_agents:
             _native.episode_merge_actions(src.data_ptr(), t['actions'].data_ptr(), t['pending'].data_ptr(), t['episode'].data_ptr(),
@@ -719,6 +734,14 @@ class VecD2DEnv:
         if self._obs64 and not self._native_obs64 and not isinstance(obs, tuple):   # the reference's dtype (obs_fn.py:51) for a custom array obs: cast here
             obs = obs.double() if self.use_torch else np.asarray(obs, dtype=np.float64)
         return obs
+
+    def path_loss_db(self):
+        """The live path-loss table of SpatialChannelPathLoss as the last step read it: [B, N + 1, N] dB, pl_db[b, j, i] from the
+        transmitter of link j to the receiver of link i, row N the links' own paths (the diagonal); the model's table_dtype.  The
+        route's own tensor, rewritten before every step (clone it to keep it).  ValueError for every other model."""
+        if not self._channel:
+            raise ValueError('path_loss_db() needs path_loss_model=SpatialChannelPathLoss: no other model keeps a table of every pair')
+        return self.simulator.path_loss_table.live
 
     def link_positions(self):
         """[B, N, 4] float32 (tx_x, tx_y, rx_x, rx_y) of every link = columns 0-3 of the obs table (obs_fn.py:57-59), constant

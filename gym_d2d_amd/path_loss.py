@@ -14,6 +14,8 @@ array-native form of the same plugin - compute(view) -> pl_db[B,N,N] on whole ar
 for a single pair), handed to the library from device memory (d2d_set_path_loss_link_table_dev).  An ArrayPathLoss with
 `per_step = True` is evaluated before EVERY step instead (a stochastic model: shadowing, fading), into a table the step kernel
 reads in place (D2D_PL_TABLE_LIVE); its view carries the step counter and the built-in shadowing's normal stream.
+`SpatialChannelPathLoss` is the native stochastic channel: a power-law median, spatially correlated shadowing and block fading,
+filled into the same live table by a HIP kernel of its own before every step (include/d2d_channel.h).
 """
 from __future__ import annotations
 
@@ -272,6 +274,117 @@ class ShadowingPathLoss(LogDistancePathLoss):
             # adds the per-evaluation Gaussian beyond d0 (csrc/d2d_step.hip, PL_SHADOW)
             cols['shadowing'] = {'d0_m': self.d0_m, 'chi_dB': self.chi_dB}
         return cols
+
+
+_UNSET = object()
+_U64 = (1 << 64) - 1
+SHADOW_SEED_MIX = 0x736861646F77696E     # 'shadowin': the three streams of one seed (mobility.SEED_MIX is the third) never coincide
+FADING_SEED_MIX = 0x666164696E676368     # 'fadingch'
+
+
+class SpatialChannelPathLoss(PathLoss):
+    """A spatially consistent stochastic channel, evaluated on the GPU before every step (csrc/d2d_channel.hip, one fill of the live
+    dB table the step kernel reads; include/d2d_channel.h states the model completely, counters included):
+
+        pl_db[b, j, i] = M(u, v) + S(p_u, p_v) + F(u, v)        u the transmitter DEVICE of link j, v the receiver device of link i
+
+    M: the median - any model that is a power law in distance (power_law_columns: LogDistancePathLoss with any exponent,
+       FreeSpacePathLoss, CostHataPathLoss), built as median(carrier_freq_GHz, **median_kwargs).
+    S: log-normal shadowing of standard deviation shadow_std_dB, a sum of num_sinusoids (8, 16 or 32) plane waves over the joint
+       (transmitter position, receiver position) space, redrawn per (env, episode) and never per step, with
+       E[S S'] = shadow_std_dB^2 exp(-(|dp_u| + |dp_v|) / decorrelation_m): a pair that stands still keeps its shadow, two receivers
+       a metre apart see nearly the same one, and with mobility= the shadow changes only as far as the devices move.
+       shadow_std_dB = 0: no shadowing work is launched.
+    F: block fading -10 log10 |h|^2, independent per step and per DEVICE pair: 'rayleigh' (|h|^2 ~ Exp(1)), 'rician' with
+       K = 10^(rician_k_dB / 10), or None.  Keyed by device pair, not link pair: every link the base station receives sees one
+       channel from a given transmitter.
+
+    The SNR's own evaluation of the signal path (row N of the live table, simulator.py:114) is the diagonal entry: the SAME physical
+    channel, not a second draw - unlike the built-in ShadowingPathLoss, which follows the reference in drawing again for the SNR.
+
+    table_dtype: 'float64' (default) or 'float32', the live table's entries.  A float32 entry above 128 dB (COST-Hata urban at a few
+    hundred metres) has an ulp of 1.5e-5 dB, so storing it alone costs up to 7.6e-6 dB - most of the project's 1e-5 bar where a step's
+    sinr_db is near 0 dB; float64 entries keep the step within the bar at twice the table's bytes (8.6 GB at 4096 x 512).
+
+    Stateless: a pure function of (seed, global env index, episode, step in the episode, device positions), so autoreset, sharding
+    and mobility= reproduce the lockstep single-GPU values bit for bit.  seed None: the env's seed; the shadowing and fading keys
+    are that seed XOR two constants of their own.  VecD2DEnv on the torch path only: the model needs the env's episode clock, and
+    it is a field over an env - it has no value for one isolated pair, so the per-object call raises NotImplementedError.
+
+    Reference plugin construction: one positional carrier_freq_GHz; everything else by keyword or as subclass attributes."""
+
+    median = LogDistancePathLoss
+    median_kwargs: Optional[dict] = None
+    shadow_std_dB = 8.0
+    decorrelation_m = 20.0
+    num_sinusoids = 16
+    fading: Optional[str] = 'rayleigh'
+    rician_k_dB = 6.0
+    seed: Optional[int] = None
+    table_dtype = 'float64'
+
+    def __init__(self, carrier_freq_GHz: float, median=_UNSET, median_kwargs=_UNSET, shadow_std_dB=_UNSET, decorrelation_m=_UNSET,
+                 num_sinusoids=_UNSET, fading=_UNSET, rician_k_dB=_UNSET, seed=_UNSET, table_dtype=_UNSET) -> None:
+        super().__init__(carrier_freq_GHz)
+        for name, v in (('median', median), ('median_kwargs', median_kwargs), ('shadow_std_dB', shadow_std_dB),
+                        ('decorrelation_m', decorrelation_m), ('num_sinusoids', num_sinusoids), ('fading', fading),
+                        ('rician_k_dB', rician_k_dB), ('seed', seed), ('table_dtype', table_dtype)):
+            if v is not _UNSET:
+                setattr(self, name, v)
+        for name in ('shadow_std_dB', 'decorrelation_m', 'rician_k_dB'):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
+                raise ValueError(f'{name} must be a finite number, got {v!r}')
+            setattr(self, name, float(v))
+        if self.shadow_std_dB < 0:
+            raise ValueError(f'shadow_std_dB must be >= 0, got {self.shadow_std_dB!r}')
+        if self.decorrelation_m <= 0:
+            raise ValueError(f'decorrelation_m must be > 0, got {self.decorrelation_m!r}')
+        if isinstance(self.num_sinusoids, bool) or self.num_sinusoids not in (8, 16, 32):
+            raise ValueError(f'num_sinusoids must be 8, 16 or 32, got {self.num_sinusoids!r}')
+        self.num_sinusoids = int(self.num_sinusoids)
+        if self.fading not in ('rayleigh', 'rician', None):
+            raise ValueError(f"fading must be 'rayleigh', 'rician' or None, got {self.fading!r}")
+        if self.table_dtype not in ('float32', 'float64'):
+            raise ValueError(f"table_dtype must be 'float32' or 'float64', got {self.table_dtype!r}")
+        s = self.seed
+        if s is not None and (isinstance(s, bool) or not isinstance(s, (int, np.integer)) or not 0 <= int(s) <= _U64):
+            raise ValueError(f'seed must be None or an int in [0, 2^64), got {s!r}')
+        self.seed = None if s is None else int(s)
+        if not (isinstance(self.median, type) and issubclass(self.median, PathLoss)) or issubclass(self.median, SpatialChannelPathLoss):
+            raise ValueError(f'median must be a PathLoss class that is a power law in distance, got {self.median!r}')
+        self.median_model = self.median(carrier_freq_GHz, **dict(self.median_kwargs or {}))
+
+    def __call__(self, tx: Device, rx: Device) -> float:
+        raise NotImplementedError('SpatialChannelPathLoss is a field over an env (its shadowing is a function of every position of the '
+                                  'env, its draws are keyed by env, episode and step): it has no value for one isolated (tx, rx) pair. '
+                                  'Use it as the path_loss_model of a VecD2DEnv')
+
+    def median_columns(self, devices: Sequence[Device]) -> Dict[str, np.ndarray]:
+        """The median's power-law columns, or ValueError: a median the fill kernel cannot evaluate per pair."""
+        cols = self.median_model.power_law_columns(devices)
+        if cols is None:
+            raise ValueError(f'SpatialChannelPathLoss: median={type(self.median_model).__name__} is not a power law in distance '
+                             '(its power_law_columns is None); the median must be LogDistancePathLoss, FreeSpacePathLoss, '
+                             'CostHataPathLoss or another model with columns')
+        if 'shadowing' in cols:
+            raise ValueError(f'SpatialChannelPathLoss: median={type(self.median_model).__name__} draws a shadowing of its own per '
+                             'evaluation; the median must be deterministic (shadow_std_dB is this model\'s shadowing)')
+        return cols
+
+    def constants(self):
+        """(num_sinusoids or 0, shadow_amp_db, wave_scale, fading id, rician_mu, rician_s) as the kernel takes them: formed in
+        double, the float32 ones rounded once."""
+        m = self.num_sinusoids if self.shadow_std_dB > 0 else 0
+        amp = float(np.float32(self.shadow_std_dB * math.sqrt(2.0 / self.num_sinusoids)))
+        k = 10.0 ** (self.rician_k_dB / 10.0)
+        mu, s = float(np.float32(math.sqrt(k / (k + 1.0)))), float(np.float32(math.sqrt(1.0 / (2.0 * (k + 1.0)))))
+        return m, amp, 1.0 / (2.0 * math.pi * self.decorrelation_m), {None: 0, 'rayleigh': 1, 'rician': 2}[self.fading], mu, s
+
+    def stream_seeds(self, env_seed: int):
+        """(shadowing key, fading key) for an env seeded env_seed."""
+        base = self.seed if self.seed is not None else int(env_seed)
+        return (base ^ SHADOW_SEED_MIX) & _U64, (base ^ FADING_SEED_MIX) & _U64
 
 
 class AreaType(Enum):

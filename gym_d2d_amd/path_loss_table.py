@@ -6,6 +6,8 @@
     array         a batch, an ArrayPathLoss: compute(view) on the GPU once per reset, [B, N, N] from device memory
                   (d2d_set_path_loss_link_table_dev), or a live [B, N+1, N] table when compute returns the SNR row
     per_step      ArrayPathLoss.per_step: compute(view) before every step into a live [B, N+1, N] table the step kernel reads
+    channel       SpatialChannelPathLoss: libd2d_channel.so fills a live [B, N+1, N] table (float64, or float32 on request) before every step, at the clock
+                  (episode, step in the episode) VecD2DEnv hands over
 """
 from __future__ import annotations
 
@@ -17,10 +19,10 @@ from typing import Optional
 import numpy as np
 
 from . import _native
-from .path_loss import ArrayPathLoss, PathLoss, PathLossView, warn_if_stochastic
+from .path_loss import ArrayPathLoss, PathLoss, PathLossView, SpatialChannelPathLoss, warn_if_stochastic
 from .position import Position
 
-NATIVE, DEVICE_TABLE, LINK_TABLE, ARRAY, PER_STEP = 'native', 'device_table', 'link_table', 'array', 'per_step'
+NATIVE, DEVICE_TABLE, LINK_TABLE, ARRAY, PER_STEP, CHANNEL = 'native', 'device_table', 'link_table', 'array', 'per_step', 'channel'
 PL_CHUNK_BYTES = 1 << 30            # ArrayPathLoss.env_chunk = None: envs per compute() call keep one [b,N,N] float64 within this
 
 
@@ -51,7 +53,7 @@ def positions_move_unserved(sim, use_torch: bool):
     if not use_torch:
         return 'numpy', ''
     route = sim.path_loss_table.route
-    if route not in (NATIVE, PER_STEP):
+    if route not in (NATIVE, PER_STEP, CHANNEL):
         return 'route', route
     mask, xy = sim.fixed_positions()
     if mask.any() and (xy != xy.astype(np.float32)).any():
@@ -63,8 +65,17 @@ class PathLossTable:
     def __init__(self, handle, model: PathLoss, devices, config) -> None:
         self.handle, self.model, self.devices = handle, model, devices      # devices: the Device objects in handle order
         self.num_envs, self.device_ordinal, self.config_seed = int(config.num_envs), config.device_ordinal, config.seed
-        self.law = model.power_law_columns(devices)
-        if self.law is not None:
+        self.channel = None                         # channel: the route's device-side state (ChannelFill)
+        spatial = isinstance(model, SpatialChannelPathLoss)
+        # channel: the law is the MEDIAN's (ValueError: a median without columns, or a stochastic one)
+        self.law = model.median_columns(devices) if spatial else model.power_law_columns(devices)
+        if spatial:
+            if len(devices) >= 65536:
+                raise ValueError('SpatialChannelPathLoss: the env must have fewer than 65536 devices (the fading counter holds two '
+                                 'device indices in one word)')
+            self.route = CHANNEL
+            self.channel = ChannelFill(self, model)
+        elif self.law is not None:
             self.route = NATIVE
         elif isinstance(model, ArrayPathLoss) and model.per_step:
             _torch_cuda()
@@ -87,6 +98,8 @@ class PathLossTable:
     def install(self) -> None:
         """Hand the native route's law to the handle and draw the seeds (again: restarts the built-in shadowing's stream)."""
         law = self.law
+        if self.route == CHANNEL:
+            return                                  # the law is the fill kernel's; the keys derive from the env's seed per fill
         if law is not None and law.get('shadowing'):
             self.shadowing_seed = self.config_seed if self.config_seed is not None else random.getrandbits(63)
             self.handle.set_path_loss_shadowing(law['a_tx_db'], law['a_rx_db'], law['exponent'], law['shadowing']['d0_m'],
@@ -104,6 +117,9 @@ class PathLossTable:
         """positions [B, D, 2] as the handle was given them, or None: the Device objects' (one env) or the handle's (a batch)."""
         if self.route == NATIVE:
             return
+        if self.route == CHANNEL:
+            self.channel.moved = True               # the fill reads POS_X / POS_Y where they are
+            return
         self.positions_known, self.covered, self.cols = True, (set(), set()), None
         # a COPY: the caller may reuse its array before a later set_links re-evaluates the table from it
         self.positions = None if positions is None else np.array(positions, dtype=np.float64, copy=True)
@@ -112,13 +128,19 @@ class PathLossTable:
     def links_changed(self, link_tx: np.ndarray, link_rx: np.ndarray) -> None:
         self.link_tx, self.link_rx = link_tx, link_rx
         self.cols, self.live_bound = None, False    # d2d_set_links drops a table bound for the old list
+        if self.channel is not None:
+            self.channel.links = None
         if self.positions_known:
             self._evaluate()                        # pairs the new link list reads that the table does not hold yet
 
     def before_step(self) -> None:
         """per_step: evaluate the model for the step about to be enqueued (view.step = the step's counter) into the live table
         the step kernel reads.  Ordered with the step: on the handle's stream when that is torch's current one (VecD2DEnv), else
-        by synchronising both sides."""
+        by synchronising both sides.  channel: libd2d_channel.so's fill for that step, on the handle's stream."""
+        if self.route == CHANNEL:
+            if len(self.link_tx):
+                self.channel.fill()
+            return
         if self.route == PER_STEP and len(self.link_tx):
             torch = _torch_cuda()
             dev, n = torch.device('cuda', self.device_ordinal), len(self.link_tx)
@@ -140,6 +162,12 @@ class PathLossTable:
                     self.live_bound = True
         if self.seed is not None:
             self.step += 1                          # also the counter a once-per-reset ArrayPathLoss sees at its next evaluation
+
+    def set_channel_clock(self, env_seed: int, episode: int = 0, step: int = 0, per_env: Optional[dict] = None) -> None:
+        """channel: where the step about to be enqueued stands - lockstep (episode, step in the episode; 0 is the reset's own
+        step), or per_env: VecD2DEnv's tensors 'episode', 'elapsed', 'pending' of an autoreset step.  A no-op for other routes."""
+        if self.channel is not None:
+            self.channel.clock = (int(env_seed), int(episode), int(step), per_env)
 
     # ------------------------------------------------------------------ the routes
     def _evaluate(self) -> None:
@@ -257,3 +285,67 @@ class PathLossTable:
             out = live if live is not None else table
             self.handle.set_path_loss_link_table_dev(out.data_ptr(), _native.F64 if out.dtype == torch.float64 else _native.F32, n,
                                                      _native.PL_TABLE_LIVE if live is not None else True)
+
+
+class ChannelFill:
+    """The 'channel' route's device side: the live table (the model's table_dtype), the phase work space, the link lists and law columns as device
+    tensors (allocated once per link list), and one d2d_channel_fill per step on the handle's stream.  With fading=None the table
+    depends on the positions and the episode only: a fill is skipped when nothing moved since the last one (no mobility=, no
+    device-side reset that step)."""
+
+    def __init__(self, table: PathLossTable, model: SpatialChannelPathLoss) -> None:
+        self.table, self.model, self.consts = table, model, model.constants()
+        self.clock = None                           # (env seed, episode, step, per-env tensors or None): set_channel_clock
+        self.links = None                           # (link_tx, link_rx) int32 device tensors of the current list
+        self.cols = self.scratch = self.start = None
+        self.moved = True
+        self.fills = 0
+
+    def start_episode(self, elapsed) -> None:
+        """Autoreset: what `elapsed` is at reset() - the per-env clock's origin, as Mobility.start."""
+        if self.start is None:
+            self.start = elapsed.clone()
+        else:
+            self.start.copy_(elapsed)
+
+    def fill(self) -> None:
+        t = self.table
+        if self.clock is None:
+            raise ValueError('SpatialChannelPathLoss needs an episode clock (episode, step in the episode), which only VecD2DEnv '
+                             'keeps: Simulator.step / step_arrays and the single-env D2DEnv cannot drive it')
+        env_seed, episode, step, per_env = self.clock
+        m, amp, wave_scale, fading, mu, s = self.consts
+        if self.links is not None and per_env is None and not self.moved and fading == _native.CHANNEL_FADING_NONE:
+            return                                  # same positions, same episode, no per-step draw: the table is still right
+        torch = _torch_cuda()
+        h, n, d = t.handle, len(t.link_tx), len(t.devices)
+        dev = torch.device('cuda', t.device_ordinal)
+        stream = t.stream if t.stream is not None else 0
+        with torch.cuda.device(dev):
+            if t.stream is None:
+                raise ValueError("SpatialChannelPathLoss: the handle must run on torch's current stream (VecD2DEnv puts it there)")
+            if self.cols is None:
+                self.cols = tuple(torch.as_tensor(np.ascontiguousarray(t.law[k], dtype=np.float64), device=dev)
+                                  for k in ('a_tx_db', 'a_rx_db', 'exponent'))
+            if self.links is None:
+                self.links = tuple(torch.as_tensor(np.ascontiguousarray(j, dtype=np.int32), device=dev) for j in (t.link_tx, t.link_rx))
+                f64 = self.model.table_dtype == 'float64'
+                t.live = torch.empty((t.num_envs, n + 1, n), dtype=torch.float64 if f64 else torch.float32, device=dev)
+                self.scratch = torch.empty((t.num_envs, n, m, 4), dtype=torch.float32, device=dev) if m else None
+                self.dtype = _native.F64 if f64 else _native.F32
+                h.set_path_loss_link_table_dev(t.live.data_ptr(), self.dtype, n, _native.PL_TABLE_LIVE)
+                t.live_bound = True
+            shadow_seed, fading_seed = self.model.stream_seeds(env_seed)
+            clock = dict(step=step, episode=episode)
+            if per_env is not None:
+                if self.start is None:
+                    self.start = torch.zeros(t.num_envs, dtype=torch.int32, device=dev)
+                clock = dict(elapsed_ptr=per_env['elapsed'].data_ptr(), start_ptr=self.start.data_ptr(),
+                             episode_ptr=per_env['episode'].data_ptr(), reset_ptr=per_env['pending'].data_ptr())
+            _native.channel_fill(h.get_buffer(_native.BUF_POS_X)[0], h.get_buffer(_native.BUF_POS_Y)[0], self.links[0].data_ptr(),
+                                 self.links[1].data_ptr(), *(c.data_ptr() for c in self.cols), t.num_envs, d, n, h.env_offset, m, amp,
+                                 wave_scale, fading, mu, s, shadow_seed, fading_seed,
+                                 0 if self.scratch is None else self.scratch.data_ptr(), t.live.data_ptr(), self.dtype, stream_ptr=stream,
+                                 **clock)
+        self.moved = False
+        self.fills += 1

@@ -1,0 +1,303 @@
+"""SpatialChannelPathLoss on the GPU (csrc/d2d_channel.hip, the 'channel' route): the live table against the float64 restatement of
+include/d2d_channel.h (tests/channel_util.py) entry by entry, the step against the oracle's step on that table, and the table against
+itself: row N, device-pair keying, shards, staggered autoreset, the skipped fill, mobility's Lipschitz bound, the refusals."""
+import numpy as np
+import pytest
+
+import channel_util as cu
+from oracle import d2d_oracle as orc
+
+pytestmark = pytest.mark.gpu
+TOL = 1e-5                      # the project's parity bar
+DEEP_FADE = 1e-4                # entries whose restated |h|^2 is below this are left out ...
+DEEP_FADE_CAP = 1e-3            # ... and may be this fraction of the entries at most (Exp(1) puts 1e-4 there)
+FIRST_ENV, SEED, CFG_SEED = 4096, 29, 4321
+SHAPES = {'small': (3, 3, 2, 4), 'large': (6, 70, 61, 8)}          # B, CUEs, DUE pairs, RBs: 131 links, 193 devices
+MEDIANS = ('ple2', 'ple3.5', 'hata_urban')
+
+
+def _median(name):
+    """(median class, its kwargs, the oracle's spec of the same law)."""
+    from gym_d2d_amd.path_loss import AreaType, CostHataPathLoss, LogDistancePathLoss
+    if name == 'hata_urban':
+        return CostHataPathLoss, {'area_type': AreaType.URBAN}, orc.PathLossSpec('cost_hata', 2.1, area='urban')
+    ple = float(name[3:])
+    return LogDistancePathLoss, {'ple': ple}, orc.PathLossSpec('log_distance', 2.1, ple=ple)
+
+
+def _model(median='ple2', **kw):
+    from gym_d2d_amd.path_loss import SpatialChannelPathLoss
+    cls, kwargs, _ = _median(median)
+    return type('Channel', (SpatialChannelPathLoss,), dict(median=cls, median_kwargs=kwargs, **kw))
+
+
+def _env(shape, model, **kw):
+    from gym_d2d_amd.envs import VecD2DEnv
+    b, cues, pairs, rbs = SHAPES[shape] if isinstance(shape, str) else shape
+    kw.setdefault('first_env', FIRST_ENV)
+    return VecD2DEnv({'num_rbs': rbs, 'num_cues': cues, 'num_due_pairs': pairs, 'seed': CFG_SEED, 'path_loss_model': model},
+                     num_envs=b, **kw)
+
+
+def _cols(shape):
+    _, cues, pairs, _ = SHAPES[shape] if isinstance(shape, str) else shape
+    _, cfgs, is_bs = orc.device_configs(cues, pairs)
+    return orc.device_columns(cfgs, is_bs)
+
+
+def _table(env):
+    return env.simulator.path_loss_table.live.cpu().numpy().copy()
+
+
+def _actions(env, rng):
+    import torch
+    highs = env._initial_action_highs()
+    return torch.as_tensor(np.stack([rng.integers(0, h, env.num_envs) for h in highs], 1).astype(np.int32), device='cuda')
+
+
+def _restated(env, shape, median, episode, t, **kw):
+    sim = env.simulator
+    return cu.table_db(sim.positions().astype(np.float64), sim.link_tx, sim.link_rx, _cols(shape), _median(median)[2], env_seed=SEED,
+                       first_env=env.first_env, episode=episode, t=t, **kw)
+
+
+def _entry_error(got, want, h2):
+    """Worst |got - want| / |want| over the entries that are not deep fades; the share of entries left out."""
+    keep = np.ones(want.shape, dtype=bool)
+    if h2 is not None:
+        n = h2.shape[1]
+        keep[:, :n] = h2 >= DEEP_FADE
+        keep[:, n] = h2[:, np.arange(n), np.arange(n)] >= DEEP_FADE
+    assert np.isfinite(want[keep]).all()
+    return float(np.max(np.abs(got - want)[keep] / np.abs(want)[keep])), 1.0 - keep.mean()
+
+
+# ------------------------------------------------------------------------------------------ 1: the table, entry by entry
+@pytest.mark.parametrize('dtype', ['float64', 'float32'])
+@pytest.mark.parametrize('median', MEDIANS)
+@pytest.mark.parametrize('fading', ['rayleigh', 'rician', None])
+@pytest.mark.parametrize('shape', list(SHAPES))
+def test_table_matches_the_restatement_entry_by_entry(shape, fading, median, dtype):
+    """Both entry widths, the same bar.  Measured on one MI355X: with float32 entries an earlier run gave a worst error of 1.96e-7 of the entry over all 54 cases (reset's step and step 1); float64 entries: not measured here."""
+    rng = np.random.default_rng(3)
+    for m in (8, 16, 32):
+        kw = dict(num_sinusoids=m, fading=fading, shadow_std_dB=8.0, decorrelation_m=20.0, rician_k_dB=6.0)
+        env = _env(shape, _model(median, table_dtype=dtype, **kw))
+        env.reset(seed=SEED)
+        assert _table(env).dtype == np.dtype(dtype)
+        for t in (0, 1):
+            if t:
+                env.step(_actions(env, rng))
+            want, h2 = _restated(env, shape, median, 0, t, **kw)
+            err, left_out = _entry_error(_table(env), want, h2)
+            print(f'{shape} {median} {fading} {dtype} M={m} t={t}: worst error {err:.3g} of the entry, {left_out:.2%} left out')
+            assert left_out <= DEEP_FADE_CAP
+            assert err <= TOL
+        assert env.status_flags() == 0
+        env.close()
+
+
+def test_no_shadowing_launches_no_shadowing_work_and_matches():
+    kw = dict(shadow_std_dB=0.0, fading='rayleigh')
+    env = _env('large', _model('ple3.5', **kw))
+    env.reset(seed=SEED)
+    assert env.simulator.path_loss_table.channel.scratch is None
+    want, h2 = _restated(env, 'large', 'ple3.5', 0, 0, **kw)
+    err, left_out = _entry_error(_table(env), want, h2)
+    print(f'no shadowing: worst error {err:.3g}')
+    assert err <= TOL and left_out <= DEEP_FADE_CAP
+    env.close()
+
+
+# ------------------------------------------------------------------------------------------ 2: the step against the oracle
+@pytest.mark.parametrize('dtype', ['float64', 'float32'])
+@pytest.mark.parametrize('mobile', [False, True])
+@pytest.mark.parametrize('shape,fading,median', [('small', 'rayleigh', 'ple2'), ('large', 'rician', 'hata_urban'),
+                                                 ('large', 'rayleigh', 'ple3.5')])
+def test_step_matches_the_oracle_on_the_restated_table(shape, fading, median, mobile, dtype):
+    """float64 entries (the model's default): the project's bar, 1e-5, on all three outputs.
+
+    float32 entries (table_dtype='float32'): the bar plus what the FORMAT costs, worked out from the reference table of the case and
+    nothing else.  Storing an entry x as float32 moves it by up to d = ulp32(|x|) / 2 dB - 7.63e-6 dB for 128 <= x < 256, where the
+    COST-Hata urban entries at a few hundred metres lie.  snr_db reads one entry: it moves by d at most.  sinr_db is the signal
+    entry minus 10 log10 of a positively weighted sum of 10^(-entry / 10) terms and the noise, which moves by at most the largest
+    move of a term: 2 d in all.  capacity_mbps moves by bandwidth (0.18 MHz) x 0.33 per dB of sinr: below 1e-6, left at the bar.
+    So: snr_db <= 1e-5 + d, sinr_db <= 1e-5 + 2 d, d from the largest finite entry of the restated table.
+
+    Measured on one MI355X: with float32 entries an earlier run gave sinr_db up to 1.08e-5 and snr_db up to 8.2e-6 (COST-Hata urban), capacity_mbps 6.1e-7."""
+    from gym_d2d_amd.mobility import GaussMarkovMobility
+    kw = dict(num_sinusoids=16, fading=fading)
+    env = _env(shape, _model(median, table_dtype=dtype, **kw), mobility=GaussMarkovMobility(speed_std_mps=5.0) if mobile else None)
+    env.reset(seed=SEED)
+    sim, cols, rng = env.simulator, _cols(shape), np.random.default_rng(8)
+    worst, d = {}, 0.0
+    for t in range(4):                                               # the reset's step and three further steps
+        if t:
+            env.step(_actions(env, rng))
+        pos = sim.positions().astype(np.float64)
+        want, _ = _restated(env, shape, median, 0, t, **kw)
+        dense = cu.scatter_to_devices(want, sim.link_tx, sim.link_rx, pos.shape[1])
+        if dtype == 'float32':
+            top = np.float32(np.abs(want[np.isfinite(want)]).max())
+            d = max(d, 0.5 * float(np.nextafter(top, np.float32(np.inf)) - top))
+        view = env._view()
+        ref = orc.step(pos, sim.link_tx, sim.link_rx, view.rb.cpu().numpy(), view.pwr.cpu().numpy(), cols,
+                       orc.PathLossSpec('table', table_db=dense))
+        for f in ('sinr_db', 'snr_db', 'capacity_mbps'):
+            got = getattr(view, f).cpu().numpy()
+            err = float(np.max(np.abs(got - ref[f]) / np.maximum(np.abs(ref[f]), 1.0)))
+            worst[f] = max(worst.get(f, 0.0), err)
+            print(f'{shape} {fading} {median} {dtype} mobile={mobile} t={t} {f}: {err:.3g}')
+    assert env.status_flags() == 0
+    env.close()
+    bars = {'sinr_db': TOL + 2 * d, 'snr_db': TOL + d, 'capacity_mbps': TOL}
+    for f, err in worst.items():
+        assert err <= bars[f], (f, err, bars[f])
+
+
+# ------------------------------------------------------------------------------------------ 3: bit for bit
+def test_float32_entries_are_the_float64_entries_rounded_once():
+    tabs = {}
+    for dtype in ('float64', 'float32'):
+        env = _env('large', _model('hata_urban', fading='rician', num_sinusoids=16, table_dtype=dtype))
+        env.reset(seed=SEED)
+        env.step(_actions(env, np.random.default_rng(1)))
+        tabs[dtype] = _table(env)
+        assert env.status_flags() == 0
+        env.close()
+    assert tabs['float64'].dtype == np.float64 and tabs['float32'].dtype == np.float32
+    assert (tabs['float64'] != tabs['float64'].astype(np.float32)).any()             # the float64 entries carry more than float32
+    assert np.array_equal(tabs['float64'].astype(np.float32), tabs['float32'])
+
+
+def test_row_n_is_the_diagonal_and_entries_are_keyed_by_device_pair():
+    env = _env('large', _model('ple3.5', fading='rician', num_sinusoids=32))
+    env.reset(seed=SEED)
+    env.step(_actions(env, np.random.default_rng(1)))
+    tab, n, cues = _table(env), env.num_links, env.num_cues
+    assert np.array_equal(env.path_loss_db().cpu().numpy(), tab)         # the public accessor is the table the step read
+    assert np.array_equal(tab[:, n], tab[:, np.arange(n), np.arange(n)])
+    # every CUE uplink is received by the base station: links with the same (tx, rx) devices as seen from row j hold the same entry
+    assert (env.simulator.link_rx[:cues] == 0).all()
+    assert np.array_equal(tab[:, :n, :cues], np.repeat(tab[:, :n, :1], cues, axis=2))
+    assert not np.array_equal(tab[:, :n, cues], tab[:, :n, cues + 1])
+    env.close()
+
+
+def test_two_shards_equal_the_whole_batch():
+    b, cues, pairs, rbs = SHAPES['large']
+    model = _model('hata_urban', fading='rayleigh', num_sinusoids=8)
+    rng = np.random.default_rng(2)
+    whole = _env('large', model)
+    whole.reset(seed=SEED)
+    acts = _actions(whole, rng)
+    whole.step(acts)
+    want = _table(whole)
+    whole.close()
+    for k, (lo, hi) in enumerate(((0, 2), (2, b))):                  # uneven shards
+        part = _env((hi - lo, cues, pairs, rbs), model, first_env=FIRST_ENV + lo)
+        part.reset(seed=SEED)
+        part.step(acts[lo:hi].contiguous())
+        assert np.array_equal(_table(part), want[lo:hi]), k
+        part.close()
+
+
+def test_staggered_autoreset_equals_one_lockstep_env_each():
+    from gym_d2d_amd.envs.d2d_env import EPISODE_LENGTH
+    shape, steps = (5, 4, 3, 3), 24                                  # two episode boundaries for every env
+    model = _model('ple2', fading='rayleigh', num_sinusoids=16)
+    env = _env(shape, model, autoreset=True, first_env=40)
+    env.reset(seed=SEED, elapsed=np.arange(shape[0]) % EPISODE_LENGTH)
+    first, rng = _table(env), np.random.default_rng(4)
+    acts, tabs, sinrs, resets = [], [], [], []
+    for _ in range(steps):
+        a = _actions(env, rng)
+        _, _, _, info = env.step(a)
+        acts.append(a); tabs.append(_table(env)); sinrs.append(info['sinr_db'].cpu().numpy().copy())
+        resets.append(info['reset'].cpu().numpy().copy())
+    env.close()
+    resets = np.array(resets)
+    assert (resets.sum(axis=0) >= 2).all()
+    for e in range(shape[0]):
+        one = _env((1,) + shape[1:], model, first_env=40 + e)
+        one.reset(seed=SEED)
+        assert np.array_equal(_table(one), first[e:e + 1]), e
+        for t in range(steps):
+            if resets[t, e]:
+                one.reset()
+            else:
+                one.step(acts[t][e:e + 1].contiguous())
+            assert np.array_equal(_table(one), tabs[t][e:e + 1]), (e, t)
+            assert np.array_equal(one._view().sinr_db.cpu().numpy(), sinrs[t][e:e + 1]), (e, t)
+        one.close()
+
+
+def test_without_fading_or_mobility_the_table_is_filled_once_per_episode():
+    from gym_d2d_amd import _native
+    env = _env('small', _model('ple2', fading=None))
+    rng = np.random.default_rng(6)
+    per_episode = []
+    for _ in range(2):
+        before = _native.channel_launches
+        env.reset()
+        tabs = [_table(env)]
+        for _ in range(4):
+            env.step(_actions(env, rng))
+            tabs.append(_table(env))
+        assert _native.channel_launches == before + 1
+        assert all(np.array_equal(tabs[0], t) for t in tabs[1:])
+        per_episode.append(tabs[0])
+    assert not np.array_equal(per_episode[0], per_episode[1])
+    env.close()
+    # with fading the kernel runs before every step
+    env = _env('small', _model('ple2', fading='rayleigh'))
+    before = _native.channel_launches
+    env.reset()
+    for _ in range(3):
+        env.step(_actions(env, rng))
+    assert _native.channel_launches == before + 4
+    env.close()
+
+
+# ------------------------------------------------------------------------------------------ 4: mobility
+def test_a_moving_pair_s_shadow_changes_within_the_model_s_lipschitz_bound():
+    from gym_d2d_amd.mobility import GaussMarkovMobility
+    sigma, m, dc = 8.0, 16, 20.0
+    kw = dict(fading=None, shadow_std_dB=sigma, num_sinusoids=m, decorrelation_m=dc)
+    env = _env('large', _model('ple2', **kw), mobility=GaussMarkovMobility(speed_std_mps=0.5))
+    env.reset(seed=SEED)
+    sim, b, n = env.simulator, env.num_envs, env.num_links
+    k_tx, k_rx, _ = cu.wave_vectors(cu.stream_seeds(SEED)[0], FIRST_ENV, 0, b, m, dc)
+    k_max = np.sqrt(np.maximum((k_tx ** 2).sum(-1), (k_rx ** 2).sum(-1))).max(axis=1)          # [B]: max_m |k_m| of the env's draws
+    spec, cols, rng = _median('ple2')[2], _cols('large'), np.random.default_rng(9)
+
+    def shadow():
+        pos = sim.positions().astype(np.float64)
+        with np.errstate(divide='ignore'):
+            return _table(env)[:, :n].astype(np.float64) - orc.pair_path_loss_db(spec, pos, sim.link_tx, sim.link_rx, cols), pos
+    prev, prev_pos = shadow()
+    series = [prev]
+    for _ in range(9):
+        env.step(_actions(env, rng))
+        cur, pos = shadow()
+        move = np.linalg.norm(pos - prev_pos, axis=-1)               # [B, D]
+        bound = sigma * np.sqrt(2 * m) * (move[:, sim.link_tx][:, :, None] + move[:, sim.link_rx][:, None, :]) * k_max[:, None, None]
+        # (the median was taken off the GPU's table in float64: 1e-4 dB covers the two's arithmetic, far below the bound's own size)
+        assert (np.abs(cur - prev) <= bound + 1e-4).all()
+        series.append(cur); prev, prev_pos = cur, pos
+    series = np.array(series)
+    assert (np.ptp(series, axis=0)[:, env.num_cues:, env.num_cues:] > 1e-3).all()              # non-constant over the episode
+    env.close()
+
+
+# ------------------------------------------------------------------------------------------ 5: refusals
+def test_sensing_coupling_and_marginal_capacity_refuse_the_route():
+    env = _env('small', _model('ple2'))
+    env.reset(seed=SEED)
+    with pytest.raises(ValueError, match="sense\\(\\) does not serve the 'channel' path-loss route"):
+        env.sense()
+    with pytest.raises(ValueError, match="'channel' path-loss route"):
+        env.coupling()
+    with pytest.raises(ValueError, match="'channel' path-loss route"):
+        env.marginal_capacity()
+    env.close()
