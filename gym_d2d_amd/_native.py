@@ -1,6 +1,6 @@
 """ctypes binding of libd2d_hip.so (include/d2d_hip.h), libd2d_plugin.so (include/d2d_plugin.h), libd2d_episode.so
 (include/d2d_episode.h), libd2d_sense.so (include/d2d_sense.h), libd2d_graph.so (include/d2d_graph.h), libd2d_marginal.so (include/d2d_marginal.h), libd2d_mobility.so
-(include/d2d_mobility.h) and libd2d_channel.so (include/d2d_channel.h).  There is no CPU fallback: if a library or a gfx950 GPU is missing, the calls below raise."""
+(include/d2d_mobility.h), libd2d_channel.so (include/d2d_channel.h) and libd2d_queue.so (include/d2d_queue.h).  There is no CPU fallback: if a library or a gfx950 GPU is missing, the calls below raise."""
 from __future__ import annotations
 
 import ctypes as C
@@ -17,6 +17,7 @@ GRAPH_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_graph.so'
 MARGINAL_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_marginal.so'
 MOBILITY_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_mobility.so'
 CHANNEL_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_channel.so'
+QUEUE_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_queue.so'
 ABI_VERSION = 7
 MAX_LINKS = 2048
 
@@ -58,6 +59,8 @@ MARGINAL_LAW_INV_SQUARE, MARGINAL_LAW_POWER, MARGINAL_LAW_POW_K = 0, 1, 2
 MARGINAL_MAX_RBS = 8192
 # d2d_channel_fill's fading (include/d2d_channel.h)
 CHANNEL_FADING_NONE, CHANNEL_FADING_RAYLEIGH, CHANNEL_FADING_RICIAN = 0, 1, 2
+# d2d_queue_step's limits (include/d2d_queue.h)
+QUEUE_MAX_DEADLINE, QUEUE_TABLE = 32, 64
 
 BUFFER_DTYPES = {BUF_ACTIONS: np.int32, BUF_RB: np.int32, BUF_PWR: np.int32, BUF_ENV_FLAGS: np.int32, BUF_RESET_PENDING: np.int32,
                  BUF_EPISODE: np.uint32}
@@ -185,6 +188,13 @@ CHANNEL_SIGNATURES = {
     'd2d_channel_last_error': (C.c_char_p, []),
 }
 
+# every symbol include/d2d_queue.h declares
+QUEUE_SIGNATURES = {
+    'd2d_queue_step': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _I, _I, _I, C.c_int64, C.c_int64, C.c_double,
+                                 C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _P, _P, _P, _P, _P]),
+    'd2d_queue_last_error': (C.c_char_p, []),
+}
+
 _lib: Optional[C.CDLL] = None
 _plugin: Optional[C.CDLL] = None
 _episode: Optional[C.CDLL] = None
@@ -198,6 +208,8 @@ _mobility: Optional[C.CDLL] = None
 mobility_launches = 0               # d2d_mobility_move calls made through mobility_move() in this process
 _channel: Optional[C.CDLL] = None
 channel_launches = 0                # d2d_channel_fill calls made through channel_fill() in this process
+_queue: Optional[C.CDLL] = None
+queue_launches = 0                  # d2d_queue_step calls made through queue_step() in this process
 
 
 def load_library() -> C.CDLL:
@@ -460,6 +472,46 @@ def channel_fill(pos_x_ptr: int, pos_y_ptr: int, link_tx_ptr: int, link_rx_ptr: 
     if rc != 0:
         raise NativeError(rc, lib.d2d_channel_last_error().decode(errors='replace'))
     channel_launches += 1
+
+
+def load_queue_library() -> C.CDLL:
+    """dlopen libd2d_queue.so and type its entry points.  Raises if it has not been built."""
+    global _queue
+    if _queue is not None:
+        return _queue
+    if not QUEUE_PATH.exists():
+        raise ImportError(f'{QUEUE_PATH} is missing - build it with `python -m gym_d2d_amd.build`')
+    lib = C.CDLL(str(QUEUE_PATH))
+    for name, (res, args) in QUEUE_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    _queue = lib
+    return lib
+
+
+def queue_step(capacity_ptr: int, ring_ptr: int, arrived_ptr: int, served_ptr: int, expired_ptr: int, overflow_ptr: int, backlog_ptr: int,
+               hol_age_ptr: int, mean_delay_ptr: int, on_ptr: int, thresholds: np.ndarray, n_envs: int, n_cues: int, n_due_pairs: int,
+               deadline_steps: int, packet_bits: int, buffer_bits: int, bits_per_mbps_step: float, p_on_to_off: int, p_off_to_on: int,
+               p_start_on: int, first_env: int, seed: int, step: int = 0, episode: int = 0, elapsed_ptr: int = 0, start_ptr: int = 0,
+               episode_ptr: int = 0, reset_ptr: int = 0, stream_ptr: int = 0) -> None:
+    """d2d_queue_step: one step of the packet queues behind the capacity plane [n_envs, n_links] (device pointers; `thresholds` is a
+    host uint32 [2, 64] array), or the start of an episode (step 0); reset_ptr != 0: the per-env clock of the four [n_envs] arrays."""
+    global queue_launches
+    lib = load_queue_library()
+    tab = np.ascontiguousarray(thresholds, dtype=np.uint32)
+    if tab.shape != (2, QUEUE_TABLE):
+        raise ValueError(f'thresholds must be uint32 [2, {QUEUE_TABLE}], got {tab.shape}')
+    rc = lib.d2d_queue_step(_P(capacity_ptr or None), _P(ring_ptr or None), _P(arrived_ptr or None), _P(served_ptr or None),
+                            _P(expired_ptr or None), _P(overflow_ptr or None), _P(backlog_ptr or None), _P(hol_age_ptr or None),
+                            _P(mean_delay_ptr or None), _P(on_ptr or None), _P(tab.ctypes.data), n_envs, n_cues, n_due_pairs,
+                            deadline_steps, packet_bits, buffer_bits, bits_per_mbps_step, p_on_to_off, p_off_to_on, p_start_on,
+                            C.c_uint64(first_env), C.c_uint64(seed & (2 ** 64 - 1)), step & 0xFFFFFFFF, episode & 0xFFFFFFFF,
+                            _P(elapsed_ptr or None), _P(start_ptr or None), _P(episode_ptr or None), _P(reset_ptr or None),
+                            _P(stream_ptr or None))
+    if rc != 0:
+        raise NativeError(rc, lib.d2d_queue_last_error().decode(errors='replace'))
+    queue_launches += 1
 
 
 def _check(rc: int) -> None:

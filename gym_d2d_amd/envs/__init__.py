@@ -2,7 +2,8 @@
 `gym_d2d_amd.envs.env_config` without dragging in d2d_env (which imports the simulator) - the reference has exactly
 this cycle and fails on `import gym_d2d.simulator` first."""
 
-__all__ = ['D2DEnv', 'VecD2DEnv', 'RbSensingObsFunction', 'NeighborObsFunction', 'DifferenceRewardFunction']
+__all__ = ['D2DEnv', 'VecD2DEnv', 'RbSensingObsFunction', 'NeighborObsFunction', 'DifferenceRewardFunction', 'QueueObsFunction',
+           'GoodputRewardFunction']
 
 
 def __getattr__(name):
@@ -21,4 +22,10 @@ def __getattr__(name):
     if name == 'DifferenceRewardFunction':
         from .reward_fn import DifferenceRewardFunction
         return DifferenceRewardFunction
+    if name == 'QueueObsFunction':
+        from .obs_fn import QueueObsFunction
+        return QueueObsFunction
+    if name == 'GoodputRewardFunction':
+        from .reward_fn import GoodputRewardFunction
+        return GoodputRewardFunction
     raise AttributeError(name)

@@ -132,3 +132,22 @@ class NeighborObsFunction(ArrayObsFunction):
 
     def compute(self, view):
         return view.neighbor_obs
+
+
+class QueueObsFunction(ArrayObsFunction):
+    """Each agent observes its own link and its own packet queue (VecD2DEnv(traffic=PacketTraffic(...)), csrc/d2d_queue.hip), width 6:
+    [B, N, 6] float32 = (sinr_dB, snr_dB, capacity_mbps, backlog_bits / buffer_bits, hol_age_steps / deadline_steps, on).  The two
+    ratios are formed in float64 and rounded once.  `needs_traffic` makes an env without traffic= refuse it at construction."""
+    native_mode = _native.OBS_NONE
+    needs_traffic = True
+
+    def get_obs_space(self, env_config) -> Space:
+        return Box(low=-np.inf, high=np.inf, shape=(6,))
+
+    def compute(self, view):
+        m = view.traffic
+        import torch
+        f32 = torch.float32
+        fill = (view.backlog_bits.to(torch.float64) / float(max(m.buffer_bits, 1))).to(f32)
+        age = (view.hol_age_steps.to(torch.float64) / float(m.deadline_steps)).to(f32)
+        return torch.stack([view.sinr_db, view.snr_db, view.capacity_mbps, fill, age, view.on.to(f32)], dim=-1)

@@ -1,7 +1,8 @@
 """Reward plugins (mirrors gym_d2d/envs/reward_fn.py).  The three built-ins are evaluated inside the HIP step
 kernel (csrc/d2d_step.hip, pass 3); `native_id` / `native_param` select the branch.  Calling a built-in with a
 NativeState just re-keys the kernel's per-agent output.  A user subclass that overrides __call__ runs as Python.
-DifferenceRewardFunction is the array-native one: VecD2DEnv hands it the planes of csrc/d2d_marginal.hip."""
+DifferenceRewardFunction and GoodputRewardFunction are the array-native ones: VecD2DEnv hands them the planes of csrc/d2d_marginal.hip
+and csrc/d2d_queue.hip."""
 from __future__ import annotations
 
 from abc import ABC, abstractmethod
@@ -88,3 +89,22 @@ class DifferenceRewardFunction(RewardFunction):
     def __call__(self, actions, state):
         raise RuntimeError('DifferenceRewardFunction is computed from the batched planes of VecD2DEnv (marginal_capacity()); the '
                            'single-env dict D2DEnv does not serve it')
+
+
+class GoodputRewardFunction(RewardFunction):
+    """Delivered traffic per link in Mbps, less what was lost: (served_bits - drop_penalty * (expired_bits + overflow_bits)) /
+    (1e6 * dt_s), float32 [B, N], formed in float64 and rounded once (VecD2DEnv(traffic=PacketTraffic(...)), csrc/d2d_queue.hip).
+    A subclass sets another `drop_penalty`.  VecD2DEnv only; `needs_traffic` makes an env without traffic= refuse it at construction."""
+    native_id = _native.REWARD_NONE
+    needs_traffic = True
+    drop_penalty = 1.0
+
+    def compute(self, view):
+        import torch
+        f64 = torch.float64
+        lost = view.expired_bits.to(f64) + view.overflow_bits.to(f64)
+        return ((view.served_bits.to(f64) - float(self.drop_penalty) * lost) / view.traffic.bits_per_mbps_step).to(torch.float32)
+
+    def __call__(self, actions, state):
+        raise RuntimeError('GoodputRewardFunction is computed from the queue planes of VecD2DEnv(traffic=...); the single-env dict '
+                           'D2DEnv does not serve it')

@@ -24,6 +24,7 @@ import numpy as np
 
 from .. import _native, graph, marginal, sensing
 from .. import mobility as mobility_mod
+from .. import queues as queues_mod
 from ..path_loss_table import CHANNEL, PER_STEP, positions_move_unserved
 from ..simulator import BASE_STATION_ID, Simulator
 from ..traffic_model import DownlinkTrafficModel
@@ -46,7 +47,7 @@ class VecD2DEnv:
                  cue_actions: str = 'agent', use_torch: Optional[bool] = None, first_env: int = 0,
                  export_actions: bool = True, reward_per_env: bool = False, placement_trials: int = 0,
                  placement_budget_bytes: int = 1 << 30, autoreset: bool = False, mobility=None,
-                 neighbor_refresh: int = 1) -> None:
+                 neighbor_refresh: int = 1, traffic=None) -> None:
         """cue_actions: 'agent' - step() takes actions for CUEs and DUEs [B, C+P] (reference behaviour);
         'traffic' - CUE links follow the env's traffic model (round-robin RB at max power,
         traffic_model.py:15-22): their (rb, pwr) are constants of the kernel's link records
@@ -101,6 +102,17 @@ class VecD2DEnv:
         every neighbor_refresh-th step() call since reset() (default 1: every step; between refreshes the lists are the last
         refresh's, and under autoreset the envs a step reset still get theirs at once).
         One d2d_graph_neighbors launch per refresh - profiles/mobility_cost.jsonl has its cost.
+
+        traffic: a gym_d2d_amd.queues.PacketTraffic - finite-buffer packet traffic with deadlines behind every link
+        (csrc/d2d_queue.hip, one launch per step, right after the step kernel): an on/off source with Poisson arrivals, tail drop, a
+        deadline of D steps and oldest-first service by what this step's capacity_mbps carries in dt_s.  reset() starts the episode
+        behind the reset's own step (cleared rings, zero planes; that step serves nothing), step() queues behind d2d_step; under
+        autoreset=True an env that is reset inside a step shows zero planes and a cleared ring in that step.  The draws are keyed by
+        (global env index, episode, step in the episode, link): sharding and autoreset reproduce the lockstep single-GPU run bit for
+        bit.  queues() returns the planes; the view carries them (view.backlog_bits, ...) and the model (view.traffic), and info
+        gains served_bits, backlog_bits, expired_bits and overflow_bits.  A link whose buffer is empty still transmits: the step
+        kernel has no off state.  None (default): nothing is loaded, allocated or launched.  Needs the torch path (ValueError); any
+        path-loss route serves it, since it only reads capacity_mbps.
 
         env_config['obs_dtype'] = 'float64' returns observations in the reference's dtype (obs_fn.py:51 builds float64
         arrays); the default float32 is the kernels' own block, zero copy.
@@ -180,6 +192,17 @@ class VecD2DEnv:
             why = mobility_mod.refusal(sim, self.use_torch)
             if why:
                 raise ValueError(why)
+        if traffic is not None:
+            if not isinstance(traffic, queues_mod.PacketTraffic):
+                raise TypeError(f'traffic must be a PacketTraffic or None, got {type(traffic).__name__}')
+            why = queues_mod.refusal(self.use_torch)
+            if why:
+                raise ValueError(why)
+        else:
+            for fn, what in ((self.obs_fn, 'obs function'), (self.reward_fn, 'reward function')):
+                if getattr(fn, 'needs_traffic', False):
+                    raise ValueError(f'{type(fn).__name__} needs traffic=: this env has no packet queues for the {what} to read '
+                                     '(VecD2DEnv(traffic=PacketTraffic(...)))')
         self._t = {}
         if self.use_torch:
             self._bind_torch_buffers()
@@ -212,6 +235,15 @@ class VecD2DEnv:
             sim.path_loss_table.device_resets = True           # a per-step ArrayPathLoss gathers the coordinates before every step
             self._mobility = mobility_mod.Mobility(mobility, sim, torch, self.device, self.first_env, self.autoreset)
             self._t['vel_x'], self._t['vel_y'] = self._mobility.vel_x, self._mobility.vel_y
+            self._view_cache = None
+        # packet traffic: likewise nothing is loaded, allocated or launched unless a model is given
+        self._queues = None
+        if traffic is not None:
+            self._queues = queues_mod.Queues(traffic, self.num_envs, self.num_cues, self.num_due_pairs, torch, self.device,
+                                             self.first_env, self.autoreset)
+            for name in queues_mod.PLANES:
+                self._t[name] = getattr(self._queues, name)
+            self._t['traffic'] = traffic
             self._view_cache = None
         # per-RB sensing (sense()): nothing is built, allocated or launched unless sense() is called or the obs function asks
         self._sensor = None
@@ -332,6 +364,8 @@ class VecD2DEnv:
             self._view_cache = view
             self._info = {'rb': view.rb, 'tx_pwr_dbm': view.pwr, 'snr_db': view.snr_db, 'sinr_db': view.sinr_db,
                           'rate_bps': view.rate_bps, 'capacity_mbps': view.capacity_mbps}
+            if self._queues is not None:
+                self._info.update({k: v[k] for k in ('served_bits', 'backlog_bits', 'expired_bits', 'overflow_bits')})
         return view
 
     # ------------------------------------------------------------------ gym-like API
@@ -390,6 +424,8 @@ class VecD2DEnv:
                 self.simulator.path_loss_table.channel.start_episode(self._t['elapsed'])
         if self._mobility is not None:                        # behind the sampler; the reset's own step did not see a move
             self._mobility.start_episode(self._t, self._seed, self._episode - 1, self._stream_ptr)
+        if self._queues is not None:                          # t = 0 behind the reset's step, which serves nothing
+            self._queues.start_episode(self._t, self._seed, self._episode - 1, self._stream_ptr)
         self.simulator.check_flags()
         if self._placement_trials > 1 and self.placement is None:
             self._choose_obs_placement(self._placement_trials)
@@ -494,6 +530,8 @@ class VecD2DEnv:
             else:
                 self._t['actions'].copy_(src)
                 sim.handle.step()
+            if self._queues is not None:
+                self._queues.step(self._t, self._seed, self.num_steps + 1, self._episode - 1, self._stream_ptr)
         else:
             src = np.asarray(actions, dtype=np.int32)
             if src.shape != (self.num_envs, self.num_agents):
@@ -537,6 +575,8 @@ class VecD2DEnv:
             _native.episode_merge_actions(src.data_ptr(), t['actions'].data_ptr(), t['pending'].data_ptr(), t['episode'].data_ptr(),
                                           t['high'].data_ptr(), self.num_envs, self.num_agents, self.first_env, self._seed, stream)
         h.step()
+        if self._queues is not None:                          # before episode_advance: the clock is the move's
+            self._queues.step_per_env(t, self._seed, stream)
         self.num_steps += 1
         view = self._view()
         native = self._native_reward
@@ -575,6 +615,14 @@ class VecD2DEnv:
         if self._mobility is None:
             raise ValueError('velocities() needs mobility=: this env\'s devices stand still between resets')
         return self._mobility.vel_x, self._mobility.vel_y
+
+    def queues(self):
+        """The packet queues' planes as a namespace (traffic= only): arrived_bits, served_bits, expired_bits, overflow_bits,
+        backlog_bits, hol_age_steps int32, mean_delay_steps float32, on uint8, all [B, N], and ring int32 [D, B, N] - the env's own
+        tensors, updated in place by every step (clone them to keep a step's values)."""
+        if self._queues is None:
+            raise ValueError('queues() needs traffic=: this env\'s links are full-buffer')
+        return self._queues.planes()
 
     def request_reset(self, mask) -> None:
         """Reset the envs mask marks (bool [B], tensor or ndarray) at the next step() instead of stepping them - device-side and
