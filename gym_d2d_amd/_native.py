@@ -1,6 +1,7 @@
 """ctypes binding of libd2d_hip.so (include/d2d_hip.h), libd2d_plugin.so (include/d2d_plugin.h), libd2d_episode.so
 (include/d2d_episode.h), libd2d_sense.so (include/d2d_sense.h), libd2d_graph.so (include/d2d_graph.h), libd2d_marginal.so (include/d2d_marginal.h), libd2d_mobility.so
-(include/d2d_mobility.h), libd2d_channel.so (include/d2d_channel.h) and libd2d_queue.so (include/d2d_queue.h).  There is no CPU fallback: if a library or a gfx950 GPU is missing, the calls below raise."""
+(include/d2d_mobility.h), libd2d_channel.so (include/d2d_channel.h), libd2d_queue.so (include/d2d_queue.h) and libd2d_bestrb.so
+(include/d2d_bestrb.h).  There is no CPU fallback: if a library or a gfx950 GPU is missing, the calls below raise."""
 from __future__ import annotations
 
 import ctypes as C
@@ -18,6 +19,7 @@ MARGINAL_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_marginal.so'
 MOBILITY_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_mobility.so'
 CHANNEL_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_channel.so'
 QUEUE_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_queue.so'
+BESTRB_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_bestrb.so'
 ABI_VERSION = 7
 MAX_LINKS = 2048
 
@@ -61,6 +63,9 @@ MARGINAL_MAX_RBS = 8192
 CHANNEL_FADING_NONE, CHANNEL_FADING_RAYLEIGH, CHANNEL_FADING_RICIAN = 0, 1, 2
 # d2d_queue_step's limits (include/d2d_queue.h)
 QUEUE_MAX_DEADLINE, QUEUE_TABLE = 32, 64
+# d2d_best_rb's law / limits (include/d2d_bestrb.h): the sensing kernel's
+BESTRB_LAW_INV_SQUARE, BESTRB_LAW_POWER, BESTRB_LAW_POW_K = 0, 1, 2
+BESTRB_MAX_RBS = 8192
 
 BUFFER_DTYPES = {BUF_ACTIONS: np.int32, BUF_RB: np.int32, BUF_PWR: np.int32, BUF_ENV_FLAGS: np.int32, BUF_RESET_PENDING: np.int32,
                  BUF_EPISODE: np.uint32}
@@ -195,6 +200,12 @@ QUEUE_SIGNATURES = {
     'd2d_queue_last_error': (C.c_char_p, []),
 }
 
+# every symbol include/d2d_bestrb.h declares
+BESTRB_SIGNATURES = {
+    'd2d_best_rb': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, C.c_int64, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    'd2d_bestrb_last_error': (C.c_char_p, []),
+}
+
 _lib: Optional[C.CDLL] = None
 _plugin: Optional[C.CDLL] = None
 _episode: Optional[C.CDLL] = None
@@ -204,6 +215,8 @@ _graph: Optional[C.CDLL] = None
 graph_launches = {'coupling': 0, 'neighbors': 0, 'neighbor_obs': 0}     # launches made through the graph_*() wrappers in this process
 _marginal: Optional[C.CDLL] = None
 marginal_launches = 0               # d2d_marginal_capacity calls made through marginal_capacity() in this process
+_bestrb: Optional[C.CDLL] = None
+bestrb_launches = 0                 # d2d_best_rb calls made through best_rb() in this process
 _mobility: Optional[C.CDLL] = None
 mobility_launches = 0               # d2d_mobility_move calls made through mobility_move() in this process
 _channel: Optional[C.CDLL] = None
@@ -401,6 +414,39 @@ def marginal_capacity(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int,
     if rc != 0:
         raise NativeError(rc, lib.d2d_marginal_last_error().decode(errors='replace'))
     marginal_launches += 1
+
+
+def load_bestrb_library() -> C.CDLL:
+    """dlopen libd2d_bestrb.so and type its entry points.  Raises if it has not been built."""
+    global _bestrb
+    if _bestrb is not None:
+        return _bestrb
+    if not BESTRB_PATH.exists():
+        raise ImportError(f'{BESTRB_PATH} is missing - build it with `python -m gym_d2d_amd.build`')
+    lib = C.CDLL(str(BESTRB_PATH))
+    for name, (res, args) in BESTRB_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    _bestrb = lib
+    return lib
+
+
+def best_rb(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, link_tx_ptr: int, link_rx_ptr: int, cols_ptr: int, law: int,
+            pow_k: int, n_envs: int, n_dev: int, n_links: int, n_rbs: int, allowed_ptr: int, env_mask_ptr: int, best_rb_ptr: int,
+            best_sinr_ptr: int, gain_ptr: int, stream_ptr: int = 0) -> None:
+    """d2d_best_rb: every link's best RB (int32), the SINR there and the gain over its own RB (dB) into three planes [n_envs, n_links]
+    (device pointers; allowed_ptr 0: every RB, else uint32 [n_links, ceil(n_rbs / 32)]; env_mask_ptr 0: every env, else uint8
+    [n_envs] and the envs whose byte is 0 keep their rows)."""
+    global bestrb_launches
+    lib = load_bestrb_library()
+    rc = lib.d2d_best_rb(_P(pos_x_ptr or None), _P(pos_y_ptr or None), _P(rb_ptr or None), _P(pwr_ptr or None), _P(link_tx_ptr or None),
+                         _P(link_rx_ptr or None), _P(cols_ptr or None), law, pow_k, n_envs, n_dev, n_links, n_rbs,
+                         _P(allowed_ptr or None), _P(env_mask_ptr or None), _P(best_rb_ptr or None), _P(best_sinr_ptr or None),
+                         _P(gain_ptr or None), _P(stream_ptr or None))
+    if rc != 0:
+        raise NativeError(rc, lib.d2d_bestrb_last_error().decode(errors='replace'))
+    bestrb_launches += 1
 
 
 def load_mobility_library() -> C.CDLL:

@@ -1,0 +1,121 @@
+"""Best-response RB selection: the host side of libd2d_bestrb.so (include/d2d_bestrb.h, csrc/d2d_bestrb.hip).
+
+`BestRb` owns the device-side constants of one env object (link lists, the columns sensing.fold_columns folds, unchanged) and launches
+the kernel on torch's device pointers.  `pack_allowed` lowers a bool [N, R] mask to the kernel's words, `encode_actions` turns the
+kernel's planes into the action tensor VecD2DEnv.step() takes.  Torch path only.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+
+from . import _native
+from .sensing import fold_columns, unserved
+
+
+def refusal(sim, export_actions: bool, use_torch: bool = True) -> Optional[str]:
+    """Why this env has no best_rb() (None: it has): the predicate of sensing.unserved under texts of its own."""
+    if not use_torch:
+        return 'best_rb() needs the torch path (use_torch): its planes are device tensors'
+    why = unserved(sim, export_actions)
+    if why is None:
+        return None
+    kind, route = why
+    return {
+        'export_actions': 'best_rb() reads the decoded (rb, tx power) planes, which export_actions=False does not write: build the '
+                          'env with export_actions=True',
+        'route': f"best_rb() does not serve the '{route}' path-loss route (a table, not a law its kernel can evaluate for the pairs "
+                 'no step reads); it serves the native power-law models',
+        'shadowing': 'best_rb() does not serve ShadowingPathLoss: a fresh draw per evaluation has no counterfactual (what another RB '
+                     'would have given is another draw)',
+        'pinned': 'best_rb() does not serve pinned device_config coordinates that float32 cannot hold: their low parts live inside '
+                  'the handle (float64 positions)',
+    }[kind]
+
+
+def pack_allowed(mask, xp=np):
+    """bool [N, R] (link i may choose RB r) -> the kernel's words [N, ceil(R / 32)]: bit r & 31 of word r // 32.  NumPy: uint32;
+    torch (xp=torch): int32 holding the same bits, on the mask's device."""
+    n, r = mask.shape
+    words = (r + 31) // 32
+    if xp is np:
+        bits = np.zeros((n, words * 32), dtype=np.uint64)
+        bits[:, :r] = np.asarray(mask, dtype=bool)
+        return (bits.reshape(n, words, 32) << np.arange(32, dtype=np.uint64)).sum(axis=2).astype(np.uint32)
+    bits = xp.zeros((n, words * 32), dtype=xp.int64, device=mask.device)
+    bits[:, :r] = mask.to(xp.int64)
+    word = (bits.view(n, words, 32) << xp.arange(32, dtype=xp.int64, device=mask.device)).sum(dim=2)
+    return xp.where(word >= 1 << 31, word - (1 << 32), word).to(xp.int32)
+
+
+def encode_actions(rb, pwr, best_rb, gain_db, levels, min_gain_db: float, first_agent: int = 0):
+    """The action array [B, num_agents] that moves every agent link whose gain_db > min_gain_db to best_rb at its current power level
+    and repeats the last action of every other one: rb * levels + power level, the env's own layout (d2d_env.py:94-96).  rb, pwr,
+    best_rb, gain_db: [B, N] (the decoded planes and the kernel's); levels: int [num_agents], the power levels of every agent
+    link's class; the agents are links first_agent .. first_agent + num_agents - 1 (links on fixed actions come first and have no
+    column).  NaN gains (no allowed RB, an own rb outside [0, R)) compare false: such links repeat their last action.  NumPy arrays
+    or torch tensors alike; the result is int32."""
+    n = first_agent + levels.shape[0]
+    rb, pwr, best_rb, gain_db = (a[:, first_agent:n] for a in (rb, pwr, best_rb, gain_db))
+    move = gain_db > min_gain_db
+    if isinstance(move, np.ndarray):
+        return (np.where(move, best_rb, rb) * levels + pwr).astype(np.int32)
+    import torch
+    return (torch.where(move, best_rb, rb) * levels + pwr).to(torch.int32)
+
+
+class BestRb:
+    """The best-response kernel bound to one env object: constants uploaded once, one launch per call."""
+
+    def __init__(self, sim, num_links: int, torch, device) -> None:
+        from .device import link_budget_columns
+        self.sim, self.torch, self.device = sim, torch, device
+        h = sim.handle
+        self.b, self.d, self.n, self.r = sim.num_envs, h.num_devices, int(num_links), int(sim.config.num_rbs)
+        if self.r > _native.BESTRB_MAX_RBS:
+            raise ValueError(f'best_rb() serves at most {_native.BESTRB_MAX_RBS} RBs (num_rbs = {self.r})')
+        tx, rx = np.asarray(sim.link_tx, dtype=np.int32), np.asarray(sim.link_rx, dtype=np.int32)
+        if len(tx) != self.n or tx.min() < 0 or tx.max() >= self.d or rx.min() < 0 or rx.max() >= self.d:
+            raise ValueError('the link list does not match the env')
+        cols, self.law, self.pow_k = fold_columns(link_budget_columns(sim._dev_list), sim.path_loss_table.law, tx)
+        self.own = None                              # the three planes this object owns, allocated by the first call without out=
+        self.tx, self.rx, self.cols = (torch.as_tensor(a, device=device) for a in (tx, rx, cols))
+        self.ptrs = tuple(t.data_ptr() for t in (self.tx, self.rx, self.cols))
+
+    def words(self, allowed):
+        """None, or the packed words of `allowed` (bool [N, R], tensor or array) as an int32 tensor on the device."""
+        if allowed is None:
+            return None
+        torch = self.torch
+        mask = torch.as_tensor(allowed, device=self.device) if not torch.is_tensor(allowed) else allowed.to(self.device)
+        if tuple(mask.shape) != (self.n, self.r) or mask.dtype != torch.bool:
+            raise ValueError(f'allowed must be bool [{self.n}, {self.r}] (link, RB) or None')
+        return pack_allowed(mask, torch).contiguous()
+
+    def planes(self, t: dict, allowed, out, stream: int, env_mask=None):
+        torch = self.torch
+        shape = (self.b, self.n)
+        if out is None:
+            if self.own is None:
+                self.own = (torch.empty(shape, dtype=torch.int32, device=self.device),
+                            torch.empty(shape, dtype=torch.float32, device=self.device),
+                            torch.empty(shape, dtype=torch.float32, device=self.device))
+            out = self.own
+        else:
+            ok = isinstance(out, (tuple, list)) and len(out) == 3 and all(
+                torch.is_tensor(o) and tuple(o.shape) == shape and o.dtype == dt and o.is_contiguous() and o.device == self.device
+                for o, dt in zip(out, (torch.int32, torch.float32, torch.float32)))
+            if not ok or len({o.data_ptr() for o in out}) != 3:
+                raise ValueError(f'out must be (best_rb, best_sinr_db, gain_db): contiguous int32, float32, float32 tensors {list(shape)} '
+                                 f'on {self.device} that do not share memory')
+            out = tuple(out)
+        words = self.words(allowed)                  # lives until the launch is enqueued; the stream orders its release behind it
+        best, sinr, gain = out
+        _native.best_rb(t['pos_x'].data_ptr(), t['pos_y'].data_ptr(), t['rb'].data_ptr(), t['pwr'].data_ptr(), *self.ptrs, self.law,
+                        self.pow_k, self.b, self.d, self.n, self.r, 0 if words is None else words.data_ptr(),
+                        0 if env_mask is None else env_mask.data_ptr(), best.data_ptr(), sinr.data_ptr(), gain.data_ptr(), stream)
+        return best, sinr, gain
+
+    def close(self) -> None:
+        pass

@@ -3,7 +3,7 @@
 this cycle and fails on `import gym_d2d.simulator` first."""
 
 __all__ = ['D2DEnv', 'VecD2DEnv', 'RbSensingObsFunction', 'NeighborObsFunction', 'DifferenceRewardFunction', 'QueueObsFunction',
-           'GoodputRewardFunction']
+           'GoodputRewardFunction', 'BestRbObsFunction']
 
 
 def __getattr__(name):
@@ -28,4 +28,7 @@ def __getattr__(name):
     if name == 'GoodputRewardFunction':
         from .reward_fn import GoodputRewardFunction
         return GoodputRewardFunction
+    if name == 'BestRbObsFunction':
+        from .obs_fn import BestRbObsFunction
+        return BestRbObsFunction
     raise AttributeError(name)

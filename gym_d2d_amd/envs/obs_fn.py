@@ -56,10 +56,13 @@ class ArrayObsFunction(ABC):
     for it; without the attribute nothing is launched or allocated.  A subclass that sets `needs_neighbors = k` (1 .. min(N - 1, 64))
     also gets neighbor_idx int32 [B,N,k] and neighbor_coupling_db float32 [B,N,k], every link's k strongest interferers
     (VecD2DEnv.neighbors: receiver-major, row [b, i] belongs to the RECEIVING link i, strongest first): selected at reset() and for
-    the envs an autoreset step reset, never per step; without the attribute nothing is built, allocated or launched."""
+    the envs an autoreset step reset, never per step; without the attribute nothing is built, allocated or launched.  A subclass that
+    sets `needs_best_rb = True` also gets best_rb int32, best_sinr_db and gain_db float32 [B,N] (VecD2DEnv.best_rb: one launch of
+    csrc/d2d_bestrb.hip behind every step and reset); without the attribute nothing is loaded, allocated or launched."""
     native_mode = _native.OBS_TABLE
     needs_rb_sensing = False
     needs_neighbors = 0
+    needs_best_rb = False
 
     @abstractmethod
     def get_obs_space(self, env_config) -> Space:
@@ -109,6 +112,22 @@ class RbSensingObsFunction(ArrayObsFunction):
 
     def compute(self, view):
         return view.rb_sinr_db
+
+
+class BestRbObsFunction(ArrayObsFunction):
+    """Each agent observes where it would be best off and by how much, width 3: [B, N, 3] float32 = (best_rb, best_sinr_dB, gain_dB) of
+    VecD2DEnv.best_rb(), evaluated by csrc/d2d_bestrb.hip behind every step - the RB on which the link would see the highest SINR if it
+    alone moved there, that SINR, and what the move would gain over its own RB (0.0: it already sits there).  Width 3 instead of
+    RbSensingObsFunction's R, and no [B, N, R] block behind it.  A fresh tensor per call."""
+    native_mode = _native.OBS_NONE
+    needs_best_rb = True
+
+    def get_obs_space(self, env_config) -> Space:
+        return Box(low=-np.inf, high=np.inf, shape=(3,))
+
+    def compute(self, view):
+        import torch
+        return torch.stack([view.best_rb.to(torch.float32), view.best_sinr_db, view.gain_db], dim=-1)
 
 
 class NeighborObsFunction(ArrayObsFunction):

@@ -22,7 +22,7 @@ from typing import Optional
 
 import numpy as np
 
-from .. import _native, graph, marginal, sensing
+from .. import _native, best_response, graph, marginal, sensing
 from .. import mobility as mobility_mod
 from .. import queues as queues_mod
 from ..path_loss_table import CHANNEL, PER_STEP, positions_move_unserved
@@ -263,6 +263,13 @@ class VecD2DEnv:
         self._wants_marginal = self._obs_marginal or bool(getattr(self.reward_fn, 'needs_marginal', False))
         if self._wants_marginal:
             self._marginal_kernel()                # refusals surface here, not inside the first step
+        # best-response RB selection (best_rb()): likewise nothing unless it is called or the obs / reward function asks
+        self._bestrb = None
+        self._action_levels = None                 # best_response_actions(): the power levels of every agent link's class
+        self._obs_best_rb = bool(getattr(self.obs_fn, 'needs_best_rb', False)) and self._array_obs
+        self._wants_best_rb = self._obs_best_rb or bool(getattr(self.reward_fn, 'needs_best_rb', False))
+        if self._wants_best_rb:
+            self._best_rb_kernel()                 # refusals surface here, not inside the first step
 
     def _setup_autoreset(self) -> None:
         """Refuse what a device-side per-env reset cannot serve, then allocate the per-env bookkeeping: pending / episode are bound
@@ -432,7 +439,11 @@ class VecD2DEnv:
         if self._neighbors_k:
             self._select_neighbors()
         view = self._view()
-        return self._observe(self._with_marginal(view) if self._obs_marginal else view)
+        if self._obs_marginal:
+            view = self._with_marginal(view)
+        if self._obs_best_rb:
+            view = self._with_best_rb(view)
+        return self._observe(view)
 
     def _choose_obs_placement(self, trials: int, warm_ms: float = 15.0, steps: int = 256) -> None:
         """Time the step on up to `trials` candidate blocks for the dominant output (all held until the choice, hence distinct
@@ -543,6 +554,8 @@ class VecD2DEnv:
         view = self._view()
         if self._wants_marginal:
             view = self._with_marginal(view)
+        if self._wants_best_rb:
+            view = self._with_best_rb(view)
         obs = self._observe(view)
         rewards = view.reward if self._native_reward else self.reward_fn.compute(view)
         done = self.num_steps >= EPISODE_LENGTH
@@ -589,6 +602,8 @@ class VecD2DEnv:
             self._select_neighbors(None if refresh else t['reset'])   # the envs this step reset stand at new positions; moved: all
         if self._wants_marginal:
             view = self._with_marginal(view)                  # after the step: the envs it reset at their new positions and actions
+        if self._wants_best_rb:
+            view = self._with_best_rb(view)                   # likewise: one launch behind the step serves every env
         obs = self._observe(view)
         if native:
             rewards = view.reward
@@ -765,6 +780,58 @@ class VecD2DEnv:
         diff, harm = self.marginal_capacity()
         return SimpleNamespace(**vars(view), difference_mbps=diff, harm_mbps=harm)
 
+    # ------------------------------------------------------------------ best-response RB selection
+    def _best_rb_kernel(self):
+        if self._bestrb is None:
+            why = best_response.refusal(self.simulator, self.export_actions, self.use_torch)
+            if why:
+                raise ValueError(why)
+            self._bestrb = best_response.BestRb(self.simulator, self.num_links, torch, self.device)
+        return self._bestrb
+
+    def best_rb(self, allowed=None, out=None):
+        """Where every link would be best off, with everything else as the last step left it: (best_rb int32, best_sinr_db float32,
+        gain_db float32), each [B, N].
+
+        best_rb[b, i] is the RB on which link i would see the highest SINR if it alone moved there at its current power - the argmax
+        over r of sense('sinr_db')[b, i, r], equal values (RBs nobody else uses) to the lowest r - best_sinr_db that SINR, a value
+        of the sensed block bit for bit, and gain_db = best_sinr_db - sinr_db: what the move would gain, 0.0 exactly for a link that
+        already sits on its best RB.  One kernel launch (csrc/d2d_bestrb.hip) that keeps a running best in registers: no [B, N, R]
+        block is written or read.  Valid after reset() and after every step(), autoreset steps included, as sense() is.
+
+        allowed: bool [N, R] (tensor or array), allowed[i, r] = link i may choose RB r; None: every RB.  A link with no allowed RB
+        gets best_rb -1 and NaN values; a link whose own RB is not allowed still gets a finite (possibly negative) gain_db.
+
+        Torch path only: enqueued on torch's current stream, nothing is synchronised; the three tensors the env owns, rewritten by
+        every call (clone them to keep them), or `out` = (best_rb, best_sinr_db, gain_db), contiguous int32 / float32 / float32
+        [B, N] on the env's device.  Serves what sense() serves; ValueError for export_actions=False, ShadowingPathLoss, every table
+        route, pinned device_config coordinates float32 cannot hold."""
+        k = self._best_rb_kernel()
+        self._follow_torch_stream()
+        return k.planes(self._t, allowed, out, self._stream_ptr)
+
+    def best_response_actions(self, allowed=None, min_gain_db: float = 0.0):
+        """One round of best response as an action tensor, int32 [B, num_agents], ready for step(): every agent link whose
+        gain_db > min_gain_db moves to its best_rb() at its current power level, every other one repeats its last action (as the
+        decoded planes hold it), encoded rb * power levels + level.  Links on fixed actions (cue_actions='traffic') have no column
+        and are never moved; `allowed` as best_rb() takes it.  All links moving at once can chase each other onto the same quiet
+        RBs: a min_gain_db above 0, or an `allowed` mask that lets a part of the links move per round, damps that."""
+        if not np.isfinite(min_gain_db) or min_gain_db < 0.0:
+            raise ValueError(f'min_gain_db must be a finite number >= 0, got {min_gain_db!r}')
+        best, _, gain = self.best_rb(allowed)
+        if self._action_levels is None:
+            p = self.num_pwr_actions
+            levels = ([p[self._cue_kind]] * self.num_cues if self.cue_actions == 'agent' else []) + [p['due']] * self.num_due_pairs
+            self._action_levels = torch.as_tensor(np.asarray(levels, dtype=np.int32), device=self.device)
+        return best_response.encode_actions(self._t['rb'], self._t['pwr'], best, gain, self._action_levels, float(min_gain_db),
+                                            self.num_links - self.num_agents)
+
+    def _with_best_rb(self, view):
+        """The view plus best_rb / best_sinr_db / gain_db, as a namespace of its own: the cached view stays what every other consumer
+        sees."""
+        best, sinr, gain = self.best_rb()
+        return SimpleNamespace(**vars(view), best_rb=best, best_sinr_db=sinr, gain_db=gain)
+
     def _observe(self, view):
         extra = {}
         if self._senses:
@@ -825,4 +892,7 @@ class VecD2DEnv:
         if self._marginal is not None:
             self._marginal.close()
             self._marginal = None
+        if self._bestrb is not None:
+            self._bestrb.close()
+            self._bestrb = None
         self.simulator.handle.close()

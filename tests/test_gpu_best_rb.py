@@ -1,0 +1,468 @@
+"""Best-response RB selection on the GPU (VecD2DEnv.best_rb, best_response_actions, BestRbObsFunction, csrc/d2d_bestrb.hip).
+
+Two yardsticks.  Bit for bit: the existing sensing kernel's block (d2d_sense_rb / VecD2DEnv.sense) on the same state, reduced on the
+host with np.argmax (first maximum) - best_rb is its argmax, best_sinr_db its value there, gain_db the float32 difference to the
+own-RB column.  Within the project's bar of 1e-5 max(|ref|, 1): the oracle's counterfactual (rb_sensing_util.counterfactual), with
+best_rb compared on every link the bar can decide (best_rb_util.oracle_side; test_best_rb_cpu.py holds the share of the others
+under 1 % on the oracle alone)."""
+import json
+
+import numpy as np
+import pytest
+
+import best_rb_util as bru
+from golden_util import rel_err
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip('torch')
+
+BAR = bru.BAR
+GUARD, PAD = 0x5AFEC0DE, 64
+SENT_I, SENT_F = -77, 123.25                   # what the outputs hold before a launch
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def _dev():
+    return torch.device('cuda', 0)
+
+
+def _inputs(c):
+    dev = _dev()
+    return [torch.as_tensor(np.ascontiguousarray(a), device=dev) for a in
+            (c['pos'][..., 0], c['pos'][..., 1], c['rb'], c['pwr'], c['tx'], c['rx'], c['cols'])]
+
+
+_blocks = {}
+
+
+def _sense(c, key):
+    """The reference: the sensing kernel's [B, N, R] block of the case, computed once."""
+    if key not in _blocks:
+        from gym_d2d_amd import _native
+        t = _inputs(c)
+        out = torch.empty((c['b'], c['n'], c['r']), dtype=torch.float32, device=_dev())
+        _native.sense_rb(*(x.data_ptr() for x in t), c['kind'], c['pow_k'], c['b'], c['d'], c['n'], c['r'], _native.SENSE_SINR_DB,
+                         out.data_ptr(), torch.cuda.current_stream(_dev()).cuda_stream)
+        torch.cuda.synchronize()
+        _blocks[key] = out.cpu().numpy()
+    return _blocks[key]
+
+
+def _best(c, allowed=None, env_mask=None):
+    """One d2d_best_rb launch into three planes that sit between guard words and hold sentinels: host copies (best, sinr, gain)."""
+    from gym_d2d_amd import _native
+    from gym_d2d_amd.best_response import pack_allowed
+    dev = _dev()
+    t = _inputs(c)
+    words = c['b'] * c['n']
+    arena = torch.full((3 * words + 4 * PAD,), GUARD, dtype=torch.int32, device=dev)
+    at = [PAD + k * (words + PAD) for k in range(3)]
+    arena[at[0]:at[0] + words] = SENT_I
+    for k in (1, 2):
+        arena[at[k]:at[k] + words].view(torch.float32).fill_(SENT_F)
+    w = None if allowed is None else torch.as_tensor(pack_allowed(allowed).view(np.int32), device=dev)
+    m = None if env_mask is None else torch.as_tensor(np.asarray(env_mask, dtype=np.uint8), device=dev)
+    _native.best_rb(*(x.data_ptr() for x in t), c['kind'], c['pow_k'], c['b'], c['d'], c['n'], c['r'], 0 if w is None else w.data_ptr(),
+                    0 if m is None else m.data_ptr(), *(arena.data_ptr() + 4 * a for a in at),
+                    torch.cuda.current_stream(dev).cuda_stream)
+    torch.cuda.synchronize()                                            # raises if the device faulted
+    host = arena.cpu().numpy()
+    for lo, hi in zip([0] + [a + words for a in at], at + [host.size]):
+        assert (host[lo:hi] == GUARD).all()
+    shape = (c['b'], c['n'])
+    return (host[at[0]:at[0] + words].reshape(shape), host[at[1]:at[1] + words].view(np.float32).reshape(shape),
+            host[at[2]:at[2] + words].view(np.float32).reshape(shape))
+
+
+def _check_against_block(c, blk, best, sinr, gain, allowed=None):
+    """best / sinr / gain against the block reduced on the host; returns the links that have an allowed RB."""
+    masked = blk if allowed is None else np.where(allowed[None], blk, -np.inf)
+    some = np.ones(best.shape, bool) if allowed is None else np.broadcast_to(allowed.any(axis=1)[None], best.shape)
+    ref_best = np.where(some, np.argmax(masked, axis=-1), -1)
+    assert np.array_equal(best, ref_best)
+    ref_val = np.take_along_axis(blk, np.maximum(ref_best, 0)[:, :, None], axis=2)[:, :, 0]
+    assert np.array_equal(_bits(sinr[some]), _bits(ref_val[some])) and np.isnan(sinr[~some]).all()
+    on_rb = (c['rb'] >= 0) & (c['rb'] < c['r'])
+    own = np.take_along_axis(blk, np.where(on_rb, c['rb'], 0)[:, :, None], axis=2)[:, :, 0]
+    fin = some & on_rb
+    assert np.array_equal(_bits(gain[fin]), _bits((ref_val - own).astype(np.float32)[fin])) and np.isnan(gain[~fin]).all()
+    return some, on_rb
+
+
+# ------------------------------------------------------------------------------------------ direct launches, bit for bit
+@pytest.mark.parametrize('law', bru.LAWS + ('mixed',))
+@pytest.mark.parametrize('r', bru.DIRECT_R)
+@pytest.mark.parametrize('n', bru.DIRECT_N)
+def test_direct_launch_equals_the_sensed_block_reduced_on_the_host(n, r, law):
+    from gym_d2d_amd import _native
+    c = bru.make_case(n, r, law)
+    assert c['kind'] == {'ld2': _native.BESTRB_LAW_INV_SQUARE, 'mixed': _native.BESTRB_LAW_POWER}.get(law, _native.BESTRB_LAW_POW_K)
+    blk = _sense(c, (n, r, law))
+    assert np.isfinite(blk).all()
+    best, sinr, gain = _best(c)
+    some, on_rb = _check_against_block(c, blk, best, sinr, gain)
+    assert some.all() and not on_rb.all() and on_rb.any()               # the case does hold links on no RB
+    assert (gain[on_rb] >= 0.0).all() and not np.signbit(gain[on_rb]).any()
+    assert (gain[on_rb & (best == c['rb'])] == 0.0).all()               # 0.0 exactly on the best RB
+    again = _best(c)
+    for a, b in zip((best, sinr, gain), again):                         # two calls, the same bits
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+# ------------------------------------------------------------------------------------------ the oracle
+@pytest.mark.parametrize('n,r,law', bru.ORACLE_CASES)
+def test_against_the_oracle_counterfactual(n, r, law):
+    c = bru.make_case(n, r, law, cell_radius=bru.ORACLE_CELL_M)
+    ref, expect, decided = bru.oracle_side(n, r, law)
+    best, sinr, gain = _best(c)
+    top = ref.max(axis=-1)
+    e = rel_err(sinr, top)
+    left_out = float((~decided).mean())
+    empty = ~bru.occupied(c['rb'], r)
+    tied = ((ref == top[:, :, None]) & empty).sum(axis=-1) > 1           # the top value is an exact tie between empty RBs
+    print(f'{n} links, {r} RBs, {law}: best_sinr_db vs the oracle rel_err {e:.3e}; {left_out:.2%} of {decided.size} links left out as '
+          f'near-ties, {int(tied.sum())} exact ties between empty RBs')
+    assert e <= BAR
+    assert left_out <= 0.01
+    assert np.array_equal(best[decided], expect[decided])
+    first_empty = np.where(empty, np.arange(r)[None, None, :], r).min(axis=-1)
+    assert np.array_equal(best[tied & decided], first_empty[tied & decided])          # ... resolved to the lowest r
+    on_rb = (c['rb'] >= 0) & (c['rb'] < r)
+    own = np.take_along_axis(ref, np.where(on_rb, c['rb'], 0)[:, :, None], axis=2)[:, :, 0]
+    # a difference of two values that each meet the bar: twice the bar, on the larger of the two magnitudes
+    assert (np.abs(gain - (top - own))[on_rb] <= 2 * BAR * np.maximum(np.maximum(np.abs(top), np.abs(own)), 1.0)[on_rb]).all()
+    assert np.isnan(gain[~on_rb]).all()
+
+
+# ------------------------------------------------------------------------------------------ allowed, env_mask
+@pytest.mark.parametrize('n,r,law', [(131, 70, 'ld35'), (300, 33, 'ld2'), (7, 3, 'mixed')])
+def test_allowed_mask_restricts_the_argmax(n, r, law):
+    c = bru.make_case(n, r, law)
+    blk = _sense(c, (n, r, law))
+    rng = np.random.default_rng(n + r)
+    allowed = rng.random((n, r)) < 0.5
+    allowed[:, 0] |= ~allowed.any(axis=1)                               # every row has one ...
+    allowed[5] = False                                                  # ... but this one
+    best, sinr, gain = _best(c, allowed=allowed)
+    some, on_rb = _check_against_block(c, blk, best, sinr, gain, allowed)
+    assert (best[:, 5] == -1).all() and np.isnan(sinr[:, 5]).all() and np.isnan(gain[:, 5]).all()
+    assert (best[some] >= 0).all() and allowed[np.nonzero(some)[1], best[some]].all()
+    own_barred = some & on_rb & ~allowed[np.arange(n)[None, :], np.where(on_rb, c['rb'], 0)]
+    assert own_barred.any() and np.isfinite(gain[own_barred]).all()     # where it stands still counts, allowed or not
+    assert (gain[own_barred] != 0.0).any()
+    full = _best(c, allowed=np.ones((n, r), bool))
+    for a, b in zip(full, _best(c)):                                    # an all-ones mask is no mask
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+def test_env_mask_leaves_unmarked_envs_as_they_were():
+    c = bru.make_case(131, 33, 'urban')
+    full = _best(c)
+    for mask in ([1, 0, 1], [0, 0, 0], [0, 7, 0]):
+        best, sinr, gain = _best(c, env_mask=mask)
+        for b, on in enumerate(mask):
+            if on:
+                for got, want in zip((best, sinr, gain), full):
+                    assert np.array_equal(got[b].view(np.uint32), want[b].view(np.uint32))
+            else:
+                assert (best[b] == SENT_I).all() and (sinr[b] == SENT_F).all() and (gain[b] == SENT_F).all()
+
+
+# ------------------------------------------------------------------------------------------ through the env
+B, CUES, PAIRS, R = 4, 6, 20, 5
+N = CUES + PAIRS
+CFG = {'num_rbs': R, 'num_cues': CUES, 'num_due_pairs': PAIRS}
+
+
+def _env(cfg=None, b=B, **kw):
+    from gym_d2d_amd.envs import VecD2DEnv
+    return VecD2DEnv(dict(CFG, **(cfg or {})), num_envs=b, **kw)
+
+
+def _actions(env, rng):
+    highs = env._initial_action_highs()
+    return torch.as_tensor(np.stack([rng.integers(0, h, env.num_envs) for h in highs], axis=1).astype(np.int32), device=env.device)
+
+
+def _same(a, b, what=''):
+    a, b = (x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x) for x in (a, b))
+    assert a.shape == b.shape and a.dtype == b.dtype, what
+    np.testing.assert_array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8), err_msg=what)
+
+
+def _planes(env, **kw):
+    return tuple(t.clone() for t in env.best_rb(**kw))
+
+
+@pytest.mark.parametrize('cue_actions', ['agent', 'traffic'])
+def test_best_response_actions_move_exactly_the_links_that_gain(cue_actions):
+    env = _env(cue_actions=cue_actions)
+    try:
+        rng = np.random.default_rng(3)
+        env.reset(seed=5)
+        _, _, _, info = env.step(_actions(env, rng))
+        rb0, pwr0 = info['rb'].clone(), info['tx_pwr_dbm'].clone()
+        best, sinr, gain = _planes(env)
+        blk = env.sense('sinr_db').cpu().numpy()
+        assert np.array_equal(best.cpu().numpy(), np.argmax(blk, axis=-1))
+        _same(sinr, np.take_along_axis(blk, best.cpu().numpy()[:, :, None].astype(np.int64), axis=2)[:, :, 0])
+        _same(gain, sinr - info['sinr_db'])                             # the own-RB value is the step's sinr_db
+        a = env.best_response_actions()
+        assert a.dtype == torch.int32 and tuple(a.shape) == (B, env.num_agents)
+        _, _, _, info = env.step(a)
+        moved = info['rb'] != rb0
+        wants = gain > 0
+        first = N - env.num_agents
+        wants[:, :first] = False                                        # links on fixed actions have no column: never moved
+        assert bool(wants[:, first:].any()) and not bool(wants[:, first:].all())
+        assert torch.equal(moved, wants)
+        assert torch.equal(info['rb'][moved], best[moved]) and torch.equal(info['tx_pwr_dbm'], pwr0)
+        if cue_actions == 'traffic':
+            assert bool((gain[:, :CUES] > 0).any())                     # some CUE would gain, and stays all the same
+            assert torch.equal(info['rb'][:, :CUES], rb0[:, :CUES])
+        none = env.best_response_actions(min_gain_db=1e9)               # nobody gains that much: everybody repeats
+        _, _, _, info2 = env.step(none)
+        assert torch.equal(info2['rb'], info['rb']) and torch.equal(info2['tx_pwr_dbm'], pwr0)
+        assert env.status_flags() == 0
+    finally:
+        env.close()
+
+
+def test_a_link_that_moved_alone_sits_on_its_best_rb():
+    env = _env()
+    try:
+        rng = np.random.default_rng(8)
+        env.reset(seed=6)
+        a0 = _actions(env, rng)
+        env.step(a0)
+        best, _, gain = _planes(env)
+        pick = gain.argmax(dim=1)                                       # ONE link per env moves, the one with the most to gain
+        rows = torch.arange(B, device=env.device)
+        assert bool((gain[rows, pick] > 0).all())
+        levels = torch.as_tensor([env.num_pwr_actions['cue']] * CUES + [env.num_pwr_actions['due']] * PAIRS, device=env.device)
+        a1 = a0.clone()
+        a1[rows, pick] = (best[rows, pick] * levels[pick] + a0[rows, pick] % levels[pick]).to(torch.int32)
+        _, _, _, info = env.step(a1)
+        assert int((a1 != a0).sum()) == B
+        best2, sinr2, gain2 = _planes(env)
+        assert bool((gain2[rows, pick] == 0.0).all()) and torch.equal(best2[rows, pick], best[rows, pick])
+        assert torch.equal(best2[rows, pick], info['rb'][rows, pick]) and torch.equal(sinr2[rows, pick], info['sinr_db'][rows, pick])
+    finally:
+        env.close()
+
+
+def test_allowed_through_the_env_and_out_planes():
+    env = _env()
+    try:
+        env.reset(seed=2)
+        rng = np.random.default_rng(1)
+        allowed = rng.random((N, R)) < 0.6
+        allowed[3] = False
+        blk = env.sense('sinr_db').cpu().numpy()
+        for mask in (allowed, torch.as_tensor(allowed), torch.as_tensor(allowed, device=env.device)):
+            best, sinr, gain = (t.cpu().numpy() for t in env.best_rb(allowed=mask))
+            ref = np.where(allowed.any(axis=1)[None], np.argmax(np.where(allowed[None], blk, -np.inf), axis=-1), -1)
+            assert np.array_equal(best, ref) and (best[:, 3] == -1).all() and np.isnan(sinr[:, 3]).all() and np.isnan(gain[:, 3]).all()
+        own = env.best_rb()
+        assert all(a is b for a, b in zip(own, env.best_rb()))          # the env's one triple, reused
+        want = tuple(t.clone() for t in own)
+        out = (torch.empty((B, N), dtype=torch.int32, device=env.device), torch.empty((B, N), device=env.device),
+               torch.empty((B, N), device=env.device))
+        got = env.best_rb(out=out)
+        assert all(a is b for a, b in zip(got, out))
+        for a, b in zip(got, want):
+            _same(a, b)
+        for bad in ((out[0], out[1]), (out[1], out[1], out[2]), (out[0], out[1], out[1]), out[0],
+                    (out[0], out[1], torch.empty((B, N + 1), device=env.device))):
+            with pytest.raises(ValueError, match='out must be'):
+                env.best_rb(out=bad)
+        with pytest.raises(ValueError, match='allowed must be'):
+            env.best_rb(allowed=np.ones((N, R + 1), bool))
+        with pytest.raises(ValueError, match='allowed must be'):
+            env.best_rb(allowed=np.ones((N, R), np.int32))
+    finally:
+        env.close()
+
+
+@pytest.mark.parametrize('autoreset', [False, True])
+def test_obs_function_and_views_equal_the_method(autoreset):
+    from gym_d2d_amd import _native
+    from gym_d2d_amd.envs import BestRbObsFunction
+    from gym_d2d_amd.envs.obs_fn import ArrayObsFunction
+    from gym_d2d_amd.spaces import Box
+    seen = {}
+
+    class Gain:
+        needs_best_rb = True
+
+        def compute(self, view):
+            seen['reward'] = (view.best_rb, view.best_sinr_db, view.gain_db)
+            return -view.gain_db
+
+    class Mine(ArrayObsFunction):
+        native_mode = _native.OBS_NONE
+        needs_best_rb = True
+
+        def get_obs_space(self, env_config):
+            return Box(low=-np.inf, high=np.inf, shape=(2,))
+
+        def compute(self, view):
+            seen['obs'] = (view.best_rb, view.best_sinr_db, view.gain_db)
+            return torch.stack([view.best_sinr_db, view.gain_db], dim=2)
+    kw = {'elapsed': np.arange(B) % 10} if autoreset else {}
+    by_hand = (torch.empty((B, N), dtype=torch.int32, device=_dev()), torch.empty((B, N), device=_dev()), torch.empty((B, N), device=_dev()))
+    for obs_fn, reward_fn in ((BestRbObsFunction, None), (Mine, Gain)):
+        env = _env({'obs_fn': obs_fn, **({'reward_fn': reward_fn} if reward_fn else {})}, autoreset=autoreset)
+        try:
+            before = _native.bestrb_launches
+            obs = env.reset(seed=9, **kw).clone()
+            assert _native.bestrb_launches == before + 1                # the obs function asks at reset too
+            assert env.observation_space.shape == ((3,) if reward_fn is None else (2,))
+            rng = np.random.default_rng(2)
+            resets = 0
+            for step in range(12 if autoreset else 3):
+                if step:
+                    before = _native.bestrb_launches
+                    obs, rewards, _, info = env.step(_actions(env, rng))
+                    assert _native.bestrb_launches == before + 1        # ONE launch serves the obs and the reward function
+                    obs, rewards = obs.clone(), rewards.clone()
+                best, sinr, gain = env.best_rb(out=by_hand)
+                if reward_fn is None:
+                    assert tuple(obs.shape) == (B, N, 3) and obs.dtype == torch.float32
+                    _same(obs[:, :, 0], best.to(torch.float32)); _same(obs[:, :, 1], sinr); _same(obs[:, :, 2], gain)
+                else:
+                    _same(obs[:, :, 0], sinr); _same(obs[:, :, 1], gain)
+                    assert seen['obs'][0] is env.best_rb()[0]            # the env's own planes, not copies
+                    if step:
+                        assert all(a is b for a, b in zip(seen['obs'], seen['reward']))
+                        if autoreset:
+                            was_reset = info['reset']
+                            assert bool((rewards[was_reset] == 0.0).all()) and torch.equal(rewards[~was_reset], -gain[~was_reset])
+                        else:
+                            _same(rewards, -gain)
+                if step and autoreset:
+                    resets += int(info['reset'].sum())                  # reset envs: the values of their reset's step, as by_hand
+                cached = env._view()
+                assert not hasattr(cached, 'best_rb') and not hasattr(cached, 'gain_db')     # the cached view is untouched
+            assert not autoreset or resets >= B
+        finally:
+            env.close()
+
+
+def test_envs_that_do_not_ask_launch_nothing():
+    from gym_d2d_amd import _native
+    from gym_d2d_amd.envs import BestRbObsFunction, RbSensingObsFunction
+    from gym_d2d_amd.envs.obs_fn import LinearObsFunction, OwnLinkObsFunction, SignalPlanesObsFunction
+
+    def launches(obs_fn, **kw):
+        before = _native.bestrb_launches
+        env = _env({'obs_fn': obs_fn}, **kw)
+        try:
+            env.reset(seed=1)
+            for _ in range(3):
+                env.step(env.action_buffer().clone())
+            assert (env._bestrb is None) == (obs_fn is not BestRbObsFunction)
+        finally:
+            env.close()
+        return _native.bestrb_launches - before
+    for fn in (LinearObsFunction, OwnLinkObsFunction, SignalPlanesObsFunction, RbSensingObsFunction):
+        assert launches(fn) == 0
+        assert launches(fn, autoreset=True) == 0
+    assert launches(BestRbObsFunction) == 4                             # the reset's step and three steps
+
+
+def test_two_shards_equal_the_whole_batch():
+    rng = np.random.default_rng(4)
+    whole = _env()
+    acts = [_actions(whole, rng) for _ in range(2)]
+
+    def run(env, rows):
+        out = []
+        env.reset(seed=11)
+        out.append(_planes(env))
+        for a in acts:
+            env.step(a[rows].contiguous())
+            out.append(_planes(env))
+        env.close()
+        return out
+    ref = run(whole, slice(0, B))
+    for k in range(2):
+        rows = slice(k * B // 2, (k + 1) * B // 2)
+        got = run(_env(b=B // 2, first_env=k * B // 2), rows)
+        for t, (a, b) in enumerate(zip(ref, got)):
+            for x, y, what in zip(a, b, ('best_rb', 'best_sinr_db', 'gain_db')):
+                _same(x[rows], y, f'shard {k}, step {t}: {what}')
+
+
+@pytest.mark.parametrize('moving', [False, True])
+def test_staggered_autoreset_equals_one_lockstep_env_each(moving):
+    from gym_d2d_amd.envs import BestRbObsFunction
+    from gym_d2d_amd.mobility import GaussMarkovMobility
+    mob = (lambda: {'mobility': GaussMarkovMobility(speed_std_mps=8.0, memory=0.7)}) if moving else (lambda: {})
+    cfg, steps, first = {'obs_fn': BestRbObsFunction, 'seed': 7}, 13, 40
+    env = _env(cfg, autoreset=True, first_env=first, **mob())
+    obs0 = env.reset(seed=21, elapsed=np.arange(B) % 10).clone()
+    rng = np.random.default_rng(4)
+    acts, outs, resets = [], [], []
+    for t in range(steps):
+        a = _actions(env, rng)
+        obs, _, _, info = env.step(a)
+        outs.append(obs.clone()); resets.append(info['reset'].cpu().numpy().copy()); acts.append(a)
+    env.close()
+    assert np.array(resets).sum() >= B
+    for e in range(B):
+        one = _env(cfg, b=1, first_env=first + e, **mob())
+        _same(obs0[e:e + 1], one.reset(seed=21), f'env {e} reset')
+        for t in range(steps):
+            want = one.reset() if resets[t][e] else one.step(acts[t][e:e + 1].contiguous())[0]
+            _same(outs[t][e:e + 1], want, f'env {e} step {t + 1}')
+        one.close()
+
+
+# ------------------------------------------------------------------------------------------ refusals
+def test_unsupported_envs_are_refused_by_name(tmp_path):
+    from gym_d2d_amd.envs import BestRbObsFunction, VecD2DEnv
+    from gym_d2d_amd.path_loss import ArrayPathLoss, PathLoss, ShadowingPathLoss
+    small = {'num_rbs': 4, 'num_cues': 3, 'num_due_pairs': 3}
+
+    class Foo(PathLoss):
+        def __call__(self, tx, rx):
+            return 20 * np.log10(tx.position.distance(rx.position)) + 40.0
+
+    class Arr(ArrayPathLoss):
+        def compute(self, view):
+            return 20 * view.xp.log10(view.distance()) + 40.0
+
+    class PerStep(Arr):
+        per_step = True
+
+    def refused(text, cfg=None, **kw):
+        env = VecD2DEnv(dict(small, **(cfg or {})), num_envs=2, **kw)
+        try:
+            env.reset(seed=1)
+            with pytest.raises(ValueError, match=text):
+                env.best_rb()
+            with pytest.raises(ValueError, match=text):
+                env.best_response_actions()
+            assert env._bestrb is None
+        finally:
+            env.close()
+    refused(r'best_rb\(\).*export_actions', export_actions=False)
+    refused(r'best_rb\(\).*ShadowingPathLoss', {'path_loss_model': ShadowingPathLoss})
+    refused(r"best_rb\(\).*'link_table'", {'path_loss_model': Foo})
+    refused(r"best_rb\(\).*'array'", {'path_loss_model': Arr})
+    refused(r"best_rb\(\).*'per_step'", {'path_loss_model': PerStep})
+    pinned = tmp_path / 'pinned.json'
+    pinned.write_text(json.dumps({'cue00': {'position': [100.1, -20.3], 'config': {'max_tx_power_dBm': 23}}}))
+    refused(r'best_rb\(\).*float32 cannot hold', {'device_config_file': pinned})
+    with pytest.raises(ValueError, match=r'best_rb\(\).*export_actions'):         # at construction, not inside the first step
+        VecD2DEnv(dict(small, obs_fn=BestRbObsFunction), num_envs=2, export_actions=False)
+    env = VecD2DEnv(dict(small), num_envs=2, use_torch=False)
+    try:
+        with pytest.raises(ValueError, match=r'best_rb\(\) needs the torch path'):
+            env.best_rb()
+    finally:
+        env.close()
