@@ -22,7 +22,7 @@ from typing import Optional
 
 import numpy as np
 
-from .. import _native, best_response, graph, marginal, sensing
+from .. import _native, best_response, graph, marginal, power_control, sensing
 from .. import mobility as mobility_mod
 from .. import queues as queues_mod
 from ..path_loss_table import CHANNEL, PER_STEP, positions_move_unserved
@@ -270,6 +270,9 @@ class VecD2DEnv:
         self._wants_best_rb = self._obs_best_rb or bool(getattr(self.reward_fn, 'needs_best_rb', False))
         if self._wants_best_rb:
             self._best_rb_kernel()                 # refusals surface here, not inside the first step
+        # target-SINR power control (power_control()): nothing is loaded, allocated or launched unless it is called
+        self._powerctl = None
+        self._power_levels = None                  # power_control_actions(): (lowest power, power levels) of every agent link's class
 
     def _setup_autoreset(self) -> None:
         """Refuse what a device-side per-env reset cannot serve, then allocate the per-env bookkeeping: pending / episode are bound
@@ -832,6 +835,57 @@ class VecD2DEnv:
         best, sinr, gain = self.best_rb()
         return SimpleNamespace(**vars(view), best_rb=best, best_sinr_db=sinr, gain_db=gain)
 
+    # ------------------------------------------------------------------ target-SINR power control
+    def _power_control_kernel(self):
+        if self._powerctl is None:
+            why = power_control.refusal(self.simulator, self.export_actions, self.use_torch)
+            if why:
+                raise ValueError(why)
+            p_min, p_max = power_control.class_bounds(self.num_pwr_actions, self._cue_kind, self.num_cues, self.num_due_pairs)
+            agent = np.arange(self.num_links) >= self.num_links - self.num_agents
+            self._powerctl = power_control.PowerControl(self.simulator, self.num_links, p_min, p_max, agent, torch, self.device)
+        return self._powerctl
+
+    def power_control(self, target_sinr_db, adjustable=None, max_iters: int = 64, out=None, env_mask=None):
+        """The least powers that meet a target SINR, with positions and RBs as the last step left them: (power_dbm int32 [B, N],
+        sinr_db float32 [B, N], iters int32 [B], converged uint8 [B]), a tuple with those names.
+
+        The constrained target-SINR iteration (Foschini-Miljanic / Yates) on the env's integer dBm alphabet: every adjustable link
+        starts at the lowest power of its class and raises it, whole dBm at a time and all links at once from the same old vector,
+        to ceil(power + target - sinr_db), never past its class maximum and never down.  It ends at the least fixed point - the
+        componentwise power-minimal assignment that meets the targets when they are feasible; links whose target is out of reach
+        end at their maximum - or after max_iters sweeps that each changed a link (converged 0, iters == max_iters).  sinr_db is
+        the step's sinr_db for power_dbm bit for bit, valid at the cap too.  All sweeps of an env run in one workgroup of one kernel
+        launch (csrc/d2d_powerctl.hip) out of LDS: no [B, N, N] pass per sweep.  Valid after reset() and after every step(),
+        autoreset steps included, as sense() is.
+
+        target_sinr_db: a number, {'cue': x, 'due': y}, or [N] values (array or tensor), dB.  adjustable: bool [N], the links that
+        may move; None: every agent link.  Links on fixed actions (cue_actions='traffic') are never adjusted; a link that is not
+        adjusted keeps its power and interferes; a link on no RB (rb outside [0, R)) keeps its power and has sinr_db NaN.  The
+        bounds are the ones step() decodes: an agent's power is its action's level, 0 .. levels - 1 dBm (due_min_tx_power_dBm is
+        not added back, as in d2d_env.py:94-96).  env_mask: bool / uint8 [B], envs whose entry is 0 keep their rows; None: all.
+
+        Torch path only: enqueued on torch's current stream, nothing is synchronised; the four tensors the env owns, rewritten by
+        every call (clone them to keep them), or `out` = (power_dbm, sinr_db, iters, converged), contiguous int32 / float32 [B, N],
+        int32 / uint8 [B] on the env's device.  Serves what sense() serves; ValueError for export_actions=False, ShadowingPathLoss,
+        every table route, pinned device_config coordinates float32 cannot hold."""
+        k = self._power_control_kernel()
+        target, adj = k.target(target_sinr_db, self.num_cues), k.adjustable(adjustable)
+        self._follow_torch_stream()
+        return k.solve(self._t, target, adj, max_iters, out, self._stream_ptr, env_mask)
+
+    def power_control_actions(self, target_sinr_db, adjustable=None, max_iters: int = 64):
+        """power_control() as an action tensor, int32 [B, num_agents], ready for step(): every agent link stays on its RB (as the
+        decoded planes hold it) at the solved power, encoded rb * power levels + level; an agent link that is not adjustable
+        repeats its last action.  Links on fixed actions (cue_actions='traffic') have no column.  Composes with
+        best_response_actions(): one call picks RBs, the other picks powers."""
+        power = self.power_control(target_sinr_db, adjustable, max_iters)[0]
+        first = self.num_links - self.num_agents
+        if self._power_levels is None:
+            p_min, p_max = power_control.class_bounds(self.num_pwr_actions, self._cue_kind, self.num_cues, self.num_due_pairs)
+            self._power_levels = tuple(torch.as_tensor(a[first:], device=self.device) for a in (p_min, p_max - p_min + 1))
+        return power_control.encode_actions(self._t['rb'], power, *self._power_levels, first)
+
     def _observe(self, view):
         extra = {}
         if self._senses:
@@ -895,4 +949,7 @@ class VecD2DEnv:
         if self._bestrb is not None:
             self._bestrb.close()
             self._bestrb = None
+        if self._powerctl is not None:
+            self._powerctl.close()
+            self._powerctl = None
         self.simulator.handle.close()

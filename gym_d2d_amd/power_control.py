@@ -1,0 +1,168 @@
+"""Target-SINR power control: the host side of libd2d_powerctl.so (include/d2d_powerctl.h, csrc/d2d_powerctl.hip).
+
+`PowerControl` owns the device-side constants of one env object (link lists, the columns sensing.fold_columns folds, unchanged, the
+power bounds of every link's class) and launches the kernel on torch's device pointers.  `class_bounds` gives the bounds,
+`encode_actions` turns the solved powers into the action tensor VecD2DEnv.step() takes.  Torch path only.
+"""
+from __future__ import annotations
+
+from typing import NamedTuple, Optional
+
+import numpy as np
+
+from . import _native
+from .sensing import fold_columns, unserved
+
+
+class PowerControlResult(NamedTuple):
+    """What power_control() returns: a tuple with names."""
+    power_dbm: object          # int32 [B, N]: the powers when the iteration stopped
+    sinr_db: object            # float32 [B, N]: every link's SINR at those powers
+    iters: object              # int32 [B]: the sweeps that changed a link; max_iters at the cap
+    converged: object          # uint8 [B]: 1 - the fixed point was reached
+
+
+def refusal(sim, export_actions: bool, use_torch: bool = True) -> Optional[str]:
+    """Why this env has no power_control() (None: it has): the predicate of sensing.unserved under texts of its own."""
+    if not use_torch:
+        return 'power_control() needs the torch path (use_torch): its planes are device tensors'
+    why = unserved(sim, export_actions)
+    if why is None:
+        return None
+    kind, route = why
+    return {
+        'export_actions': 'power_control() reads the decoded (rb, tx power) planes, which export_actions=False does not write: build '
+                          'the env with export_actions=True',
+        'route': f"power_control() does not serve the '{route}' path-loss route (a table, not a law its kernel can evaluate for the "
+                 'powers no step has applied); it serves the native power-law models',
+        'shadowing': 'power_control() does not serve ShadowingPathLoss: a fresh draw per evaluation has no fixed point (the SINR a '
+                     'power was solved for is another draw than the one the next step sees)',
+        'pinned': 'power_control() does not serve pinned device_config coordinates that float32 cannot hold: their low parts live '
+                  'inside the handle (float64 positions)',
+    }[kind]
+
+
+def class_bounds(num_pwr_actions: dict, cue_kind: str, num_cues: int, num_due_pairs: int):
+    """(p_min, p_max) int32 [N] of the default link list (CUE links first), in the dBm the step transmits.  The env's decoder takes
+    a link's power as its action's level, action mod levels, and does not add due_min_tx_power_dBm back (d2d_env.py:94-96): what a
+    DUE transmits runs over 0 .. due_max - due_min, a CUE over 0 .. cue_max, a base station over 0 .. mbs_max.  The bounds are the
+    decoder's, so that a solved power is a power step() applies."""
+    levels = np.asarray([num_pwr_actions[cue_kind]] * num_cues + [num_pwr_actions['due']] * num_due_pairs, dtype=np.int32)
+    return np.zeros_like(levels), levels - 1
+
+
+def encode_actions(rb, power_dbm, p_min, levels, first_agent: int = 0):
+    """The action array [B, num_agents] that keeps every agent link on its RB at power_dbm: rb * levels + (power_dbm - p_min), the
+    env's own layout (d2d_env.py:94-96).  rb, power_dbm: [B, N]; p_min, levels: int [num_agents], the lowest power and the number of
+    power levels of every agent link's class; the agents are links first_agent .. first_agent + num_agents - 1 (links on fixed
+    actions come first and have no column).  NumPy arrays or torch tensors alike; the result is int32."""
+    n = first_agent + levels.shape[0]
+    rb, power_dbm = rb[:, first_agent:n], power_dbm[:, first_agent:n]
+    act = rb * levels + (power_dbm - p_min)
+    if isinstance(act, np.ndarray):
+        return act.astype(np.int32)
+    import torch
+    return act.to(torch.int32)
+
+
+class PowerControl:
+    """The power-control kernel bound to one env object: constants uploaded once, one launch per call."""
+
+    def __init__(self, sim, num_links: int, p_min, p_max, agent, torch, device) -> None:
+        from .device import link_budget_columns
+        self.sim, self.torch, self.device = sim, torch, device
+        h = sim.handle
+        self.b, self.d, self.n, self.r = sim.num_envs, h.num_devices, int(num_links), int(sim.config.num_rbs)
+        if self.r > _native.POWERCTL_MAX_RBS:
+            raise ValueError(f'power_control() serves at most {_native.POWERCTL_MAX_RBS} RBs (num_rbs = {self.r})')
+        tx, rx = np.asarray(sim.link_tx, dtype=np.int32), np.asarray(sim.link_rx, dtype=np.int32)
+        if len(tx) != self.n or tx.min() < 0 or tx.max() >= self.d or rx.min() < 0 or rx.max() >= self.d:
+            raise ValueError('the link list does not match the env')
+        cols, self.law, self.pow_k = fold_columns(link_budget_columns(sim._dev_list), sim.path_loss_table.law, tx)
+        p_min, p_max = np.asarray(p_min, dtype=np.int32), np.asarray(p_max, dtype=np.int32)
+        self.agent = np.asarray(agent, dtype=bool)                   # links that have an action column: the only ones ever adjusted
+        if not (p_min.shape == p_max.shape == self.agent.shape == (self.n,)) or (p_min > p_max).any() or np.abs(p_max).max() >= 4096:
+            raise ValueError('the power bounds do not match the env')
+        self.own = None                              # the four outputs this object owns, allocated by the first call without out=
+        self.tx, self.rx, self.cols, self.p_min, self.p_max = (torch.as_tensor(a, device=device) for a in (tx, rx, cols, p_min, p_max))
+        self.ptrs = tuple(t.data_ptr() for t in (self.tx, self.rx, self.cols))
+        self._target = self._adjustable = None       # (key, tensor) of the last call: a repeated target is not uploaded again
+
+    def target(self, target_sinr_db, num_cues: int):
+        """float32 [N] on the device from a scalar, {'cue': x, 'due': y} or [N] values (array or tensor)."""
+        torch = self.torch
+        if torch.is_tensor(target_sinr_db):
+            t = target_sinr_db.to(device=self.device, dtype=torch.float32).contiguous()
+            if tuple(t.shape) != (self.n,):
+                raise ValueError(f'target_sinr_db must be a number, {{"cue": x, "due": y}} or [{self.n}] values')
+            return t
+        if isinstance(target_sinr_db, dict):
+            if set(target_sinr_db) != {'cue', 'due'}:
+                raise ValueError("target_sinr_db as a dict takes exactly the keys 'cue' and 'due'")
+            host = np.asarray([target_sinr_db['cue']] * num_cues + [target_sinr_db['due']] * (self.n - num_cues), dtype=np.float32)
+        else:
+            host = np.asarray(target_sinr_db, dtype=np.float32)
+            if host.ndim == 0:
+                host = np.full(self.n, host, dtype=np.float32)
+        if host.shape != (self.n,) or np.isnan(host).any():
+            raise ValueError(f'target_sinr_db must be a number, {{"cue": x, "due": y}} or [{self.n}] values, none of them NaN')
+        key = host.tobytes()
+        if self._target is None or self._target[0] != key:
+            self._target = (key, torch.as_tensor(host, device=self.device))
+        return self._target[1]
+
+    def adjustable(self, adjustable):
+        """uint8 [N] on the device: the agent links (None), or those of them `adjustable` (bool [N], array or tensor) marks."""
+        torch = self.torch
+        if adjustable is None:
+            host = self.agent
+        else:
+            host = adjustable.cpu().numpy() if torch.is_tensor(adjustable) else np.asarray(adjustable)
+            if host.shape != (self.n,) or host.dtype != np.bool_:
+                raise ValueError(f'adjustable must be bool [{self.n}] (link) or None')
+            host = host & self.agent
+        key = host.tobytes()
+        if self._adjustable is None or self._adjustable[0] != key:
+            self._adjustable = (key, torch.as_tensor(host.astype(np.uint8), device=self.device))
+        return self._adjustable[1]
+
+    def outputs(self, out):
+        torch = self.torch
+        shapes = ((self.b, self.n), (self.b, self.n), (self.b,), (self.b,))
+        dtypes = (torch.int32, torch.float32, torch.int32, torch.uint8)
+        if out is None:
+            if self.own is None:
+                self.own = tuple(torch.empty(s, dtype=dt, device=self.device) for s, dt in zip(shapes, dtypes))
+            return self.own
+        ok = isinstance(out, (tuple, list)) and len(out) == 4 and all(
+            torch.is_tensor(o) and tuple(o.shape) == s and o.dtype == dt and o.is_contiguous() and o.device == self.device
+            for o, s, dt in zip(out, shapes, dtypes))
+        if not ok or len({o.data_ptr() for o in out}) != 4:
+            raise ValueError(f'out must be (power_dbm, sinr_db, iters, converged): contiguous int32 {list(shapes[0])}, float32 '
+                             f'{list(shapes[1])}, int32 [{self.b}] and uint8 [{self.b}] tensors on {self.device} that do not share '
+                             'memory')
+        return tuple(out)
+
+    def env_mask(self, env_mask):
+        torch = self.torch
+        if env_mask is None:
+            return None
+        m = env_mask if torch.is_tensor(env_mask) else torch.as_tensor(np.asarray(env_mask))
+        if tuple(m.shape) != (self.b,) or m.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f'env_mask must be bool or uint8 [{self.b}] or None')
+        return m.to(device=self.device, dtype=torch.uint8).contiguous()
+
+    def solve(self, t: dict, target, adjustable, max_iters: int, out, stream: int, env_mask=None) -> PowerControlResult:
+        """target, adjustable: the tensors target() and adjustable() return."""
+        if isinstance(max_iters, bool) or not isinstance(max_iters, (int, np.integer)) or max_iters < 1:
+            raise ValueError(f'max_iters must be an int >= 1, got {max_iters!r}')
+        power, sinr, iters, conv = self.outputs(out)
+        mask = self.env_mask(env_mask)               # lives until the launch is enqueued; the stream orders its release behind it
+        _native.power_control(t['pos_x'].data_ptr(), t['pos_y'].data_ptr(), t['rb'].data_ptr(), t['pwr'].data_ptr(), *self.ptrs,
+                              self.law, self.pow_k, self.b, self.d, self.n, self.r, target.data_ptr(), self.p_min.data_ptr(),
+                              self.p_max.data_ptr(), adjustable.data_ptr(), int(max_iters), 0 if mask is None else mask.data_ptr(),
+                              power.data_ptr(), sinr.data_ptr(), iters.data_ptr(), conv.data_ptr(), stream)
+        return PowerControlResult(power, sinr, iters, conv)
+
+    def close(self) -> None:
+        pass
