@@ -1,7 +1,7 @@
 """ctypes binding of libd2d_hip.so (include/d2d_hip.h), libd2d_plugin.so (include/d2d_plugin.h), libd2d_episode.so
 (include/d2d_episode.h), libd2d_sense.so (include/d2d_sense.h), libd2d_graph.so (include/d2d_graph.h), libd2d_marginal.so (include/d2d_marginal.h), libd2d_mobility.so
 (include/d2d_mobility.h), libd2d_channel.so (include/d2d_channel.h), libd2d_queue.so (include/d2d_queue.h) libd2d_bestrb.so
-(include/d2d_bestrb.h) and libd2d_powerctl.so (include/d2d_powerctl.h).  There is no CPU fallback: if a library or a gfx950 GPU is missing, the calls below raise."""
+(include/d2d_bestrb.h), libd2d_powerctl.so (include/d2d_powerctl.h) and libd2d_brdyn.so (include/d2d_brdyn.h).  There is no CPU fallback: if a library or a gfx950 GPU is missing, the calls below raise."""
 from __future__ import annotations
 
 import ctypes as C
@@ -21,6 +21,7 @@ CHANNEL_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_channel.so'
 QUEUE_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_queue.so'
 BESTRB_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_bestrb.so'
 POWERCTL_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_powerctl.so'
+BRDYN_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_brdyn.so'
 ABI_VERSION = 7
 MAX_LINKS = 2048
 
@@ -70,6 +71,11 @@ BESTRB_MAX_RBS = 8192
 # d2d_power_control's law / limits (include/d2d_powerctl.h): the sensing kernel's
 POWERCTL_LAW_INV_SQUARE, POWERCTL_LAW_POWER, POWERCTL_LAW_POW_K = 0, 1, 2
 POWERCTL_MAX_RBS = 8192
+# d2d_best_response_dynamics's law / limits (include/d2d_brdyn.h): the sensing kernel's, and the LDS of one workgroup
+BRDYN_LAW_INV_SQUARE, BRDYN_LAW_POWER, BRDYN_LAW_POW_K = 0, 1, 2
+BRDYN_MAX_RBS = 8192
+BRDYN_MAX_ROUNDS = 1024
+BRDYN_MAX_LDS_BYTES = 163840
 
 BUFFER_DTYPES = {BUF_ACTIONS: np.int32, BUF_RB: np.int32, BUF_PWR: np.int32, BUF_ENV_FLAGS: np.int32, BUF_RESET_PENDING: np.int32,
                  BUF_EPISODE: np.uint32}
@@ -216,6 +222,13 @@ POWERCTL_SIGNATURES = {
     'd2d_powerctl_last_error': (C.c_char_p, []),
 }
 
+# every symbol include/d2d_brdyn.h declares
+BRDYN_SIGNATURES = {
+    'd2d_best_response_dynamics': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, C.c_int64, _I, _I, _I, _P, _P, C.c_float, _I, _P, _P, _P, _P,
+                                             _P, _P, _P]),
+    'd2d_brdyn_last_error': (C.c_char_p, []),
+}
+
 _lib: Optional[C.CDLL] = None
 _plugin: Optional[C.CDLL] = None
 _episode: Optional[C.CDLL] = None
@@ -229,6 +242,8 @@ _bestrb: Optional[C.CDLL] = None
 bestrb_launches = 0                 # d2d_best_rb calls made through best_rb() in this process
 _powerctl: Optional[C.CDLL] = None
 powerctl_launches = 0               # d2d_power_control calls made through power_control() in this process
+_brdyn: Optional[C.CDLL] = None
+brdyn_launches = 0                  # d2d_best_response_dynamics launches made through best_response_dynamics() in this process
 _mobility: Optional[C.CDLL] = None
 mobility_launches = 0               # d2d_mobility_move calls made through mobility_move() in this process
 _channel: Optional[C.CDLL] = None
@@ -496,6 +511,44 @@ def power_control(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, lin
         raise NativeError(rc, lib.d2d_powerctl_last_error().decode(errors='replace'))
     if n_envs:
         powerctl_launches += 1
+
+
+def load_brdyn_library() -> C.CDLL:
+    """dlopen libd2d_brdyn.so and type its entry points.  Raises if it has not been built."""
+    global _brdyn
+    if _brdyn is not None:
+        return _brdyn
+    if not BRDYN_PATH.exists():
+        raise ImportError(f'{BRDYN_PATH} is missing - build it with `python -m gym_d2d_amd.build`')
+    lib = C.CDLL(str(BRDYN_PATH))
+    for name, (res, args) in BRDYN_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    _brdyn = lib
+    return lib
+
+
+def best_response_dynamics(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, link_tx_ptr: int, link_rx_ptr: int, cols_ptr: int,
+                           law: int, pow_k: int, n_envs: int, n_dev: int, n_links: int, n_rbs: int, allowed_ptr: int, movable_ptr: int,
+                           min_gain_db: float, max_rounds: int, env_mask_ptr: int, rb_out_ptr: int, sinr_ptr: int, rounds_ptr: int,
+                           moves_ptr: int, converged_ptr: int, stream_ptr: int = 0) -> None:
+    """d2d_best_response_dynamics: sequential best response on the RBs of every env in one launch - rb int32 and sinr_db float32
+    [n_envs, n_links], rounds / moves int32 and converged uint8 [n_envs] (device pointers; allowed_ptr 0: every RB, else uint32
+    [n_links, ceil(n_rbs / 32)]; movable_ptr 0: every link, else uint8 [n_links]; env_mask_ptr 0: every env, else uint8 [n_envs]
+    and the envs whose byte is 0 keep their rows)."""
+    global brdyn_launches
+    lib = load_brdyn_library()
+    rc = lib.d2d_best_response_dynamics(_P(pos_x_ptr or None), _P(pos_y_ptr or None), _P(rb_ptr or None), _P(pwr_ptr or None),
+                                        _P(link_tx_ptr or None), _P(link_rx_ptr or None), _P(cols_ptr or None), law, pow_k, n_envs,
+                                        n_dev, n_links, n_rbs, _P(allowed_ptr or None), _P(movable_ptr or None), min_gain_db,
+                                        max_rounds, _P(env_mask_ptr or None), _P(rb_out_ptr or None), _P(sinr_ptr or None),
+                                        _P(rounds_ptr or None), _P(moves_ptr or None), _P(converged_ptr or None),
+                                        _P(stream_ptr or None))
+    if rc != 0:
+        raise NativeError(rc, lib.d2d_brdyn_last_error().decode(errors='replace'))
+    if n_envs:
+        brdyn_launches += 1
 
 
 def load_mobility_library() -> C.CDLL:

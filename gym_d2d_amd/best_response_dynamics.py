@@ -1,0 +1,164 @@
+"""Sequential best-response RB dynamics: the host side of libd2d_brdyn.so (include/d2d_brdyn.h, csrc/d2d_brdyn.hip).
+
+`BestResponseDynamics` owns the device-side constants of one env object (link lists, the columns sensing.fold_columns folds,
+unchanged) and launches the kernel on torch's device pointers; the allowed mask goes through best_response.pack_allowed.
+`encode_actions` turns the solved RBs into the action tensor VecD2DEnv.step() takes.  Torch path only.
+"""
+from __future__ import annotations
+
+import math
+from typing import NamedTuple, Optional
+
+import numpy as np
+
+from . import _native
+from .best_response import pack_allowed
+from .sensing import fold_columns, unserved
+
+
+class BestResponseDynamicsResult(NamedTuple):
+    """What best_response_dynamics() returns: a tuple with names."""
+    rb: object                 # int32 [B, N]: the RBs when the dynamics stopped
+    sinr_db: object            # float32 [B, N]: every link's SINR on those RBs
+    rounds: object             # int32 [B]: the rounds that moved a link; max_rounds at the cap
+    moves: object              # int32 [B]: the moves made
+    converged: object          # uint8 [B]: 1 - a round moved nobody
+
+
+def refusal(sim, export_actions: bool, use_torch: bool = True) -> Optional[str]:
+    """Why this env has no best_response_dynamics() (None: it has): the predicate of sensing.unserved under texts of its own."""
+    if not use_torch:
+        return 'best_response_dynamics() needs the torch path (use_torch): its planes are device tensors'
+    why = unserved(sim, export_actions)
+    if why is None:
+        return None
+    kind, route = why
+    return {
+        'export_actions': 'best_response_dynamics() reads the decoded (rb, tx power) planes, which export_actions=False does not '
+                          'write: build the env with export_actions=True',
+        'route': f"best_response_dynamics() does not serve the '{route}' path-loss route (a table, not a law its kernel can "
+                 'evaluate for the RBs no step has applied); it serves the native power-law models',
+        'shadowing': 'best_response_dynamics() does not serve ShadowingPathLoss: a fresh draw per evaluation has no best response '
+                     '(the SINR a move was made for is another draw than the one the next link sees)',
+        'pinned': 'best_response_dynamics() does not serve pinned device_config coordinates that float32 cannot hold: their low '
+                  'parts live inside the handle (float64 positions)',
+    }[kind]
+
+
+def lds_bytes(num_links: int, num_rbs: int, power_law: bool, allowed: bool) -> int:
+    """The LDS one workgroup of the kernel needs (the header's formula): at most _native.BRDYN_MAX_LDS_BYTES is served."""
+    r16 = lambda x: (x + 15) & ~15
+    n, n4 = num_links, (num_links + 3) & ~3
+    return (32 * n + (r16(8 * n) if power_law else 0) + 12 * n4 + (r16(4 * n * ((num_rbs + 31) // 32)) if allowed else 0)
+            + r16(4 * ((n + 31) // 32) * num_rbs) + 80)
+
+
+def encode_actions(rb, pwr, levels, first_agent: int = 0):
+    """The action array [B, num_agents] that puts every agent link on rb at its current power level: rb * levels + power level, the
+    env's own layout (d2d_env.py:94-96).  rb, pwr: [B, N] (the solved RBs, the decoded power plane); levels: int [num_agents], the
+    power levels of every agent link's class; the agents are links first_agent .. first_agent + num_agents - 1 (links on fixed
+    actions come first and have no column).  NumPy arrays or torch tensors alike; the result is int32."""
+    n = first_agent + levels.shape[0]
+    act = rb[:, first_agent:n] * levels + pwr[:, first_agent:n]
+    if isinstance(act, np.ndarray):
+        return act.astype(np.int32)
+    import torch
+    return act.to(torch.int32)
+
+
+class BestResponseDynamics:
+    """The dynamics kernel bound to one env object: constants uploaded once, one launch per call."""
+
+    def __init__(self, sim, num_links: int, agent, torch, device) -> None:
+        from .device import link_budget_columns
+        self.sim, self.torch, self.device = sim, torch, device
+        h = sim.handle
+        self.b, self.d, self.n, self.r = sim.num_envs, h.num_devices, int(num_links), int(sim.config.num_rbs)
+        if self.r > _native.BRDYN_MAX_RBS:
+            raise ValueError(f'best_response_dynamics() serves at most {_native.BRDYN_MAX_RBS} RBs (num_rbs = {self.r})')
+        tx, rx = np.asarray(sim.link_tx, dtype=np.int32), np.asarray(sim.link_rx, dtype=np.int32)
+        if len(tx) != self.n or tx.min() < 0 or tx.max() >= self.d or rx.min() < 0 or rx.max() >= self.d:
+            raise ValueError('the link list does not match the env')
+        cols, self.law, self.pow_k = fold_columns(link_budget_columns(sim._dev_list), sim.path_loss_table.law, tx)
+        self.agent = np.asarray(agent, dtype=bool)                   # links that have an action column: the only ones ever moved
+        if self.agent.shape != (self.n,):
+            raise ValueError('the agent mask does not match the env')
+        self.own = None                              # the five outputs this object owns, allocated by the first call without out=
+        self.tx, self.rx, self.cols = (torch.as_tensor(a, device=device) for a in (tx, rx, cols))
+        self.ptrs = tuple(t.data_ptr() for t in (self.tx, self.rx, self.cols))
+        self._movable = None                         # (key, tensor) of the last call: a repeated mask is not uploaded again
+
+    def words(self, allowed):
+        """None, or the packed words of `allowed` (bool [N, R], tensor or array) as an int32 tensor on the device."""
+        if allowed is None:
+            return None
+        torch = self.torch
+        mask = torch.as_tensor(allowed, device=self.device) if not torch.is_tensor(allowed) else allowed.to(self.device)
+        if tuple(mask.shape) != (self.n, self.r) or mask.dtype != torch.bool:
+            raise ValueError(f'allowed must be bool [{self.n}, {self.r}] (link, RB) or None')
+        return pack_allowed(mask, torch).contiguous()
+
+    def movable(self, movable):
+        """uint8 [N] on the device: the agent links (None), or those of them `movable` (bool [N], array or tensor) marks."""
+        torch = self.torch
+        if movable is None:
+            host = self.agent
+        else:
+            host = movable.cpu().numpy() if torch.is_tensor(movable) else np.asarray(movable)
+            if host.shape != (self.n,) or host.dtype != np.bool_:
+                raise ValueError(f'movable must be bool [{self.n}] (link) or None')
+            host = host & self.agent
+        key = host.tobytes()
+        if self._movable is None or self._movable[0] != key:
+            self._movable = (key, torch.as_tensor(host.astype(np.uint8), device=self.device))
+        return self._movable[1]
+
+    def outputs(self, out):
+        torch = self.torch
+        shapes = ((self.b, self.n), (self.b, self.n), (self.b,), (self.b,), (self.b,))
+        dtypes = (torch.int32, torch.float32, torch.int32, torch.int32, torch.uint8)
+        if out is None:
+            if self.own is None:
+                self.own = tuple(torch.empty(s, dtype=dt, device=self.device) for s, dt in zip(shapes, dtypes))
+            return self.own
+        ok = isinstance(out, (tuple, list)) and len(out) == 5 and all(
+            torch.is_tensor(o) and tuple(o.shape) == s and o.dtype == dt and o.is_contiguous() and o.device == self.device
+            for o, s, dt in zip(out, shapes, dtypes))
+        if not ok or len({o.data_ptr() for o in out}) != 5:
+            raise ValueError(f'out must be (rb, sinr_db, rounds, moves, converged): contiguous int32 {list(shapes[0])}, float32 '
+                             f'{list(shapes[1])}, int32 [{self.b}], int32 [{self.b}] and uint8 [{self.b}] tensors on {self.device} '
+                             'that do not share memory')
+        return tuple(out)
+
+    def env_mask(self, env_mask):
+        torch = self.torch
+        if env_mask is None:
+            return None
+        m = env_mask if torch.is_tensor(env_mask) else torch.as_tensor(np.asarray(env_mask))
+        if tuple(m.shape) != (self.b,) or m.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f'env_mask must be bool or uint8 [{self.b}] or None')
+        return m.to(device=self.device, dtype=torch.uint8).contiguous()
+
+    def solve(self, t: dict, allowed, movable, min_gain_db: float, max_rounds: int, out, stream: int,
+              env_mask=None) -> BestResponseDynamicsResult:
+        """movable: the tensor movable() returns; allowed: what the caller passed."""
+        if isinstance(max_rounds, bool) or not isinstance(max_rounds, (int, np.integer)) or not 0 <= max_rounds <= _native.BRDYN_MAX_ROUNDS:
+            raise ValueError(f'max_rounds must be an int in [0, {_native.BRDYN_MAX_ROUNDS}], got {max_rounds!r}')
+        if isinstance(min_gain_db, bool) or not isinstance(min_gain_db, (int, float, np.integer, np.floating)) \
+                or math.isnan(min_gain_db) or min_gain_db < 0.0:
+            raise ValueError(f'min_gain_db must be a number >= 0, got {min_gain_db!r}')
+        need = lds_bytes(self.n, self.r, self.law != _native.BRDYN_LAW_INV_SQUARE, allowed is not None)
+        if need > _native.BRDYN_MAX_LDS_BYTES:
+            raise ValueError(f'best_response_dynamics() keeps an env in the LDS of one workgroup: {self.n} links on {self.r} RBs need '
+                             f'{need} bytes, more than the {_native.BRDYN_MAX_LDS_BYTES} a workgroup can have')
+        rb, sinr, rounds, moves, conv = self.outputs(out)
+        words = self.words(allowed)                  # lives until the launch is enqueued; the stream orders its release behind it
+        mask = self.env_mask(env_mask)
+        _native.best_response_dynamics(t['pos_x'].data_ptr(), t['pos_y'].data_ptr(), t['rb'].data_ptr(), t['pwr'].data_ptr(), *self.ptrs,
+                                       self.law, self.pow_k, self.b, self.d, self.n, self.r, 0 if words is None else words.data_ptr(),
+                                       movable.data_ptr(), float(min_gain_db), int(max_rounds), 0 if mask is None else mask.data_ptr(),
+                                       rb.data_ptr(), sinr.data_ptr(), rounds.data_ptr(), moves.data_ptr(), conv.data_ptr(), stream)
+        return BestResponseDynamicsResult(rb, sinr, rounds, moves, conv)
+
+    def close(self) -> None:
+        pass

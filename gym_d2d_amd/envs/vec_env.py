@@ -22,7 +22,7 @@ from typing import Optional
 
 import numpy as np
 
-from .. import _native, best_response, graph, marginal, power_control, sensing
+from .. import _native, best_response, best_response_dynamics, graph, marginal, power_control, sensing
 from .. import mobility as mobility_mod
 from .. import queues as queues_mod
 from ..path_loss_table import CHANNEL, PER_STEP, positions_move_unserved
@@ -273,6 +273,8 @@ class VecD2DEnv:
         # target-SINR power control (power_control()): nothing is loaded, allocated or launched unless it is called
         self._powerctl = None
         self._power_levels = None                  # power_control_actions(): (lowest power, power levels) of every agent link's class
+        # sequential best-response dynamics (best_response_dynamics()): likewise nothing unless it is called
+        self._brdyn = None
 
     def _setup_autoreset(self) -> None:
         """Refuse what a device-side per-env reset cannot serve, then allocate the per-env bookkeeping: pending / episode are bound
@@ -886,6 +888,58 @@ class VecD2DEnv:
             self._power_levels = tuple(torch.as_tensor(a[first:], device=self.device) for a in (p_min, p_max - p_min + 1))
         return power_control.encode_actions(self._t['rb'], power, *self._power_levels, first)
 
+    # ------------------------------------------------------------------ sequential best-response dynamics
+    def _best_response_dynamics_kernel(self):
+        if self._brdyn is None:
+            why = best_response_dynamics.refusal(self.simulator, self.export_actions, self.use_torch)
+            if why:
+                raise ValueError(why)
+            agent = np.arange(self.num_links) >= self.num_links - self.num_agents
+            self._brdyn = best_response_dynamics.BestResponseDynamics(self.simulator, self.num_links, agent, torch, self.device)
+        return self._brdyn
+
+    def best_response_dynamics(self, allowed=None, movable=None, min_gain_db: float = 3.0, max_rounds: int = 16, out=None,
+                               env_mask=None):
+        """Sequential (Gauss-Seidel) best response on the RBs, with positions and powers as the last step left them: (rb int32
+        [B, N], sinr_db float32 [B, N], rounds int32 [B], moves int32 [B], converged uint8 [B]), a tuple with those names.
+
+        Round after round the movable links take turns in ascending link index.  A link evaluates the SINR it would have on every
+        allowed RB with every other link where it is NOW - the moves of this round included - picks the best one as best_rb() does
+        (equal values to the lowest r) and moves there at once if that gains more than min_gain_db over its own RB.  A round that
+        moves nobody ends the dynamics (converged 1, rounds = the rounds that moved a link); so do max_rounds rounds that each moved
+        one (converged 0, rounds == max_rounds; max_rounds = 0 returns the RBs as they are).  Every value is a value of sense() for
+        that state bit for bit, so the whole trajectory is what a loop of best_rb() and step() per link would give; sinr_db is the
+        step's sinr_db for rb, NaN for a link on no RB.  Selfish SINR response is no potential game: without hysteresis envs can
+        cycle until the cap, and converged is a result, not a promise.  All turns of an env run in one workgroup of one kernel
+        launch (csrc/d2d_brdyn.hip) out of LDS.  Valid after reset() and after every step(), autoreset steps included, as sense() is.
+
+        allowed: bool [N, R] (tensor or array) as best_rb() takes it; None: every RB.  movable: bool [N], the links that take
+        turns; None: every agent link.  Links on fixed actions (cue_actions='traffic') never move; neither does a link on no RB
+        (rb outside [0, R)), a link with no allowed RB, or a link whose gain is NaN; links that do not move still interfere, unless
+        they are on no RB.  min_gain_db >= 0.  env_mask: bool / uint8 [B], envs whose entry is 0 keep their rows; None: all.
+
+        Torch path only: enqueued on torch's current stream, nothing is synchronised; the five tensors the env owns, rewritten by
+        every call (clone them to keep them), or `out` = (rb, sinr_db, rounds, moves, converged), contiguous int32 / float32 [B, N],
+        int32 / int32 / uint8 [B] on the env's device.  Serves what sense() serves, as far as an env's links, allowed words and RB
+        membership fit the LDS of one workgroup; ValueError for export_actions=False, ShadowingPathLoss, every table route, pinned
+        device_config coordinates float32 cannot hold."""
+        k = self._best_response_dynamics_kernel()
+        mov = k.movable(movable)
+        self._follow_torch_stream()
+        return k.solve(self._t, allowed, mov, min_gain_db, max_rounds, out, self._stream_ptr, env_mask)
+
+    def best_response_dynamics_actions(self, allowed=None, movable=None, min_gain_db: float = 3.0, max_rounds: int = 16):
+        """best_response_dynamics() as an action tensor, int32 [B, num_agents], ready for step(): every agent link on its solved RB
+        at its current power level (as the decoded planes hold it), encoded rb * power levels + level.  Links on fixed actions
+        (cue_actions='traffic') have no column.  Composes with power_control_actions() the way best_response_actions() does: one
+        call picks RBs, the other picks powers."""
+        rb = self.best_response_dynamics(allowed, movable, min_gain_db, max_rounds)[0]
+        if self._action_levels is None:
+            p = self.num_pwr_actions
+            levels = ([p[self._cue_kind]] * self.num_cues if self.cue_actions == 'agent' else []) + [p['due']] * self.num_due_pairs
+            self._action_levels = torch.as_tensor(np.asarray(levels, dtype=np.int32), device=self.device)
+        return best_response_dynamics.encode_actions(rb, self._t['pwr'], self._action_levels, self.num_links - self.num_agents)
+
     def _observe(self, view):
         extra = {}
         if self._senses:
@@ -952,4 +1006,7 @@ class VecD2DEnv:
         if self._powerctl is not None:
             self._powerctl.close()
             self._powerctl = None
+        if self._brdyn is not None:
+            self._brdyn.close()
+            self._brdyn = None
         self.simulator.handle.close()
