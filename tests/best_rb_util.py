@@ -9,8 +9,16 @@ from oracle import d2d_oracle as orc
 from sim_util import default_links, random_layout
 
 BAR = 1e-5                                   # the project's bar on dB quantities: |d| <= BAR max(|ref|, 1)
-SHAPES = {7: (3, 4), 41: (11, 30), 131: (31, 100), 300: (100, 200)}     # links: (cues, due pairs)
+SHAPES = {7: (3, 4), 41: (11, 30), 131: (31, 100), 300: (100, 200), 2048: (512, 1536)}     # links: (cues, due pairs)
 DIRECT_N, DIRECT_R = (7, 131, 300), (1, 3, 33, 70)
+# the direct launches past those: (links, R, law, envs)
+#   2048 links at a small R: EIGHT receiver blocks (grid.y; 2 at most up to 300 links), link index 2047 in the sort key rb << 11 | j,
+#   and with a power law more than 64 KiB of LDS in d2d_bestrb.hip - the MaxDynamicSharedMemorySize branch, which d2d_sense.hip takes
+#   for the reference block of the same case as well
+#   41 links on 330 RBs: an allowed mask of ELEVEN words with a ragged tail of 10 bits (R = 70 has three)
+DIRECT_LARGE = ((2048, 3, 'ld35', 2), (2048, 3, 'mixed', 2), (2048, 5, 'ld2', 2), (41, 330, 'ld2', 3))
+# the oracle comparison at 2048 links: one env, these links on every RB (nine oracle envs of 2048 x 2048 pairs each)
+LARGE_ORACLE = (2048, 3, 'ld35', (0, 1024, 2047))
 LAWS = ('ld2', 'ld35', 'urban')              # the models the oracle knows; 'mixed' below has per-device exponents (the general law)
 # the oracle comparison: every R at 7 links, the two R either side of the 32-RB grouping at 41 (B0 * N * R oracle envs each)
 # ... in a 40 m cell: at the default 500 m most interferers under the steeper laws arrive far below the noise floor, so an occupied RB
@@ -79,3 +87,17 @@ def oracle_side(n, r, law):
     assert (np.where(cand, ref, top[:, :, None])[only_empty] == top[only_empty][:, None]).all()       # exact ties, not near ones
     decided = (cand.sum(axis=-1) == 1) | only_empty
     return ref, cand.argmax(axis=-1), decided
+
+
+@lru_cache(maxsize=None)
+def large_oracle_side():
+    """oracle_side() for LARGE_ORACLE: (case, ref float64 [1, K, R], expect int [1, K], decided bool [1, K]) of its K links in env 0."""
+    n, r, law, links = LARGE_ORACLE
+    c = make_case(n, r, law, b=2, cell_radius=ORACLE_CELL_M)
+    links = np.asarray(links)
+    ref = rbs.counterfactual(c['pos'][:1], c['tx'], c['rx'], c['rb'][:1], c['pwr'][:1], c['ocols'], c['spec'], r, links=links)
+    top = ref.max(axis=-1)
+    cand = ref >= (top - 2.0 * BAR * np.maximum(np.abs(top), 1.0))[:, :, None]
+    only_empty = ~(cand & occupied(c['rb'][:1], r)[:, links]).any(axis=-1)
+    decided = (cand.sum(axis=-1) == 1) | only_empty
+    return c, ref, cand.argmax(axis=-1), decided

@@ -32,7 +32,10 @@ CAP = 0.25                                   # at most this share of a case's en
 B = 64
 CUE_MAX, DUE_MAX = 23, 20                    # EnvConfig's defaults: 24 CUE and 21 DUE power levels
 
-# name: (cues, due pairs, R, law, cell radius m, target dB {'cue', 'due'}, links put on no RB)
+# name: (cues, due pairs, R, law, cell radius m, target dB {'cue', 'due'}, links put on no RB), then optionally a dict: b (envs; large
+# shapes take 4 to 8, not 64), seed, and every (only the links j % every == 0, 1023, 1024 and N - 1 get the class target, all others one
+# that their lowest power meets: they stay at p_min and still interfere.  With every link of 2048 raised through interior powers an
+# env has some 6000 update-deciding ceilings, each within W of a whole number with probability 4e-4: every env would be ambiguous)
 CASES = {
     'n37_r5': (12, 25, 5, 'ld2', 500.0, {'cue': -4.0, 'due': 9.0}, 0),            # not a multiple of the wave; mixed group sizes
     'n300_r7': (100, 200, 7, 'ld2', 500.0, {'cue': -22.0, 'due': -2.0}, 0),       # more links than threads: several links per lane
@@ -42,7 +45,14 @@ CASES = {
     'n50_r6_hata': (20, 30, 6, 'urban', 500.0, {'cue': -8.0, 'due': 14.0}, 0),    # COST-Hata: the pow-k law
     'n50_r6_ld35': (20, 30, 6, 'ld35', 120.0, {'cue': -6.0, 'due': 12.0}, 0),     # exponent 3.5: pow-k as well, a compact cell
     'n50_r6_no_rb': (20, 30, 6, 'ld2', 500.0, {'cue': -4.0, 'due': 9.0}, 1),      # one link per env on no RB
+    # ---- more than 64 KiB of LDS: the MaxDynamicSharedMemorySize branch of d2d_powerctl.hip (76 bytes per link with a power law, 68
+    # with the inverse-square law, 4 per RB)
+    'n1000_r64_ld35': (300, 700, 64, 'ld35', 120.0, {'cue': -6.0, 'due': 12.0}, 0, dict(b=8, every=2, seed=1)),       # 76 KiB, just past
+    # 137 KiB; link index 2047 in the sort key rb << 11 | j, and RB groups whose (first, last + 1) slots in the two 16-bit halves of
+    # a range word lie above 1023
+    'n2048_r256': (512, 1536, 256, 'ld2', 500.0, {'cue': -4.0, 'due': 14.0}, 0, dict(b=4, every=8)),
 }
+LARGE = ('n1000_r64_ld35', 'n2048_r256')
 # the general power law (per-device exponents) has no oracle model: it runs the checks that need none
 MIXED = ('n50_r6_mixed', (20, 30, 6))
 ONE_RB = 'n96_r1'
@@ -92,6 +102,8 @@ def state(cues, dues, r, seed, cell_radius=500.0, no_rb=0, b=B):
 
 
 def target_vector(target, cues, dues):
+    if isinstance(target, np.ndarray):
+        return np.asarray(target, dtype=np.float64)
     if isinstance(target, dict):
         return np.array([target['cue']] * cues + [target['due']] * dues, dtype=np.float64)
     return np.full(cues + dues, float(target))
@@ -146,12 +158,17 @@ def solve(pos, tx, rx, rb, pwr, cols, spec, r, target, p_min, p_max, adjustable=
 @lru_cache(maxsize=None)
 def make_case(name):
     """The seeded state of a case and everything the oracle needs for it."""
-    cues, dues, r, law, cell, target, no_rb = CASES[name]
-    pos, raw, rb, pwr = state(cues, dues, r, sum(map(ord, name)), cell, no_rb)
+    cues, dues, r, law, cell, target, no_rb = CASES[name][:7]
+    o = dict(dict(b=B, every=None, seed=None), **(CASES[name][7] if len(CASES[name]) > 7 else {}))
+    pos, raw, rb, pwr = state(cues, dues, r, sum(map(ord, name)) if o['seed'] is None else o['seed'], cell, no_rb, o['b'])
     tx, rx, _ = default_links(cues, dues)
     p_min, p_max, levels = bounds(cues, dues)
+    if o['every']:
+        j = np.arange(cues + dues)
+        chosen = (j % o['every'] == 0) | (j == 1023) | (j == 1024) | (j == cues + dues - 1)
+        target = np.where(chosen, target_vector(target, cues, dues), -200.0)
     return SimpleNamespace(name=name, cues=cues, dues=dues, n=cues + dues, r=r, law=law, cell=cell, target=target, pos=pos, raw=raw,
-                           rb=rb, pwr=pwr, tx=tx, rx=rx, p_min=p_min, p_max=p_max, levels=levels, spec=models()[law][1],
+                           rb=rb, pwr=pwr, b=o['b'], tx=tx, rx=rx, p_min=p_min, p_max=p_max, levels=levels, spec=models()[law][1],
                            cols=orc.device_columns(*orc.device_configs(cues, dues)[1:]))
 
 

@@ -7,21 +7,23 @@ from golden_util import GOLDEN_DIR
 from oracle import d2d_oracle as orc
 
 
-def counterfactual(pos, link_tx, link_rx, rb, pwr, cols, spec, num_rbs):
+def counterfactual(pos, link_tx, link_rx, rb, pwr, cols, spec, num_rbs, links=None):
     """sinr_db[b, i, r] of the oracle's step in the env where link i of env b alone moved to RB r: ONE oracle call on
-    B0 * N * R envs.  pos [B0, D, 2], rb / pwr [B0, N]."""
+    B0 * N * R envs.  pos [B0, D, 2], rb / pwr [B0, N].  links: the links i to do it for (None: all); the result is then
+    [B0, len(links), R] - at 2048 links the oracle's [envs, N, N] pair arrays allow a few dozen envs, not B0 * N * R."""
     pos = np.asarray(pos, dtype=np.float64)
     rb = np.asarray(rb, dtype=np.int64); pwr = np.asarray(pwr, dtype=np.int64)
     b0, n = rb.shape
     r = int(num_rbs)
-    big_rb = np.broadcast_to(rb[:, None, None, :], (b0, n, r, n)).copy()
-    idx = np.arange(n)
-    big_rb[:, idx, :, idx] = np.arange(r)[None, None, :]                  # env (b, i, r): link i sits on RB r
-    big_pwr = np.broadcast_to(pwr[:, None, None, :], (b0, n, r, n)).reshape(b0 * n * r, n)
-    big_pos = np.broadcast_to(pos[:, None, None], (b0, n, r) + pos.shape[1:]).reshape((b0 * n * r,) + pos.shape[1:])
-    res = orc.step(big_pos, link_tx, link_rx, big_rb.reshape(b0 * n * r, n), big_pwr, cols, spec)
-    sinr = res['sinr_db'].reshape(b0, n, r, n)
-    return sinr[:, idx, :, idx].transpose(1, 0, 2)                        # [b0, n, r]: entry i of env (b, i, r)
+    idx = np.arange(n) if links is None else np.asarray(links, dtype=np.int64)
+    k = len(idx)
+    big_rb = np.broadcast_to(rb[:, None, None, :], (b0, k, r, n)).copy()
+    big_rb[:, np.arange(k), :, idx] = np.arange(r)[None, None, :]         # env (b, i, r): link i sits on RB r
+    big_pwr = np.broadcast_to(pwr[:, None, None, :], (b0, k, r, n)).reshape(b0 * k * r, n)
+    big_pos = np.broadcast_to(pos[:, None, None], (b0, k, r) + pos.shape[1:]).reshape((b0 * k * r,) + pos.shape[1:])
+    res = orc.step(big_pos, link_tx, link_rx, big_rb.reshape(b0 * k * r, n), big_pwr, cols, spec)
+    sinr = res['sinr_db'].reshape(b0, k, r, n)
+    return sinr[:, np.arange(k), :, idx].transpose(1, 0, 2)               # [b0, k, r]: entry i of env (b, i, r)
 
 
 def interference_mw(pos, link_tx, link_rx, rb, pwr, cols, spec, num_rbs):

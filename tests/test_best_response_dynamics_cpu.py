@@ -255,13 +255,28 @@ def test_hand_computed_answers_on_three_links_and_two_rbs():
 def test_oracle_ambiguity_of_the_gpu_cases_stays_inside_the_cap(name):
     """The seeds of the GPU test's oracle comparison, on the oracle alone: at most 25 % of a case's envs are ambiguous
     (best_response_dynamics_util), and the cases exercise what they are there for."""
+    from gym_d2d_amd import _native
+    from gym_d2d_amd.best_response_dynamics import lds_bytes
     c, o = bu.make_case(name), bu.oracle_side(name)
     share = float(o.ambiguous.mean())
-    print(f'{name}: {share:.2%} of {bu.B} envs ambiguous; rounds {o.rounds.min()}..{o.rounds.max()}, moves {o.moves.min()}..'
-          f'{o.moves.max()}, converged {o.converged.mean():.0%}')
-    assert o.ambiguous.shape == (bu.B,) and share <= bu.CAP
+    lds = lds_bytes(c.n, c.r, c.law != 'ld2', False)
+    print(f'{name}: {share:.2%} of {c.b} envs ambiguous; rounds {o.rounds.min()}..{o.rounds.max()}, moves {o.moves.min()}..'
+          f'{o.moves.max()}, converged {o.converged.mean():.0%}; {lds} bytes of LDS; moves into each RB block '
+          f'{np.bincount(bu.rb_blocks(c.r), weights=o.dest).astype(int).tolist()}, {int(o.dest[256:].sum())} of them at r >= 256, '
+          f'{int(o.moved[1024:].sum())} by links j >= 1024')
+    assert o.ambiguous.shape == (c.b,) and share <= bu.CAP
+    assert (~o.ambiguous).sum() >= 3                                    # a small batch still compares something
     assert o.on_rb.all() and np.isfinite(o.sinr_db).all()
-    assert (o.moves > 0).any() and (o.rounds <= bu.MAX_ROUNDS).all() and ((o.rounds == bu.MAX_ROUNDS) <= ~o.converged).all()
+    assert (o.moves > 0).any() and (o.rounds <= c.max_rounds).all() and ((o.rounds == c.max_rounds) <= ~o.converged).all()
     assert (o.moves >= o.rounds).all() and ((o.rb != c.rb).sum(axis=1) <= o.moves).all()
-    if name != 'n20_r64':
+    assert o.dest.sum() == o.moves.sum() == o.moved.sum()
+    if name not in ('n20_r64', 'n320_r2500'):                           # (those two: mostly empty RBs, one round settles it)
         assert o.rounds.max() >= 2                                      # later links answer earlier moves
+    # what the multi-wave and large-LDS cases are there for, on the reference alone
+    assert lds <= _native.BRDYN_MAX_LDS_BYTES
+    if c.r > 64:
+        assert bu.covers(o.dest, c.r)                                   # every wave holds a winner, both RBs of a lane past 256
+    if name in ('n2048_r256', 'n320_r2500'):
+        assert lds > 64 * 1024
+    if c.n > 1024:
+        assert o.moved[1024:].sum() > 0 and (c.movable is None or not o.moved[~c.movable].any())

@@ -112,6 +112,41 @@ def test_direct_launch_equals_the_sensed_block_reduced_on_the_host(n, r, law):
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
+@pytest.mark.parametrize('n,r,law,b', bru.DIRECT_LARGE)
+def test_direct_launch_at_2048_links_and_on_330_rbs(n, r, law, b):
+    """best_rb_util.DIRECT_LARGE says which path each case is there for.  Where the two kernels disagree, the float64 side
+    (test_2048_links_against_the_oracle_counterfactual) says which one is wrong."""
+    c = bru.make_case(n, r, law, b=b)
+    blk = _sense(c, (n, r, law, b))
+    assert np.isfinite(blk).all()
+    best, sinr, gain = _best(c)
+    some, on_rb = _check_against_block(c, blk, best, sinr, gain)
+    assert some.all() and not on_rb.all() and on_rb.any()
+    assert (gain[on_rb] >= 0.0).all() and (gain[on_rb & (best == c['rb'])] == 0.0).all()
+    if n == 2048:                                                       # the last link and the last receiver block have answers of their own
+        assert on_rb[:, 1024:].any() and len(np.unique(best[:, 1792:])) > 1 and (gain[:, 1024:][on_rb[:, 1024:]] > 0.0).any()
+    for a, b2 in zip((best, sinr, gain), _best(c)):                     # two calls, the same bits
+        assert np.array_equal(a.view(np.uint32), b2.view(np.uint32))
+
+
+def test_2048_links_against_the_oracle_counterfactual():
+    n, r, law, links = bru.LARGE_ORACLE
+    c, ref, expect, decided = bru.large_oracle_side()
+    links = np.asarray(links)
+    best, sinr, gain = (a[:1, links] for a in _best(c))
+    blk = _sense(c, (n, r, law, 'oracle cell'))[:1, links]
+    top = ref.max(axis=-1)
+    print(f'{n} links, {r} RBs, {law}, links {links.tolist()} of env 0: best_sinr_db vs the oracle rel_err {rel_err(sinr, top):.3e}, the sensed '
+          f'block {rel_err(blk, ref):.3e}; {int((~decided).sum())} of {decided.size} left out as near-ties')
+    assert decided.sum() >= decided.size - 1
+    assert rel_err(blk, ref) <= BAR and rel_err(sinr, top) <= BAR
+    assert np.array_equal(best[decided], expect[decided])
+    on_rb = ((c['rb'] >= 0) & (c['rb'] < r))[:1, links]
+    own = np.take_along_axis(ref, np.where(on_rb, c['rb'][:1, links], 0)[:, :, None], axis=2)[:, :, 0]
+    assert (np.abs(gain - (top - own))[on_rb] <= 2 * BAR * np.maximum(np.maximum(np.abs(top), np.abs(own)), 1.0)[on_rb]).all()
+    assert np.isnan(gain[~on_rb]).all()
+
+
 # ------------------------------------------------------------------------------------------ the oracle
 @pytest.mark.parametrize('n,r,law', bru.ORACLE_CASES)
 def test_against_the_oracle_counterfactual(n, r, law):
@@ -138,10 +173,10 @@ def test_against_the_oracle_counterfactual(n, r, law):
 
 
 # ------------------------------------------------------------------------------------------ allowed, env_mask
-@pytest.mark.parametrize('n,r,law', [(131, 70, 'ld35'), (300, 33, 'ld2'), (7, 3, 'mixed')])
+@pytest.mark.parametrize('n,r,law', [(131, 70, 'ld35'), (300, 33, 'ld2'), (7, 3, 'mixed'), (41, 330, 'ld2'), (2048, 3, 'ld35')])
 def test_allowed_mask_restricts_the_argmax(n, r, law):
-    c = bru.make_case(n, r, law)
-    blk = _sense(c, (n, r, law))
+    c = bru.make_case(n, r, law, **({'b': 2} if n == 2048 else {}))
+    blk = _sense(c, (n, r, law, 2) if n == 2048 else (n, r, law, 3) if r == 330 else (n, r, law))
     rng = np.random.default_rng(n + r)
     allowed = rng.random((n, r)) < 0.5
     allowed[:, 0] |= ~allowed.any(axis=1)                               # every row has one ...

@@ -27,7 +27,7 @@ def _case(name):
         cues, dues, r = pcu.MIXED[1]
         pos, raw, rb, pwr = pcu.state(cues, dues, r, 77)
         p_min, p_max, levels = pcu.bounds(cues, dues)
-        return SimpleNamespace(name=name, cues=cues, dues=dues, n=cues + dues, r=r, law='mixed', cell=500.0,
+        return SimpleNamespace(name=name, cues=cues, dues=dues, n=cues + dues, r=r, law='mixed', cell=500.0, b=B,
                                target={'cue': -4.0, 'due': 9.0}, pos=pos, raw=raw, rb=rb, pwr=pwr, p_min=p_min, p_max=p_max, levels=levels)
     return pcu.make_case(name)
 
@@ -39,7 +39,10 @@ def _build(name, cue_actions='agent'):
         from gym_d2d_amd.envs import VecD2DEnv
         c = _case(name)
         cfg = {'num_rbs': c.r, 'num_cues': c.cues, 'num_due_pairs': c.dues, 'path_loss_model': pcu.models()[c.law][0]}
-        env = VecD2DEnv(cfg, num_envs=B, cue_actions=cue_actions)
+        if c.n > 300:                                                   # no [B, N, 6 N] observation block at these sizes
+            from gym_d2d_amd.envs.obs_fn import SignalPlanesObsFunction
+            cfg['obs_fn'] = SignalPlanesObsFunction
+        env = VecD2DEnv(cfg, num_envs=c.b, cue_actions=cue_actions)
         env.reset(seed=3)
         env.simulator.set_positions(c.pos)
         first = c.n - env.num_agents
@@ -109,8 +112,14 @@ def test_solved_powers_are_a_fixed_point_of_the_step_itself(name):
     assert _native.powerctl_launches == before + 1 and env._powerctl.law == law
     power, sinr, iters, conv = res
     assert power.dtype == np.int32 and sinr.dtype == np.float32 and iters.dtype == np.int32 and conv.dtype == np.uint8
-    assert power.shape == sinr.shape == (B, c.n) and iters.shape == conv.shape == (B,)
+    assert power.shape == sinr.shape == (c.b, c.n) and iters.shape == conv.shape == (c.b,)
     assert (conv == 1).all() and (iters < 64).all()
+    if name in pcu.LARGE:
+        # more than 64 KiB of LDS (d2d_powerctl.hip: 68 / 76 bytes per link, 4 per RB), and the sweeps reach the upper half of the
+        # links: test_power_control_cpu.py asserts that on the reference, here the kernel's own powers show it
+        assert c.n * (68 if c.law == 'ld2' else 76) + 4 * c.r > 64 * 1024
+        lo = min(1024, c.n // 2)
+        assert (iters >= 3).all() and ((power > c.p_min[None]) & (power < c.p_max[None]))[:, lo:].any(axis=1).all()
     assert (power >= c.p_min[None]).all() and (power <= c.p_max[None]).all()
     pwr_h, on = _step_check(env, c, raw, res, c.target)
     assert np.array_equal(power[~on], c.pwr[~on])                       # on no RB: the power is kept
@@ -134,9 +143,12 @@ def test_against_the_oracle_restatement(name):
     fin = o.on_rb & ok[:, None]
     dev = np.abs(sinr.astype(np.float64) - o.sinr_db)[fin]
     same = (power == o.power_dbm).all(axis=1)
-    print(f'{name}: {share:.2%} of {B} envs ambiguous; power_dbm equal in {same.mean():.2%} of all envs; sinr_db rel_err '
+    print(f'{name}: {share:.2%} of {c.b} envs ambiguous; power_dbm equal in {same.mean():.2%} of all envs; sinr_db rel_err '
           f'{rel_err(sinr[fin], o.sinr_db[fin]):.3e}, largest deviation {dev.max():.3e} dB (W = {pcu.W:g}); sweeps {iters.min()}..{iters.max()}')
-    assert share <= pcu.CAP
+    assert share <= pcu.CAP and ok.sum() >= 3
+    if name in pcu.LARGE:                                               # the reference raises links of the upper half after sweep 1
+        later = (o.power_dbm != o.after_one) & (o.power_dbm > c.p_min[None]) & (o.power_dbm < c.p_max[None])
+        assert o.iters.min() >= 3 and later[:, min(1024, c.n // 2):].any(axis=1).all()
     assert np.array_equal(power[ok], o.power_dbm[ok])
     assert np.array_equal(iters[ok], o.iters[ok]) and np.array_equal(conv[ok], o.converged[ok].astype(np.uint8))
     assert rel_err(sinr[fin], o.sinr_db[fin]) <= BAR
