@@ -1,10 +1,53 @@
-"""The yardsticks of the per-RB sensing tests: the oracle-based counterfactual and the fp64 interference sum."""
+"""What the read-side GPU tests share (test_gpu_rb_sensing.py, test_gpu_neighbors.py, test_gpu_marginal.py): their case table with its
+models and the read-back of an env's state, and the yardsticks of the per-RB sensing tests - the oracle-based counterfactual and the
+fp64 interference sum."""
 import json
 
 import numpy as np
 
 from golden_util import GOLDEN_DIR
 from oracle import d2d_oracle as orc
+
+
+def _models():
+    from gym_d2d_amd.path_loss import AreaType, CostHataPathLoss, LogDistancePathLoss
+
+    class Ple35(LogDistancePathLoss):
+        def __init__(self, f):
+            super().__init__(f, ple=3.5)
+
+    class Urban(CostHataPathLoss):
+        def __init__(self, f):
+            super().__init__(f, AreaType.URBAN)
+
+    class Suburban(CostHataPathLoss):
+        def __init__(self, f):
+            super().__init__(f, AreaType.SUBURBAN)
+    return {'ld2': (LogDistancePathLoss, orc.PathLossSpec('log_distance', 2.1, ple=2.0)),
+            'ld35': (Ple35, orc.PathLossSpec('log_distance', 2.1, ple=3.5)),
+            'urban': (Urban, orc.PathLossSpec('cost_hata', 2.1, area='urban')),
+            'suburban': (Suburban, orc.PathLossSpec('cost_hata', 2.1, area='suburban'))}
+
+
+# name: (B0, cues, due pairs, RBs, model, cue_actions, downlink traffic model)
+CASES = {
+    'small_ld2_agent': (3, 8, 8, 5, 'ld2', 'agent', False),
+    'mid_ld35_agent': (2, 64, 96, 24, 'ld35', 'agent', False),
+    'crowded_urban_traffic_up': (2, 64, 64, 8, 'urban', 'traffic', False),          # 16 links per RB
+    'empty_suburban_traffic_down': (2, 6, 6, 40, 'suburban', 'traffic', True),      # 12 links on 40 RBs
+    'mid_ld2_traffic_down': (2, 24, 40, 16, 'ld2', 'traffic', True),
+    'small_urban_agent': (3, 8, 8, 5, 'urban', 'agent', False),
+    'small_suburban_traffic_up': (3, 8, 8, 5, 'suburban', 'traffic', False),
+    'case07_device_config': None,                                                    # golden case07's per-device overrides
+}
+
+
+def _state(env):
+    import torch
+    t = env._t
+    torch.cuda.synchronize()
+    pos = np.stack([t['pos_x'].cpu().numpy(), t['pos_y'].cpu().numpy()], axis=-1).astype(np.float64)
+    return pos, t['rb'].cpu().numpy().astype(np.int64), t['pwr'].cpu().numpy().astype(np.int64)
 
 
 def counterfactual(pos, link_tx, link_rx, rb, pwr, cols, spec, num_rbs, links=None):

@@ -3,7 +3,10 @@
 The yardstick is the oracle's own step on the B0 * N envs in which one link sits on an RB of its own (marginal_util.leave_one_out),
 which test_marginal_cpu.py ties to the reference at 1e-9; the bar is the project's 1e-5 (golden_util.rel_err: |d| <= 1e-5 max(|ref|,
 1), Mbps) on BOTH planes.  Every entry is compared: the layouts come from sim_util.random_layout, which never places two interacting
-devices on one point.
+devices on one point, and the cases are small enough that no link - and no victim on its RB, with or without the link - has an SINR
+within twice the bar of its receiver's sensitivity threshold, where a capacity flips between 0 and its whole value and no bar-limited
+comparison can call it (read_side_util.leave_one_out_direct's `decided`; asserted on the float64 reference of every case here, and for
+the states that need no GPU to rebuild in test_marginal_cpu.py).
 
 Measured on an MI355X (every test prints its rel_err): harm 3.5e-8 - 1.9e-7 and difference 8.9e-8 - 3.5e-7 over the nine cases,
 1.8e-7 / 6.4e-7 at full size, 2.5 - 4.8e-7 against the simulator's own second step (CHANGELOG.md)."""
@@ -15,8 +18,11 @@ import numpy as np
 import pytest
 
 import marginal_util as mu
+import rb_sensing_util as rbs
+import read_side_util as rsu
 from golden_util import load_case, rel_err
 from oracle import d2d_oracle as orc
+from rb_sensing_util import _models, _state
 from sim_util import env_config_for, oracle_spec, random_layout
 
 pytestmark = pytest.mark.gpu
@@ -25,46 +31,9 @@ ROOT = Path(__file__).resolve().parent.parent
 BAR = 1e-5
 
 
-def _models():
-    from gym_d2d_amd.path_loss import AreaType, CostHataPathLoss, LogDistancePathLoss
-
-    class Ple35(LogDistancePathLoss):
-        def __init__(self, f):
-            super().__init__(f, ple=3.5)
-
-    class Urban(CostHataPathLoss):
-        def __init__(self, f):
-            super().__init__(f, AreaType.URBAN)
-
-    class Suburban(CostHataPathLoss):
-        def __init__(self, f):
-            super().__init__(f, AreaType.SUBURBAN)
-    return {'ld2': (LogDistancePathLoss, orc.PathLossSpec('log_distance', 2.1, ple=2.0)),
-            'ld35': (Ple35, orc.PathLossSpec('log_distance', 2.1, ple=3.5)),
-            'urban': (Urban, orc.PathLossSpec('cost_hata', 2.1, area='urban')),
-            'suburban': (Suburban, orc.PathLossSpec('cost_hata', 2.1, area='suburban'))}
-
-
-# name: (B0, cues, due pairs, RBs, model, cue_actions, downlink traffic model) - test_gpu_rb_sensing.py's eight, and one_rb
-CASES = {
-    'small_ld2_agent': (3, 8, 8, 5, 'ld2', 'agent', False),
-    'mid_ld35_agent': (2, 64, 96, 24, 'ld35', 'agent', False),
-    'crowded_urban_traffic_up': (2, 64, 64, 8, 'urban', 'traffic', False),          # 16 links per RB
-    'empty_suburban_traffic_down': (2, 6, 6, 40, 'suburban', 'traffic', True),      # 12 links on 40 RBs
-    'mid_ld2_traffic_down': (2, 24, 40, 16, 'ld2', 'traffic', True),
-    'small_urban_agent': (3, 8, 8, 5, 'urban', 'agent', False),
-    'small_suburban_traffic_up': (3, 8, 8, 5, 'suburban', 'traffic', False),
-    'case07_device_config': None,                                                    # golden case07's per-device overrides
-    'one_rb': (2, 20, 30, 1, 'ld2', 'agent', False),                                 # N^2 pairs, cancellation, the long sums
-}
+# rb_sensing_util.CASES - name: (B0, cues, due pairs, RBs, model, cue_actions, downlink traffic model) - and one_rb
+CASES = dict(rbs.CASES, one_rb=(2, 20, 30, 1, 'ld2', 'agent', False))         # N^2 pairs, cancellation, the long sums
 _cache = {}
-
-
-def _state(env):
-    t = env._t
-    torch.cuda.synchronize()
-    pos = np.stack([t['pos_x'].cpu().numpy(), t['pos_y'].cpu().numpy()], axis=-1).astype(np.float64)
-    return pos, t['rb'].cpu().numpy().astype(np.int64), t['pwr'].cpu().numpy().astype(np.int64)
 
 
 def _build(name):
@@ -100,8 +69,10 @@ def _build(name):
     pos, rb, pwr = _state(env)
     tx, rx = env.simulator.link_tx, env.simulator.link_rx
     ref_diff, ref_harm, ref_cap, _ = mu.leave_one_out(pos, tx, rx, rb, pwr, cols, spec, r)
+    decided = rsu.leave_one_out_direct(dict(b=rb.shape[0], n=rb.shape[1], r=r, pos=pos, tx=tx, rx=rx, rb=rb, pwr=pwr, ocols=cols),
+                                       pl=orc.pair_path_loss_db(spec, pos, np.asarray(tx), np.asarray(rx), cols))[3]
     out = dict(env=env, diff=diff, harm=harm, cap=info['capacity_mbps'].cpu().numpy(), pos=pos, rb=rb, pwr=pwr, tx=tx, rx=rx,
-               cols=cols, spec=spec, r=r, ref_diff=ref_diff, ref_harm=ref_harm, ref_cap=ref_cap)
+               cols=cols, spec=spec, r=r, ref_diff=ref_diff, ref_harm=ref_harm, ref_cap=ref_cap, decided=decided)
     assert env.status_flags() == 0
     _cache[name] = out
     return out
@@ -129,6 +100,7 @@ def test_both_planes_against_the_oracle(name):
     e_h, e_d, e_c = rel_err(c['harm'], c['ref_harm']), rel_err(c['diff'], c['ref_diff']), rel_err(c['cap'], c['ref_cap'])
     print(f'{name}: harm rel_err {e_h:.3e}, difference rel_err {e_d:.3e} (the step capacity itself: {e_c:.3e}) over '
           f'{c["harm"].size} links; harm up to {c["ref_harm"].max():.3f} Mbps, negative difference for {(c["ref_diff"] < 0).mean():.1%}')
+    assert c['decided'].all()        # on the float64 reference: no link within the bar of a sensitivity threshold, so every entry counts
     assert e_h <= BAR
     assert e_d <= BAR
     assert (c['harm'] >= 0.0).all()

@@ -2,7 +2,7 @@
 
 The yardstick: ref[b, i, j] = eirp_off_db[tx_j] - orc.pair_path_loss_db(...)[b, j, i] on the float32 positions read back from the
 env, and a NumPy stable descending sort of each row with the diagonal removed (neighbors_util); the bar is the project's 1e-5 on dB
-quantities (golden_util.rel_err).  Index order: [b, i, j], receiver link i first.  The cases are those of test_gpu_rb_sensing.py."""
+quantities (golden_util.rel_err).  Index order: [b, i, j], receiver link i first.  The cases are rb_sensing_util.CASES."""
 import json
 import runpy
 from pathlib import Path
@@ -13,8 +13,8 @@ import pytest
 import neighbors_util as nbu
 from golden_util import load_case, rel_err
 from oracle import d2d_oracle as orc
+from rb_sensing_util import CASES, _models, _state
 from sim_util import env_config_for, oracle_spec, random_layout
-from test_gpu_rb_sensing import CASES, _models, _state
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip('torch')

@@ -13,6 +13,7 @@ import pytest
 import rb_sensing_util as rbs
 from golden_util import GOLDEN_DIR, load_case, rel_err
 from oracle import d2d_oracle as orc
+from rb_sensing_util import CASES, _models, _state
 from sim_util import env_config_for, oracle_spec, random_layout
 
 pytestmark = pytest.mark.gpu
@@ -21,37 +22,6 @@ ROOT = Path(__file__).resolve().parent.parent
 BAR = 1e-5
 
 
-def _models():
-    from gym_d2d_amd.path_loss import AreaType, CostHataPathLoss, LogDistancePathLoss
-
-    class Ple35(LogDistancePathLoss):
-        def __init__(self, f):
-            super().__init__(f, ple=3.5)
-
-    class Urban(CostHataPathLoss):
-        def __init__(self, f):
-            super().__init__(f, AreaType.URBAN)
-
-    class Suburban(CostHataPathLoss):
-        def __init__(self, f):
-            super().__init__(f, AreaType.SUBURBAN)
-    return {'ld2': (LogDistancePathLoss, orc.PathLossSpec('log_distance', 2.1, ple=2.0)),
-            'ld35': (Ple35, orc.PathLossSpec('log_distance', 2.1, ple=3.5)),
-            'urban': (Urban, orc.PathLossSpec('cost_hata', 2.1, area='urban')),
-            'suburban': (Suburban, orc.PathLossSpec('cost_hata', 2.1, area='suburban'))}
-
-
-# name: (B0, cues, due pairs, RBs, model, cue_actions, downlink traffic model)
-CASES = {
-    'small_ld2_agent': (3, 8, 8, 5, 'ld2', 'agent', False),
-    'mid_ld35_agent': (2, 64, 96, 24, 'ld35', 'agent', False),
-    'crowded_urban_traffic_up': (2, 64, 64, 8, 'urban', 'traffic', False),          # 16 links per RB
-    'empty_suburban_traffic_down': (2, 6, 6, 40, 'suburban', 'traffic', True),      # 12 links on 40 RBs
-    'mid_ld2_traffic_down': (2, 24, 40, 16, 'ld2', 'traffic', True),
-    'small_urban_agent': (3, 8, 8, 5, 'urban', 'agent', False),
-    'small_suburban_traffic_up': (3, 8, 8, 5, 'suburban', 'traffic', False),
-    'case07_device_config': None,                                                    # golden case07's per-device overrides
-}
 _cache = {}
 
 

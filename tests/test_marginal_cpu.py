@@ -9,7 +9,9 @@ import numpy as np
 import pytest
 
 import marginal_util as mu
-from golden_util import rel_err
+import rb_sensing_util as rbs
+import read_side_util as rsu
+from golden_util import load_case, rel_err
 from oracle import d2d_oracle as orc
 from sim_util import default_links, random_layout
 
@@ -155,6 +157,53 @@ def test_oracle_side_of_the_largest_gpu_case_is_quick():
     print(f'oracle leave-one-out of 8 x 512 links: {dt:.1f} s; negative difference for {(diff < 0).mean():.1%} of the links')
     assert np.isfinite(diff).all() and (harm >= -1e-9).all()
     assert dt < 60
+
+
+def _rebuilt_state(name):
+    """The state test_gpu_marginal.py's _build(name) reaches, rebuilt by the env's rules without a GPU: the same generator, layout
+    and raw actions, decoded as the env decodes them (rb = a // P, level = a % P with 24 CUE and 21 DUE levels, d2d_env.py:93-96); under
+    cue_actions='traffic' the CUEs sit on the traffic model's round-robin RBs at their maximum power, and under
+    DownlinkTrafficModel their links run from the base station to the CUE.  case07 pins devices and keeps the layout its reset drew
+    on the device around them: here it stands on the fixture's recorded layout instead (one env)."""
+    rng = np.random.default_rng(sum(map(ord, name)))
+    cases = dict(rbs.CASES, one_rb=(2, 20, 30, 1, 'ld2', 'agent', False))
+    if cases[name] is None:
+        case = load_case(name)
+        b0, cue_actions, down = 1, 'agent', False
+        cues, dues, r = case.meta['num_cues'], case.meta['num_due_pairs'], case.meta['num_rbs']
+        from sim_util import oracle_spec
+        spec, cols, pos = oracle_spec(case), orc.device_columns(case.cfgs, case.is_bs), np.asarray(case.pos, dtype=np.float64)[None]
+    else:
+        b0, cues, dues, r, model, cue_actions, down = cases[name]
+        spec = rbs._models()[model][1]
+        cols = orc.device_columns(*orc.device_configs(cues, dues)[1:])
+        pos = random_layout(rng, b0, cues, dues).astype(np.float64)
+    tx, rx, _ = default_links(cues, dues)
+    if down:
+        tx[:cues], rx[:cues] = 0, np.arange(1, 1 + cues)
+    levels = np.array(([24] * cues if cue_actions == 'agent' else []) + [21] * dues)
+    raw = rng.integers(0, r * levels, (b0, len(levels)))
+    rb, pwr = raw // levels, raw % levels
+    if cue_actions == 'traffic':
+        rb = np.concatenate([np.broadcast_to(np.arange(cues) % r, (b0, cues)), rb], axis=1)
+        pwr = np.concatenate([np.full((b0, cues), 23), pwr], axis=1)
+    return dict(b=b0, n=cues + dues, r=r, pos=pos, tx=tx, rx=rx, rb=rb, pwr=pwr, ocols=cols, spec=spec)
+
+
+@pytest.mark.parametrize('name', list(rbs.CASES) + ['one_rb'])
+def test_no_link_of_the_small_gpu_cases_sits_on_a_sensitivity_threshold(name):
+    """test_gpu_marginal.py compares every entry.  That needs every link decided: no SINR - the link's own, or a victim's on its RB
+    with or without the link - within twice the bar of the receiver's sensitivity (read_side_util.leave_one_out_direct).  On the
+    float64 reference alone; the GPU test asserts the same on the state it really reached."""
+    c = _rebuilt_state(name)
+    pl = orc.pair_path_loss_db(c['spec'], c['pos'], c['tx'], c['rx'], c['ocols'])
+    diff, harm, cap, decided = rsu.leave_one_out_direct(c, pl=pl)
+    ref_diff, ref_harm, ref_cap, _ = mu.leave_one_out(c['pos'], c['tx'], c['rx'], c['rb'], c['pwr'], c['ocols'], c['spec'], c['r'])
+    sinr = orc.step(c['pos'], c['tx'], c['rx'], c['rb'], c['pwr'], c['ocols'], c['spec'])['sinr_db']
+    room = np.abs(sinr - c['ocols'].sens_dbm[c['rx']][None, :]).min()
+    print(f'{name}: {(~decided).mean():.2%} of {decided.size} links undecided; the nearest SINR is {room:.1f} dB from its threshold')
+    assert max(rel_err(harm, ref_harm), rel_err(diff, ref_diff), rel_err(cap, ref_cap)) <= 1e-9
+    assert decided.all()
 
 
 def test_fold_capacity_columns_follows_the_step_s_records():
