@@ -1,6 +1,7 @@
 """SpatialChannelPathLoss, the part that needs no GPU: libd2d_channel.so's header and exports, the fill kernels' resources, the
-statistics of the float64 restatement (tests/channel_util.py, the yardstick of test_gpu_channel.py), the model's range checks, every
-refusal by its text, and that an env without the model never touches the library."""
+statistics of the float64 restatement (tests/channel_util.py, the yardstick of test_gpu_channel.py), the conditions under which the
+restatement can judge the large direct launches (tests/channel_large_util.py, the cases of test_gpu_channel_large.py), the model's
+range checks, every refusal by its text, and that an env without the model never touches the library."""
 import re
 import shutil
 import subprocess
@@ -9,6 +10,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+import channel_large_util as clu
 import channel_util as cu
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -155,6 +157,113 @@ def test_fading_is_keyed_by_device_pair_step_and_episode():
     assert np.array_equal(a[:, 0], a[:, 2]) and not np.array_equal(a[:, 0], a[:, 1])       # rows 0 and 2: the same transmitter
     assert not np.array_equal(a, cu.fading_h2(3, 0, 0, 2, 2, [1, 2, 1], [0, 0, 5], 'rayleigh'))
     assert not np.array_equal(a, cu.fading_h2(3, 0, 1, 1, 2, [1, 2, 1], [0, 0, 5], 'rayleigh'))
+
+
+# ---------------------------------------------------------------------------------------------- the large cases' conditions
+MIN_ENTRY_DB = 5.0              # the relative measure |got - want| / |want| never divides by less than this
+
+
+@pytest.mark.parametrize('name', list(clu.CASES))
+def test_large_case_can_be_judged_by_the_restatement(name):
+    """The left-out share is within the cap, every kept entry is finite (but the one case h makes -inf) and at least MIN_ENTRY_DB
+    from 0 dB.  Printed per case: the share left out and the smallest kept |entry|."""
+    c = clu.build_case(name)
+    want, h2 = clu.restated(name)
+    n = c['n']
+    assert want.shape == (c['b'], n + 1, n)
+    keep = np.ones(want.shape, dtype=bool)
+    if h2 is not None:
+        keep[:, :n] = h2 >= cu.DEEP_FADE
+        keep[:, n] = h2[:, np.arange(n), np.arange(n)] >= cu.DEEP_FADE
+    inf = clu.infinite_entries(c)
+    assert np.array_equal(np.isneginf(want), inf) and int(inf.sum()) == (1 if name == 'h' else 0)
+    kept = want[keep & ~inf]
+    print(f'{name}: B {c["b"]} N {n} D {c["d"]}: {1.0 - keep.mean():.2g} left out, min |entry| of the kept {np.abs(kept).min():.3g} dB')
+    assert 1.0 - keep.mean() <= cu.DEEP_FADE_CAP
+    assert np.isfinite(kept).all()
+    assert np.abs(kept).min() >= MIN_ENTRY_DB
+    assert np.array_equal(want[:, n], want[:, np.arange(n), np.arange(n)])
+    assert c['n'] <= c['d'] and c['tx'].max() < c['d'] and c['rx'].max() < c['d'] and min(c['tx'].min(), c['rx'].min()) >= 0
+    assert c['pos'].dtype == np.float32 and (np.hypot(c['pos'][..., 0], c['pos'][..., 1]) <= 500.0 * (1 + 1e-6)).all()
+
+
+def test_large_cases_cover_what_they_claim():
+    case = {k: clu.build_case(k) for k in clu.CASES}
+    # the env mapping: more than one group of eight, the last one partial
+    for k in ('a', 'b', 'c', 'f_rayleigh', 'f_rician', 'g', 'h'):
+        assert case[k]['b'] > 8 and case[k]['b'] % 8 != 0, k
+    assert (case['a']['b'], case['b']['b'], case['c']['b']) == (9, 17, 11)
+    assert case['b']['first_env'] + case['b']['b'] == 2 ** 32                # the last env's counter word is 2^32 - 1
+    # tile edges: 64 columns, 32 rows
+    assert case['a']['n'] == 64 and case['a']['n'] % 64 == 0 and case['a']['n'] % 32 == 0
+    assert case['b']['n'] == 65 and case['b']['n'] % 64 == 1 and case['b']['n'] % 32 == 1
+    assert case['c']['n'] == 259 and case['c']['n'] % 64 == 3 and case['c']['n'] % 32 == 3
+    assert case['d']['n'] == 1030 and case['d']['n'] % 64 == 6 and case['d']['n'] % 32 == 6
+    assert case['e']['n'] == 2048 and case['e']['n'] % 64 == 0
+    assert (case['e']['n'] + 1) * case['e']['n'] > 4.19e6
+    assert (case['g']['n'], case['g']['m'], case['g']['fading']) == (131, 0, None)
+    # device indexing
+    for k in ('f_rayleigh', 'f_rician'):
+        c = case[k]
+        tx, rx = c['tx'], c['rx']
+        assert (c['n'], c['d']) == (70, 65535) and clu.TOP_DEVICE == 65534 and clu.TOP_DEVICE in tx
+        assert (tx >= 32768).sum() >= 5 and (rx >= 32768).sum() >= 5
+        assert np.bitwise_or.reduce(tx) == 0xFFFF == np.bitwise_or.reduce(rx)          # every bit of both halves of u | v << 16
+        assert len(set(tx[clu.SHARED_TX])) == 1 and len(tx[clu.SHARED_TX]) >= 2
+        assert len(set(rx[clu.SHARED_RX])) == 1 and len(rx[clu.SHARED_RX]) >= 2
+        assert not set(tx) & set(rx)                                                   # no pair at distance 0
+        assert len(set(tx)) == c['n'] - len(tx[clu.SHARED_TX]) + 1 and len(set(rx)) == c['n'] - len(rx[clu.SHARED_RX]) + 1
+        for col in ('a_tx', 'a_rx', 'expo'):                                           # by device: no two links read one value
+            assert len(set(c[col][np.unique(tx)])) == len(set(tx)) and len(set(c[col][np.unique(rx)])) == len(set(rx))
+            assert not np.array_equal(c[col][tx], c[col][:c['n']]) and not np.array_equal(c[col][tx], c[col][rx])
+    for k in ('g', 'h'):
+        c = case[k]
+        assert c['d'] == 193 and len(set(c['a_tx'])) == len(set(c['a_rx'])) == len(set(c['expo'])) == 193
+        assert (20 <= c['a_tx']).all() and (c['a_tx'] <= 60).all() and (np.abs(c['a_rx']) <= 10).all()
+        assert (2 <= c['expo']).all() and (c['expo'] <= 4).all()
+    # case h is case g but for one device of one env
+    e, j, i = clu.COINCIDENT
+    g, h = case['g'], case['h']
+    moved = np.zeros(g['pos'].shape[:2], dtype=bool)
+    moved[e, h['tx'][j]] = True
+    assert np.array_equal(g['pos'][~moved], h['pos'][~moved]) and np.array_equal(h['pos'][e, h['tx'][j]], h['pos'][e, h['rx'][i]])
+    assert e >= 8 and j != i and h['tx'][j] != h['rx'][i] and all(np.array_equal(g[k], h[k]) for k in ('tx', 'rx', 'a_tx', 'a_rx', 'expo'))
+    # the per-env clock: pending and running envs in both groups of eight, elapsed >= start, episodes in [1, 1000]
+    k = case['c']['clock']
+    pending = k['reset'] != 0
+    for group in (slice(0, 8), slice(8, 11)):
+        assert pending[group].any() and (~pending[group]).any()
+    assert (k['elapsed'] >= k['start']).all() and (k['start'][pending] != 0).any() and (1 <= k['episode']).all() and (k['episode'] <= 1000).all()
+    episode, t = clu.env_clock(case['c'])
+    assert (t[pending] == 0).all() and (t[~pending] >= 1).all() and len(set(episode)) > 8
+    assert all(case[n]['clock'] is None for n in case if n != 'c')
+    # the shards start inside a group of eight and end in the next
+    for name, (lo, hi) in clu.SHARDS.items():
+        assert 0 < lo < 8 < hi <= case[name]['b'] and lo % 8 != 0
+
+
+def test_the_column_restatement_agrees_with_the_oracle_s_median_restatement():
+    """table_db_columns on the log-distance columns (a_tx the path-loss constant, a_rx 0, exponent the ple) against table_db, whose
+    median is the oracle's own formula: 1e-12 of the entry, scalar and per-env clocks, every fading."""
+    from oracle import d2d_oracle as orc
+    from sim_util import default_links, random_layout
+    b, cues, pairs = 3, 3, 2
+    d = 1 + cues + 2 * pairs
+    pos = random_layout(np.random.default_rng(5), b, cues, pairs)
+    tx, rx, _ = default_links(cues, pairs)
+    _, cfgs, is_bs = orc.device_configs(cues, pairs)
+    cols = orc.device_columns(cfgs, is_bs)
+    shadow_seed, fading_seed = cu.stream_seeds(clu.SEED)
+    for ple, fading, m, episode, t in ((2.0, 'rayleigh', 16, 3, 5), (3.5, 'rician', 8, np.array([1, 7, 2]), np.array([0, 4, 9])),
+                                       (3.5, None, 32, 0, 0)):
+        kw = dict(first_env=clu.FIRST_ENV, episode=episode, t=t, num_sinusoids=m, fading=fading)
+        want, want_h2 = cu.table_db(pos, tx, rx, cols, orc.PathLossSpec('log_distance', 2.1, ple=ple), env_seed=clu.SEED, **kw)
+        got, got_h2 = cu.table_db_columns(pos, tx, rx, np.full(d, orc.pl_constant_db(2.1, ple)), np.zeros(d), np.full(d, ple),
+                                          shadow_seed=shadow_seed, fading_seed=fading_seed, chunk_elems=1, **kw)
+        err = np.max(np.abs(got - want) / np.abs(want))
+        print(f'ple {ple} {fading} M_s {m}: {err:.3g} of the entry')
+        assert err <= 1e-12
+        assert (got_h2 is None and want_h2 is None) or np.array_equal(got_h2, want_h2)
 
 
 # ---------------------------------------------------------------------------------------------- the host side

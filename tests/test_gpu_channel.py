@@ -8,9 +8,7 @@ import channel_util as cu
 from oracle import d2d_oracle as orc
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-5                      # the project's parity bar
-DEEP_FADE = 1e-4                # entries whose restated |h|^2 is below this are left out ...
-DEEP_FADE_CAP = 1e-3            # ... and may be this fraction of the entries at most (Exp(1) puts 1e-4 there)
+TOL, DEEP_FADE, DEEP_FADE_CAP = cu.TOL, cu.DEEP_FADE, cu.DEEP_FADE_CAP      # the project's parity bar and the deep-fade exclusion
 FIRST_ENV, SEED, CFG_SEED = 4096, 29, 4321
 SHAPES = {'small': (3, 3, 2, 4), 'large': (6, 70, 61, 8)}          # B, CUEs, DUE pairs, RBs: 131 links, 193 devices
 MEDIANS = ('ple2', 'ple3.5', 'hata_urban')
@@ -61,15 +59,7 @@ def _restated(env, shape, median, episode, t, **kw):
                        first_env=env.first_env, episode=episode, t=t, **kw)
 
 
-def _entry_error(got, want, h2):
-    """Worst |got - want| / |want| over the entries that are not deep fades; the share of entries left out."""
-    keep = np.ones(want.shape, dtype=bool)
-    if h2 is not None:
-        n = h2.shape[1]
-        keep[:, :n] = h2 >= DEEP_FADE
-        keep[:, n] = h2[:, np.arange(n), np.arange(n)] >= DEEP_FADE
-    assert np.isfinite(want[keep]).all()
-    return float(np.max(np.abs(got - want)[keep] / np.abs(want)[keep])), 1.0 - keep.mean()
+_entry_error = cu.entry_error
 
 
 # ------------------------------------------------------------------------------------------ 1: the table, entry by entry
@@ -110,10 +100,17 @@ def test_no_shadowing_launches_no_shadowing_work_and_matches():
 
 
 # ------------------------------------------------------------------------------------------ 2: the step against the oracle
+# (B, CUEs, DUE pairs, RBs) of the step on a LARGE live per-env table, mobile=False: 259 links (the step's 320-thread shape, 9 mask
+# words) and 1030 links (two links per thread, no masks, lists or sweep)
+STEP_259, STEP_1030 = (9, 129, 130, 40), (2, 513, 517, 300)
+STEP_CASES = [(shape, fading, median, mobile) for mobile in (False, True)
+              for shape, fading, median in (('small', 'rayleigh', 'ple2'), ('large', 'rician', 'hata_urban'), ('large', 'rayleigh', 'ple3.5'))]
+
+
 @pytest.mark.parametrize('dtype', ['float64', 'float32'])
-@pytest.mark.parametrize('mobile', [False, True])
-@pytest.mark.parametrize('shape,fading,median', [('small', 'rayleigh', 'ple2'), ('large', 'rician', 'hata_urban'),
-                                                 ('large', 'rayleigh', 'ple3.5')])
+@pytest.mark.parametrize('shape,fading,median,mobile', STEP_CASES + [
+    pytest.param(STEP_259, 'rician', 'ple3.5', False, id='259links-rician-ple3.5-False'),
+    pytest.param(STEP_1030, 'rayleigh', 'hata_urban', False, id='1030links-rayleigh-hata_urban-False')])
 def test_step_matches_the_oracle_on_the_restated_table(shape, fading, median, mobile, dtype):
     """float64 entries (the model's default): the project's bar, 1e-5, on all three outputs.
 
