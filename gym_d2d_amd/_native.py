@@ -1,7 +1,7 @@
 """ctypes binding of libd2d_hip.so (include/d2d_hip.h), libd2d_plugin.so (include/d2d_plugin.h), libd2d_episode.so
 (include/d2d_episode.h), libd2d_sense.so (include/d2d_sense.h), libd2d_graph.so (include/d2d_graph.h), libd2d_marginal.so (include/d2d_marginal.h), libd2d_mobility.so
 (include/d2d_mobility.h), libd2d_channel.so (include/d2d_channel.h), libd2d_queue.so (include/d2d_queue.h) libd2d_bestrb.so
-(include/d2d_bestrb.h), libd2d_powerctl.so (include/d2d_powerctl.h) and libd2d_brdyn.so (include/d2d_brdyn.h).  There is no CPU fallback: if a library or a gfx950 GPU is missing, the calls below raise."""
+(include/d2d_bestrb.h), libd2d_powerctl.so (include/d2d_powerctl.h), libd2d_brdyn.so (include/d2d_brdyn.h) and libd2d_evaluate.so (include/d2d_evaluate.h).  There is no CPU fallback: if a library or a gfx950 GPU is missing, the calls below raise."""
 from __future__ import annotations
 
 import ctypes as C
@@ -22,6 +22,7 @@ QUEUE_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_queue.so'
 BESTRB_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_bestrb.so'
 POWERCTL_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_powerctl.so'
 BRDYN_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_brdyn.so'
+EVALUATE_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_evaluate.so'
 ABI_VERSION = 7
 MAX_LINKS = 2048
 
@@ -76,6 +77,12 @@ BRDYN_LAW_INV_SQUARE, BRDYN_LAW_POWER, BRDYN_LAW_POW_K = 0, 1, 2
 BRDYN_MAX_RBS = 8192
 BRDYN_MAX_ROUNDS = 1024
 BRDYN_MAX_LDS_BYTES = 163840
+# d2d_evaluate's law / limits (include/d2d_evaluate.h): the sensing kernel's, the candidates one workgroup serves and one launch holds
+EVALUATE_LAW_INV_SQUARE, EVALUATE_LAW_POWER, EVALUATE_LAW_POW_K = 0, 1, 2
+EVALUATE_MAX_RBS = 8192
+EVALUATE_CHUNK = 8
+EVALUATE_MAX_CANDIDATES = 65535 * EVALUATE_CHUNK
+EVALUATE_MAX_LDS_BYTES = 163840
 
 BUFFER_DTYPES = {BUF_ACTIONS: np.int32, BUF_RB: np.int32, BUF_PWR: np.int32, BUF_ENV_FLAGS: np.int32, BUF_RESET_PENDING: np.int32,
                  BUF_EPISODE: np.uint32}
@@ -229,6 +236,12 @@ BRDYN_SIGNATURES = {
     'd2d_brdyn_last_error': (C.c_char_p, []),
 }
 
+# every symbol include/d2d_evaluate.h declares
+EVALUATE_SIGNATURES = {
+    'd2d_evaluate': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, C.c_int64, _I, _I, _I, _I, _P, _P, _P, _P]),
+    'd2d_evaluate_last_error': (C.c_char_p, []),
+}
+
 _lib: Optional[C.CDLL] = None
 _plugin: Optional[C.CDLL] = None
 _episode: Optional[C.CDLL] = None
@@ -244,6 +257,8 @@ _powerctl: Optional[C.CDLL] = None
 powerctl_launches = 0               # d2d_power_control calls made through power_control() in this process
 _brdyn: Optional[C.CDLL] = None
 brdyn_launches = 0                  # d2d_best_response_dynamics launches made through best_response_dynamics() in this process
+_evaluate: Optional[C.CDLL] = None
+evaluate_launches = 0               # d2d_evaluate launches made through evaluate() in this process
 _mobility: Optional[C.CDLL] = None
 mobility_launches = 0               # d2d_mobility_move calls made through mobility_move() in this process
 _channel: Optional[C.CDLL] = None
@@ -549,6 +564,39 @@ def best_response_dynamics(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr:
         raise NativeError(rc, lib.d2d_brdyn_last_error().decode(errors='replace'))
     if n_envs:
         brdyn_launches += 1
+
+
+def load_evaluate_library() -> C.CDLL:
+    """dlopen libd2d_evaluate.so and type its entry points.  Raises if it has not been built."""
+    global _evaluate
+    if _evaluate is not None:
+        return _evaluate
+    if not EVALUATE_PATH.exists():
+        raise ImportError(f'{EVALUATE_PATH} is missing - build it with `python -m gym_d2d_amd.build`')
+    lib = C.CDLL(str(EVALUATE_PATH))
+    for name, (res, args) in EVALUATE_SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    _evaluate = lib
+    return lib
+
+
+def evaluate(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, link_tx_ptr: int, link_rx_ptr: int, cols_ptr: int,
+             cap_cols_ptr: int, law: int, pow_k: int, n_envs: int, n_cand: int, n_dev: int, n_links: int, n_rbs: int, sinr_ptr: int,
+             capacity_ptr: int, total_ptr: int, stream_ptr: int = 0) -> None:
+    """d2d_evaluate: the planes n_cand candidate assignments per env would give - sinr_db and capacity_mbps float32 [n_envs, n_cand,
+    n_links] (either pointer 0: not written) and total_mbps float32 [n_envs, n_cand] (device pointers; rb_ptr / pwr_ptr int32
+    [n_envs, n_cand, n_links])."""
+    global evaluate_launches
+    lib = load_evaluate_library()
+    rc = lib.d2d_evaluate(_P(pos_x_ptr or None), _P(pos_y_ptr or None), _P(rb_ptr or None), _P(pwr_ptr or None), _P(link_tx_ptr or None),
+                          _P(link_rx_ptr or None), _P(cols_ptr or None), _P(cap_cols_ptr or None), law, pow_k, n_envs, n_cand, n_dev,
+                          n_links, n_rbs, _P(sinr_ptr or None), _P(capacity_ptr or None), _P(total_ptr or None), _P(stream_ptr or None))
+    if rc != 0:
+        raise NativeError(rc, lib.d2d_evaluate_last_error().decode(errors='replace'))
+    if n_envs:
+        evaluate_launches += 1
 
 
 def load_mobility_library() -> C.CDLL:

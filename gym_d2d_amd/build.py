@@ -7,7 +7,8 @@ include/d2d_channel.h), libd2d_queue.so (the stateless packet-queue step of
 include/d2d_queue.h), libd2d_bestrb.so (the stateless best-response RB selection of
 include/d2d_bestrb.h), libd2d_powerctl.so (the stateless target-SINR power control of
 include/d2d_powerctl.h), libd2d_brdyn.so (the stateless sequential best-response dynamics of
-include/d2d_brdyn.h) and libd2d_probe.so (measurement equipment: the write-ceiling probe
+include/d2d_brdyn.h), libd2d_evaluate.so (the stateless what-if evaluation of candidate joint actions of
+include/d2d_evaluate.h) and libd2d_probe.so (measurement equipment: the write-ceiling probe
 of include/d2d_hip_diag.h) for gfx950 with hipcc - in-tree, so the .so files travel with the repo snapshot.
 
     python -m gym_d2d_amd.build [--force] [--verbose]
@@ -39,6 +40,7 @@ QUEUE_PATH = LIB_DIR / 'libd2d_queue.so'
 BESTRB_PATH = LIB_DIR / 'libd2d_bestrb.so'
 POWERCTL_PATH = LIB_DIR / 'libd2d_powerctl.so'
 BRDYN_PATH = LIB_DIR / 'libd2d_brdyn.so'
+EVALUATE_PATH = LIB_DIR / 'libd2d_evaluate.so'
 INCLUDE = PKG.parent / 'include'
 ARCH = 'gfx950'
 
@@ -55,8 +57,9 @@ QUEUE_SOURCES = ['d2d_queue.hip']
 BESTRB_SOURCES = ['d2d_bestrb.hip']
 POWERCTL_SOURCES = ['d2d_powerctl.hip']
 BRDYN_SOURCES = ['d2d_brdyn.hip']
+EVALUATE_SOURCES = ['d2d_evaluate.hip']
 HEADERS = [CSRC / 'd2d_internal.h', CSRC / 'd2d_plan.h', CSRC / 'd2d_step_device.h', CSRC / 'd2d_store.h', INCLUDE / 'd2d_hip.h', INCLUDE / 'd2d_hip_diag.h',
-           INCLUDE / 'd2d_plugin.h', INCLUDE / 'd2d_episode.h', INCLUDE / 'd2d_sense.h', INCLUDE / 'd2d_graph.h', INCLUDE / 'd2d_marginal.h', INCLUDE / 'd2d_mobility.h', INCLUDE / 'd2d_channel.h', INCLUDE / 'd2d_queue.h', INCLUDE / 'd2d_bestrb.h', INCLUDE / 'd2d_powerctl.h', INCLUDE / 'd2d_brdyn.h']
+           INCLUDE / 'd2d_plugin.h', INCLUDE / 'd2d_episode.h', INCLUDE / 'd2d_sense.h', INCLUDE / 'd2d_graph.h', INCLUDE / 'd2d_marginal.h', INCLUDE / 'd2d_mobility.h', INCLUDE / 'd2d_channel.h', INCLUDE / 'd2d_queue.h', INCLUDE / 'd2d_bestrb.h', INCLUDE / 'd2d_powerctl.h', INCLUDE / 'd2d_brdyn.h', INCLUDE / 'd2d_evaluate.h']
 FLAGS = ['-O3', '-std=c++17', '-fPIC', f'--offload-arch={ARCH}', '-fno-gpu-rdc', '-Wall', '-Wno-unused-function', '-Wno-unused-value',
          # the kernels already issue their uniform-address LDS atomics from one lane (or on rare paths): LLVM's atomic optimizer
          # only wraps them in mbcnt / readlane / popcount-multiply sequences
@@ -76,7 +79,7 @@ def _hipcc() -> str:
 def source_digest() -> str:
     """sha256 over the kernel / C-ABI sources, headers and compile flags: identifies what a profile was taken on."""
     h = hashlib.sha256()
-    for p in [CSRC / s for s in SOURCES + PROBE_SOURCES + PLUGIN_SOURCES + EPISODE_SOURCES + SENSE_SOURCES + GRAPH_SOURCES + MARGINAL_SOURCES + MOBILITY_SOURCES + CHANNEL_SOURCES + QUEUE_SOURCES + BESTRB_SOURCES + POWERCTL_SOURCES + BRDYN_SOURCES if (CSRC / s).exists()] + [h for h in HEADERS if h.exists()]:
+    for p in [CSRC / s for s in SOURCES + PROBE_SOURCES + PLUGIN_SOURCES + EPISODE_SOURCES + SENSE_SOURCES + GRAPH_SOURCES + MARGINAL_SOURCES + MOBILITY_SOURCES + CHANNEL_SOURCES + QUEUE_SOURCES + BESTRB_SOURCES + POWERCTL_SOURCES + BRDYN_SOURCES + EVALUATE_SOURCES if (CSRC / s).exists()] + [h for h in HEADERS if h.exists()]:
         h.update(p.name.encode()); h.update(p.read_bytes())
     h.update(' '.join(FLAGS).encode())
     return h.hexdigest()
@@ -86,13 +89,13 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     LIB_DIR.mkdir(exist_ok=True)
     stamp = LIB_DIR / 'libd2d_hip.sha256'
     digest = source_digest()
-    if not force and LIB_PATH.exists() and PLUGIN_PATH.exists() and EPISODE_PATH.exists() and SENSE_PATH.exists() and GRAPH_PATH.exists() and MARGINAL_PATH.exists() and MOBILITY_PATH.exists() and CHANNEL_PATH.exists() and QUEUE_PATH.exists() and BESTRB_PATH.exists() and POWERCTL_PATH.exists() and BRDYN_PATH.exists() and stamp.exists() and stamp.read_text().strip() == digest:
+    if not force and LIB_PATH.exists() and PLUGIN_PATH.exists() and EPISODE_PATH.exists() and SENSE_PATH.exists() and GRAPH_PATH.exists() and MARGINAL_PATH.exists() and MOBILITY_PATH.exists() and CHANNEL_PATH.exists() and QUEUE_PATH.exists() and BESTRB_PATH.exists() and POWERCTL_PATH.exists() and BRDYN_PATH.exists() and EVALUATE_PATH.exists() and stamp.exists() and stamp.read_text().strip() == digest:
         return LIB_PATH
     hipcc = _hipcc()
     obj_dir = LIB_DIR / 'obj'
     obj_dir.mkdir(exist_ok=True)
     procs = []
-    for s in SOURCES + PROBE_SOURCES + PLUGIN_SOURCES + EPISODE_SOURCES + SENSE_SOURCES + GRAPH_SOURCES + MARGINAL_SOURCES + MOBILITY_SOURCES + CHANNEL_SOURCES + QUEUE_SOURCES + BESTRB_SOURCES + POWERCTL_SOURCES + BRDYN_SOURCES:
+    for s in SOURCES + PROBE_SOURCES + PLUGIN_SOURCES + EPISODE_SOURCES + SENSE_SOURCES + GRAPH_SOURCES + MARGINAL_SOURCES + MOBILITY_SOURCES + CHANNEL_SOURCES + QUEUE_SOURCES + BESTRB_SOURCES + POWERCTL_SOURCES + BRDYN_SOURCES + EVALUATE_SOURCES:
         src = CSRC / s
         obj = obj_dir / (src.stem + '.o')
         cmd = [hipcc, *FLAGS, '-I', str(INCLUDE), '-c', str(src), '-o', str(obj)]
@@ -109,7 +112,8 @@ def build(force: bool = False, verbose: bool = False) -> Path:
                          (EPISODE_PATH, EPISODE_SOURCES), (SENSE_PATH, SENSE_SOURCES), (GRAPH_PATH, GRAPH_SOURCES),
                          (MARGINAL_PATH, MARGINAL_SOURCES), (MOBILITY_PATH, MOBILITY_SOURCES), (CHANNEL_PATH, CHANNEL_SOURCES),
                          (QUEUE_PATH, QUEUE_SOURCES), (BESTRB_PATH, BESTRB_SOURCES),
-                         (POWERCTL_PATH, POWERCTL_SOURCES), (BRDYN_PATH, BRDYN_SOURCES)):
+                         (POWERCTL_PATH, POWERCTL_SOURCES), (BRDYN_PATH, BRDYN_SOURCES),
+                         (EVALUATE_PATH, EVALUATE_SOURCES)):
         objs = [str(obj_dir / (Path(s).stem + '.o')) for s in sources]
         cmd = [hipcc, '-shared', '-fPIC', f'--offload-arch={ARCH}', '-o', str(lib), *objs]
         if verbose:

@@ -23,6 +23,7 @@ from typing import Optional
 import numpy as np
 
 from .. import _native, best_response, best_response_dynamics, graph, marginal, power_control, sensing
+from .. import evaluate as evaluate_mod
 from .. import mobility as mobility_mod
 from .. import queues as queues_mod
 from ..path_loss_table import CHANNEL, PER_STEP, positions_move_unserved
@@ -275,6 +276,8 @@ class VecD2DEnv:
         self._power_levels = None                  # power_control_actions(): (lowest power, power levels) of every agent link's class
         # sequential best-response dynamics (best_response_dynamics()): likewise nothing unless it is called
         self._brdyn = None
+        # what-if evaluation of candidate joint actions (evaluate()): likewise nothing unless it is called
+        self._evaluate = None
 
     def _setup_autoreset(self) -> None:
         """Refuse what a device-side per-env reset cannot serve, then allocate the per-env bookkeeping: pending / episode are bound
@@ -940,6 +943,58 @@ class VecD2DEnv:
             self._action_levels = torch.as_tensor(np.asarray(levels, dtype=np.int32), device=self.device)
         return best_response_dynamics.encode_actions(rb, self._t['pwr'], self._action_levels, self.num_links - self.num_agents)
 
+    # ------------------------------------------------------------------ what-if evaluation of candidate joint actions
+    def _evaluate_kernel(self):
+        if self._evaluate is None:
+            why = evaluate_mod.refusal(self.simulator, self.export_actions, self.use_torch)
+            if why:
+                raise ValueError(why)
+            self._evaluate = evaluate_mod.Evaluate(self.simulator, self.num_links, torch, self.device)
+        return self._evaluate
+
+    def evaluate(self, rb, power_dbm, planes=('sinr_db', 'capacity_mbps'), out=None):
+        """What K complete joint assignments per env would give, at the current positions: a dict with 'total_mbps' float32 [B, K]
+        and the requested planes float32 [B, K, N].
+
+        rb, power_dbm: contiguous int32 [B, K, N] tensors on the env's device, candidate k of env b as the decoded planes step()
+        exports (info['rb'], info['pwr']) would hold it; K >= 1 is free and may change from call to call.  sinr_db[b, k] and
+        capacity_mbps[b, k] are, bit for bit, the planes a step() with that assignment exports at these positions, and
+        total_mbps[b, k] is the sum of capacity_mbps[b, k] over the links, accumulated in double in a fixed order (two calls give
+        the same bits).  One kernel launch (csrc/d2d_evaluate.hip): a workgroup stages an env once and evaluates a chunk of its
+        candidates out of LDS.  planes: which of 'sinr_db', 'capacity_mbps' to write; () gives the totals only and writes no
+        [B, K, N] block.  An rb outside [0, num_rbs) is outside the contract (the link is on no RB, as in marginal_capacity()).
+
+        The env is left untouched: no counter, plane, queue, position or reward changes.  Valid after reset() and after every
+        step(), autoreset steps included.  With mobility= the evaluation is at the CURRENT positions, whereas the next step() moves
+        the devices first: equality with the next step's planes holds without mobility only.
+
+        Torch path only: enqueued on torch's current stream, nothing is synchronised; the tensors the env owns, reallocated when K
+        changes and rewritten by every call (clone them to keep them), or `out`, a dict of contiguous float32 tensors with exactly
+        the returned keys and shapes.  Serves what best_rb() serves; ValueError for export_actions=False, ShadowingPathLoss, every
+        table route, pinned device_config coordinates float32 cannot hold."""
+        k = self._evaluate_kernel()
+        self._follow_torch_stream()
+        return k.planes(self._t, rb, power_dbm, planes, out, self._stream_ptr)
+
+    def evaluate_actions(self, actions, planes=('sinr_db', 'capacity_mbps')):
+        """evaluate() of K candidate action sets: actions is an integer tensor [B, K, num_agents], every [:, k] in the layout step()
+        takes (rb * power levels + level).  Links on fixed actions (cue_actions='traffic') have no column and keep their current
+        rb / power in every candidate.  Decoded by evaluate.decode_actions; the result and its validity are evaluate()'s."""
+        k = self._evaluate_kernel()
+        if not torch.is_tensor(actions) or actions.ndim != 3 or tuple(actions.shape[::2]) != (self.num_envs, self.num_agents) \
+                or actions.device != self.device:
+            raise ValueError(f'actions must be an integer tensor [{self.num_envs}, K, {self.num_agents}] (env, candidate, agent) on '
+                             f'{self.device}')
+        if self._action_levels is None:
+            p = self.num_pwr_actions
+            levels = ([p[self._cue_kind]] * self.num_cues if self.cue_actions == 'agent' else []) + [p['due']] * self.num_due_pairs
+            self._action_levels = torch.as_tensor(np.asarray(levels, dtype=np.int32), device=self.device)
+        first = self.num_links - self.num_agents
+        self._follow_torch_stream()
+        fixed = (self._t['rb'][:, :first], self._t['pwr'][:, :first]) if first else (None, None)
+        rb, pwr = evaluate_mod.decode_actions(actions, self._action_levels, *fixed)
+        return k.planes(self._t, rb, pwr, planes, None, self._stream_ptr)
+
     def _observe(self, view):
         extra = {}
         if self._senses:
@@ -1009,4 +1064,7 @@ class VecD2DEnv:
         if self._brdyn is not None:
             self._brdyn.close()
             self._brdyn = None
+        if self._evaluate is not None:
+            self._evaluate.close()
+            self._evaluate = None
         self.simulator.handle.close()
