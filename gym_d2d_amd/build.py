@@ -58,7 +58,7 @@ BESTRB_SOURCES = ['d2d_bestrb.hip']
 POWERCTL_SOURCES = ['d2d_powerctl.hip']
 BRDYN_SOURCES = ['d2d_brdyn.hip']
 EVALUATE_SOURCES = ['d2d_evaluate.hip']
-HEADERS = [CSRC / 'd2d_internal.h', CSRC / 'd2d_plan.h', CSRC / 'd2d_step_device.h', CSRC / 'd2d_store.h', INCLUDE / 'd2d_hip.h', INCLUDE / 'd2d_hip_diag.h',
+HEADERS = [CSRC / 'd2d_internal.h', CSRC / 'd2d_plan.h', CSRC / 'd2d_step_device.h', CSRC / 'd2d_store.h', CSRC / 'd2d_same_rb.h', CSRC / 'd2d_addon.h', INCLUDE / 'd2d_hip.h', INCLUDE / 'd2d_hip_diag.h',
            INCLUDE / 'd2d_plugin.h', INCLUDE / 'd2d_episode.h', INCLUDE / 'd2d_sense.h', INCLUDE / 'd2d_graph.h', INCLUDE / 'd2d_marginal.h', INCLUDE / 'd2d_mobility.h', INCLUDE / 'd2d_channel.h', INCLUDE / 'd2d_queue.h', INCLUDE / 'd2d_bestrb.h', INCLUDE / 'd2d_powerctl.h', INCLUDE / 'd2d_brdyn.h', INCLUDE / 'd2d_evaluate.h']
 FLAGS = ['-O3', '-std=c++17', '-fPIC', f'--offload-arch={ARCH}', '-fno-gpu-rdc', '-Wall', '-Wno-unused-function', '-Wno-unused-value',
          # the kernels already issue their uniform-address LDS atomics from one lane (or on rare paths): LLVM's atomic optimizer

@@ -1,7 +1,7 @@
 // libd2d_bestrb.so (include/d2d_bestrb.h): every link's best resource block, the SINR it would see there and what the move would
 // gain, one launch, without the [B][N][R] block of d2d_sense.hip.  gfx950.
 //
-// Shape: the sensing kernel's (d2d_sense.hip), restated here so that its ISA stays what it is.  grid = (env, block of 256 receivers),
+// Shape: the sensing kernel's (d2d_sense.hip); the sort both share is d2d_same_rb.h.  grid = (env, block of 256 receivers),
 // 256 threads.  The workgroup sorts the env's N links by (rb, link index) into LDS - the rank sort on the packed keys
 // rb * 2048 + j, four keys per ds_read_b128 at a wave-uniform address: stable, free of atomics, the same order on every call - as
 // transmitter tuples (tx x, tx y, linear EIRP incl. the tx side of the path-loss constant, link index), the per-tx law constants
@@ -17,25 +17,19 @@
 
 #include <string>
 
+#include "d2d_addon.h"
 #include "d2d_bestrb.h"
+#include "d2d_same_rb.h"
 #include "d2d_step_device.h"
 
 namespace {
 
 using namespace d2d;
 
-thread_local std::string g_bestrb_error;
-
-int bestrb_fail(const std::string& msg) {
-    try { g_bestrb_error = msg; } catch (...) { }
-    return 1;
-}
-
 constexpr int BEST_THREADS = 256;
 constexpr int GROUP_RBS = 32;                                    // one word of the allowed mask
-constexpr unsigned KEY_SHIFT = 11;                               // key = rb << 11 | j, j < 2048
-static_assert((1 << KEY_SHIFT) == D2D_BESTRB_MAX_LINKS, "the key packs the link index into KEY_SHIFT bits");
-static_assert((unsigned long long)(D2D_BESTRB_MAX_RBS + 1) << KEY_SHIFT < 0xFFFFFFFFull, "keys are 32 bits, all ones is the padding");
+static_assert(D2D_BESTRB_MAX_LINKS == SAME_RB_MAX_LINKS && D2D_BESTRB_MAX_RBS == SAME_RB_MAX_RBS, "the limits of the shared sort (d2d_same_rb.h)");
+static_assert(D2D_BESTRB_LAW_INV_SQUARE == LAW_INV_SQUARE && D2D_BESTRB_LAW_POWER == LAW_POWER && D2D_BESTRB_LAW_POW_K == LAW_POW_K, "the laws check_law() knows (d2d_addon.h)");
 
 struct BestArgs {
     const float* pos_x;
@@ -57,7 +51,6 @@ struct BestArgs {
 };
 
 // dynamic LDS: tuples float4[N] | hh float2[N] (power laws) | start int[R + 1] | keys u32[N rounded up to 4] | sorted rb int[N]
-__host__ __device__ inline unsigned round16(unsigned x) { return (x + 15u) & ~15u; }
 
 template <int MODE>
 __global__ __launch_bounds__(BEST_THREADS) void bestrb_kernel(const BestArgs a) {
@@ -79,14 +72,7 @@ __global__ __launch_bounds__(BEST_THREADS) void bestrb_kernel(const BestArgs a) 
     const float* py = a.pos_y + b * (size_t)D;
 
     // ---- keys: (rb, link index); a link whose rb is outside [0, R) takes the pseudo RB R behind every real one
-    for (int j = tid; j < n4; j += BEST_THREADS) {
-        unsigned k = 0xFFFFFFFFu;
-        if (j < N) {
-            const int r = rb_row[j];
-            k = ((unsigned)((unsigned)r < (unsigned)R ? r : R) << KEY_SHIFT) | (unsigned)j;
-        }
-        key[j] = k;
-    }
+    same_rb_keys<BEST_THREADS>(key, rb_row, N, n4, R);
     __syncthreads();
     // ---- rank sort: link j goes to slot #{keys below its own}; the keys are distinct, so the slots are a permutation
     for (int j = tid; j < N; j += BEST_THREADS) {
@@ -96,23 +82,14 @@ __global__ __launch_bounds__(BEST_THREADS) void bestrb_kernel(const BestArgs a) 
         float2 h = make_float2(-1.0f, 0.0f);
         if (POWLAW) h = make_float2(a.cols[4 * D + txd], a.cols[5 * D + txd]);
         const unsigned mine = key[j];
-        int slot = 0;
-        const uint4* k4 = reinterpret_cast<const uint4*>(key);
-        for (int q = 0; q < (n4 >> 2); ++q) {
-            const uint4 k = k4[q];
-            slot += (k.x < mine) + (k.y < mine) + (k.z < mine) + (k.w < mine);
-        }
+        const int slot = same_rb_rank(key, n4, mine);
         txl[slot] = make_float4(x, y, pw, __int_as_float(j));
         if (POWLAW) hh[slot] = h;
         srb[slot] = (int)(mine >> KEY_SHIFT);
     }
     __syncthreads();
     // ---- start[r]: the first sorted entry whose RB is >= r, r in [0, R]; entries from start[R] on are on no RB
-    for (int k = tid; k <= N; k += BEST_THREADS) {
-        const int prev = k == 0 ? -1 : srb[k - 1];
-        const int cur = k == N ? R : srb[k];
-        for (int r = prev + 1; r <= cur; ++r) start[r] = k;
-    }
+    same_rb_starts<BEST_THREADS>(start, srb, N, R);
     __syncthreads();
 
     // ---- lanes own receivers
@@ -170,34 +147,19 @@ __global__ __launch_bounds__(BEST_THREADS) void bestrb_kernel(const BestArgs a) 
     }
 }
 
-template <int MODE>
-hipError_t launch(const BestArgs& a, dim3 grid, unsigned lds, hipStream_t s) {
-    if (lds > 64u * 1024u) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&bestrb_kernel<MODE>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((bestrb_kernel<MODE>), grid, dim3(BEST_THREADS), lds, s, a);
-    return hipGetLastError();
-}
-
 }  // namespace
 
 extern "C" int d2d_best_rb(const float* pos_x, const float* pos_y, const int32_t* rb, const int32_t* pwr_dbm, const int32_t* link_tx,
                            const int32_t* link_rx, const float* dev_cols, int32_t law, int32_t pow_k, int64_t n_envs, int32_t n_dev,
                            int32_t n_links, int32_t n_rbs, const uint32_t* allowed, const uint8_t* env_mask, int32_t* best_rb,
                            float* best_sinr_db, float* gain_db, void* hip_stream) try {
-    if (n_envs < 0 || n_envs > 0x7FFFFFFFll) return bestrb_fail("n_envs must be in [0, 2^31)");
-    if (n_links < 1 || n_links > D2D_BESTRB_MAX_LINKS) return bestrb_fail("n_links must be in [1, " + std::to_string(D2D_BESTRB_MAX_LINKS) + "]");
-    if (n_rbs < 1 || n_rbs > D2D_BESTRB_MAX_RBS) return bestrb_fail("n_rbs must be in [1, " + std::to_string(D2D_BESTRB_MAX_RBS) + "]");
-    if (n_dev < 1) return bestrb_fail("n_dev must be >= 1");
-    if (law != D2D_BESTRB_LAW_INV_SQUARE && law != D2D_BESTRB_LAW_POWER && law != D2D_BESTRB_LAW_POW_K) return bestrb_fail("unknown law");
-    if (law == D2D_BESTRB_LAW_POW_K && (pow_k < 1 || pow_k > 8)) return bestrb_fail("pow_k must be in [1, 8]");
+    if (const char* why = check_sizes(n_envs, n_links, D2D_BESTRB_MAX_LINKS, n_rbs, D2D_BESTRB_MAX_RBS, n_dev)) return fail(why);
+    if (const char* why = check_law(law, pow_k)) return fail(why);
     if (!pos_x || !pos_y || !rb || !pwr_dbm || !link_tx || !link_rx || !dev_cols || !best_rb || !best_sinr_db || !gain_db)
-        return bestrb_fail("null device pointer");
+        return fail("null device pointer");
     if (static_cast<void*>(best_rb) == static_cast<void*>(best_sinr_db) || static_cast<void*>(best_rb) == static_cast<void*>(gain_db) ||
         best_sinr_db == gain_db)
-        return bestrb_fail("best_rb, best_sinr_db and gain_db must be three planes");
+        return fail("best_rb, best_sinr_db and gain_db must be three planes");
     if (n_envs == 0) return 0;
     BestArgs a;
     a.pos_x = pos_x; a.pos_y = pos_y; a.rb = rb; a.pwr = pwr_dbm; a.link_tx = link_tx; a.link_rx = link_rx; a.cols = dev_cols;
@@ -209,19 +171,15 @@ extern "C" int d2d_best_rb(const float* pos_x, const float* pos_y, const int32_t
     a.off_start = a.off_hh + (law == D2D_BESTRB_LAW_INV_SQUARE ? 0u : round16(N * 8u));
     a.off_key = a.off_start + round16(((unsigned)n_rbs + 1u) * 4u);
     const unsigned lds = a.off_key + n4 * 4u + N * 4u;                   // at most 96 KiB + 32 bytes (2048 links, 8192 RBs, a power law)
-    if (lds > 160u * 1024u) return bestrb_fail("n_links and n_rbs need more than the 160 KiB of LDS a workgroup can have");
+    if (lds > 160u * 1024u) return fail("n_links and n_rbs need more than the 160 KiB of LDS a workgroup can have");
     const dim3 grid((unsigned)n_envs, (N + BEST_THREADS - 1) / BEST_THREADS);
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     hipError_t e;
-    if (law == D2D_BESTRB_LAW_INV_SQUARE) e = launch<PL_INV_SQUARE>(a, grid, lds, s);
-    else if (law == D2D_BESTRB_LAW_POWER) e = launch<PL_POWER>(a, grid, lds, s);
-    else e = launch<PL_POWK>(a, grid, lds, s);
-    if (e != hipSuccess) return bestrb_fail(std::string("bestrb_kernel launch: ") + hipGetErrorString(e));
+    if (law == D2D_BESTRB_LAW_INV_SQUARE) e = launch(&bestrb_kernel<PL_INV_SQUARE>, grid, dim3(BEST_THREADS), lds, s, a);
+    else if (law == D2D_BESTRB_LAW_POWER) e = launch(&bestrb_kernel<PL_POWER>, grid, dim3(BEST_THREADS), lds, s, a);
+    else e = launch(&bestrb_kernel<PL_POWK>, grid, dim3(BEST_THREADS), lds, s, a);
+    if (e != hipSuccess) return fail(std::string("bestrb_kernel launch: ") + hipGetErrorString(e));
     return 0;
-} catch (const std::exception& ex) {
-    return bestrb_fail(ex.what());
-} catch (...) {
-    return bestrb_fail("unknown exception");
-}
+} D2D_ADDON_CATCH
 
-extern "C" const char* d2d_bestrb_last_error(void) { return g_bestrb_error.c_str(); }
+D2D_ADDON_LAST_ERROR(d2d_bestrb_last_error)

@@ -2,8 +2,8 @@
 // round of every env in one launch.  gfx950.
 //
 // Shape: ONE workgroup per env - the dynamics couple exactly the links of one env - that stages the env once and then takes turns
-// in LDS.  Staging is the power-control kernel's (d2d_powerctl.hip), restated here so that its ISA stays what it is, minus the
-// sort: per link, by link index, the transmitter tuple (tx x, tx y, linear power x the folded tx column), the power-law head /
+// in LDS.  Staging is the power-control kernel's (d2d_powerctl.hip) minus the sort (d2d_same_rb.h), which nothing
+// here needs: per link, by link index, the transmitter tuple (tx x, tx y, linear power x the folded tx column), the power-law head /
 // tail, the receiver tuple (rx x, rx y, rx side of the path-loss constant, noise), the own-pair signal, the current rb, and the
 // first allowed RB (-1: the link never takes a turn).  RB membership is a bitset word[w][r], bit j & 31 of word j / 32 = link j
 // sits on RB r: neighbouring lanes read neighbouring words, a move is two bit flips, and a find-first-set loop over w = 0, 1, ...
@@ -24,6 +24,7 @@
 
 #include <string>
 
+#include "d2d_addon.h"
 #include "d2d_brdyn.h"
 #include "d2d_step_device.h"
 
@@ -31,15 +32,9 @@ namespace {
 
 using namespace d2d;
 
-thread_local std::string g_brdyn_error;
-
-int brdyn_fail(const std::string& msg) {
-    try { g_brdyn_error = msg; } catch (...) { }
-    return 1;
-}
-
 constexpr int BR_MAX_THREADS = 256;
 constexpr int BR_MAX_WAVES = BR_MAX_THREADS / 64;
+static_assert(D2D_BRDYN_LAW_INV_SQUARE == LAW_INV_SQUARE && D2D_BRDYN_LAW_POWER == LAW_POWER && D2D_BRDYN_LAW_POW_K == LAW_POW_K, "the laws check_law() knows (d2d_addon.h)");
 
 struct DynArgs {
     const float* pos_x;
@@ -69,7 +64,6 @@ struct DynArgs {
 
 // dynamic LDS, by link index: tx float4[N] | rx float4[N] | hh float2[N] (power laws) | sig f32[n4] | rb i32[n4] | first i32[n4] |
 // allowed u32[N * words] (with a mask) | bits u32[W][R] | keys u64[2][4], own f32[2], nan-first i32[2]
-__host__ __device__ inline unsigned round16(unsigned x) { return (x + 15u) & ~15u; }
 
 struct Lds {
     float4* tx; float4* rx; float2* hh; float* sig; int* rb; int* first; unsigned* al; unsigned* bits;
@@ -265,17 +259,6 @@ __global__ __launch_bounds__(BR_MAX_THREADS) void brdyn_kernel(const DynArgs a) 
     }
 }
 
-template <int MODE>
-hipError_t launch(const DynArgs& a, dim3 grid, unsigned threads, unsigned lds, hipStream_t s) {
-    if (lds > 64u * 1024u) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&brdyn_kernel<MODE>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((brdyn_kernel<MODE>), grid, dim3(threads), lds, s, a);
-    return hipGetLastError();
-}
-
 }  // namespace
 
 extern "C" int d2d_best_response_dynamics(const float* pos_x, const float* pos_y, const int32_t* rb, const int32_t* pwr_dbm,
@@ -284,21 +267,17 @@ extern "C" int d2d_best_response_dynamics(const float* pos_x, const float* pos_y
                                           const uint32_t* allowed, const uint8_t* movable, float min_gain_db, int32_t max_rounds,
                                           const uint8_t* env_mask, int32_t* rb_out, float* sinr_db, int32_t* rounds, int32_t* moves,
                                           uint8_t* converged, void* hip_stream) try {
-    if (n_envs < 0 || n_envs > 0x7FFFFFFFll) return brdyn_fail("n_envs must be in [0, 2^31)");
-    if (n_links < 1 || n_links > D2D_BRDYN_MAX_LINKS) return brdyn_fail("n_links must be in [1, " + std::to_string(D2D_BRDYN_MAX_LINKS) + "]");
-    if (n_rbs < 1 || n_rbs > D2D_BRDYN_MAX_RBS) return brdyn_fail("n_rbs must be in [1, " + std::to_string(D2D_BRDYN_MAX_RBS) + "]");
-    if (n_dev < 1) return brdyn_fail("n_dev must be >= 1");
+    if (const char* why = check_sizes(n_envs, n_links, D2D_BRDYN_MAX_LINKS, n_rbs, D2D_BRDYN_MAX_RBS, n_dev)) return fail(why);
     if (max_rounds < 0 || max_rounds > D2D_BRDYN_MAX_ROUNDS)
-        return brdyn_fail("max_rounds must be in [0, " + std::to_string(D2D_BRDYN_MAX_ROUNDS) + "]");
-    if (!(min_gain_db >= 0.0f)) return brdyn_fail("min_gain_db must be >= 0 and not NaN");
-    if (law != D2D_BRDYN_LAW_INV_SQUARE && law != D2D_BRDYN_LAW_POWER && law != D2D_BRDYN_LAW_POW_K) return brdyn_fail("unknown law");
-    if (law == D2D_BRDYN_LAW_POW_K && (pow_k < 1 || pow_k > 8)) return brdyn_fail("pow_k must be in [1, 8]");
+        return fail("max_rounds must be in [0, " + std::to_string(D2D_BRDYN_MAX_ROUNDS) + "]");
+    if (!(min_gain_db >= 0.0f)) return fail("min_gain_db must be >= 0 and not NaN");
+    if (const char* why = check_law(law, pow_k)) return fail(why);
     if (!pos_x || !pos_y || !rb || !pwr_dbm || !link_tx || !link_rx || !dev_cols || !rb_out || !sinr_db || !rounds || !moves || !converged)
-        return brdyn_fail("null device pointer");
+        return fail("null device pointer");
     const void* outs[5] = {rb_out, sinr_db, rounds, moves, converged};
     for (int x = 0; x < 5; ++x)
         for (int y = x + 1; y < 5; ++y)
-            if (outs[x] == outs[y]) return brdyn_fail("rb_out, sinr_db, rounds, moves and converged must be five arrays");
+            if (outs[x] == outs[y]) return fail("rb_out, sinr_db, rounds, moves and converged must be five arrays");
     DynArgs a;
     a.pos_x = pos_x; a.pos_y = pos_y; a.rb = rb; a.pwr = pwr_dbm; a.link_tx = link_tx; a.link_rx = link_rx; a.cols = dev_cols;
     a.allowed = allowed; a.movable = movable; a.env_mask = env_mask;
@@ -318,7 +297,7 @@ extern "C" int d2d_best_response_dynamics(const float* pos_x, const float* pos_y
     a.off_bits = (unsigned)off; off += ((unsigned long long)a.W * (unsigned long long)n_rbs * 4ull + 15ull) & ~15ull;
     a.off_red = (unsigned)off; off += 2ull * BR_MAX_WAVES * 8ull + 16ull;
     if (off > (unsigned long long)D2D_BRDYN_MAX_LDS_BYTES)
-        return brdyn_fail("n_links and n_rbs need " + std::to_string(off) + " bytes of LDS, more than the " +
+        return fail("n_links and n_rbs need " + std::to_string(off) + " bytes of LDS, more than the " +
                           std::to_string(D2D_BRDYN_MAX_LDS_BYTES) + " (D2D_BRDYN_MAX_LDS_BYTES) a workgroup can have");
     if (n_envs == 0) return 0;
     const unsigned lds = (unsigned)off;
@@ -326,15 +305,11 @@ extern "C" int d2d_best_response_dynamics(const float* pos_x, const float* pos_y
     const dim3 grid((unsigned)n_envs);
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     hipError_t e;
-    if (law == D2D_BRDYN_LAW_INV_SQUARE) e = launch<PL_INV_SQUARE>(a, grid, threads, lds, st);
-    else if (law == D2D_BRDYN_LAW_POWER) e = launch<PL_POWER>(a, grid, threads, lds, st);
-    else e = launch<PL_POWK>(a, grid, threads, lds, st);
-    if (e != hipSuccess) return brdyn_fail(std::string("brdyn_kernel launch: ") + hipGetErrorString(e));
+    if (law == D2D_BRDYN_LAW_INV_SQUARE) e = launch(&brdyn_kernel<PL_INV_SQUARE>, grid, dim3(threads), lds, st, a);
+    else if (law == D2D_BRDYN_LAW_POWER) e = launch(&brdyn_kernel<PL_POWER>, grid, dim3(threads), lds, st, a);
+    else e = launch(&brdyn_kernel<PL_POWK>, grid, dim3(threads), lds, st, a);
+    if (e != hipSuccess) return fail(std::string("brdyn_kernel launch: ") + hipGetErrorString(e));
     return 0;
-} catch (const std::exception& ex) {
-    return brdyn_fail(ex.what());
-} catch (...) {
-    return brdyn_fail("unknown exception");
-}
+} D2D_ADDON_CATCH
 
-extern "C" const char* d2d_brdyn_last_error(void) { return g_brdyn_error.c_str(); }
+D2D_ADDON_LAST_ERROR(d2d_brdyn_last_error)

@@ -19,17 +19,11 @@
 #include <cmath>
 #include <string>
 
+#include "d2d_addon.h"
 #include "d2d_channel.h"
 #include "d2d_step_device.h"
 
 namespace {
-
-thread_local std::string g_channel_error;
-
-int channel_fail(const std::string& msg) {
-    try { g_channel_error = msg; } catch (...) { }
-    return 1;
-}
 
 constexpr int TILE_ROWS = 32;       // transmitter rows per workgroup
 constexpr int TILE_COLS = 64;       // receiver columns per workgroup: one per lane
@@ -245,22 +239,22 @@ extern "C" int d2d_channel_fill(const float* pos_x, const float* pos_y, const in
                                 uint32_t step, uint32_t episode, const int32_t* elapsed_env, int32_t* start_env,
                                 const uint32_t* episode_env, const int32_t* reset_env, float* phase_scratch, void* table,
                                 int32_t table_dtype, void* hip_stream) try {
-    if (n_envs < 0 || n_envs > 0x7FFFFFFFll) return channel_fail("n_envs must be in [0, 2^31)");
-    if (n_links < 1 || n_links > 2048) return channel_fail("n_links must be in [1, 2048]");
-    if (n_dev < 1 || n_dev >= 65536) return channel_fail("n_dev must be in [1, 65536): the fading counter holds two device indices in one word");
-    if (first_env + (uint64_t)n_envs > (1ull << 32)) return channel_fail("first_env + n_envs must not exceed 2^32 (the env counter word)");
+    if (n_envs < 0 || n_envs > 0x7FFFFFFFll) return fail("n_envs must be in [0, 2^31)");
+    if (n_links < 1 || n_links > 2048) return fail("n_links must be in [1, 2048]");
+    if (n_dev < 1 || n_dev >= 65536) return fail("n_dev must be in [1, 65536): the fading counter holds two device indices in one word");
+    if (first_env + (uint64_t)n_envs > (1ull << 32)) return fail("first_env + n_envs must not exceed 2^32 (the env counter word)");
     if (num_sinusoids != 0 && num_sinusoids != 8 && num_sinusoids != 16 && num_sinusoids != 32)
-        return channel_fail("num_sinusoids must be 0 (no shadowing), 8, 16 or 32");
-    if (fading < D2D_CHANNEL_FADING_NONE || fading > D2D_CHANNEL_FADING_RICIAN) return channel_fail("fading must be a D2D_CHANNEL_FADING_* value");
-    if (table_dtype != D2D_CHANNEL_F32 && table_dtype != D2D_CHANNEL_F64) return channel_fail("table_dtype must be D2D_CHANNEL_F32 or D2D_CHANNEL_F64");
+        return fail("num_sinusoids must be 0 (no shadowing), 8, 16 or 32");
+    if (fading < D2D_CHANNEL_FADING_NONE || fading > D2D_CHANNEL_FADING_RICIAN) return fail("fading must be a D2D_CHANNEL_FADING_* value");
+    if (table_dtype != D2D_CHANNEL_F32 && table_dtype != D2D_CHANNEL_F64) return fail("table_dtype must be D2D_CHANNEL_F32 or D2D_CHANNEL_F64");
     if (num_sinusoids && (!std::isfinite(shadow_amp_db) || !(wave_scale > 0.0) || !std::isfinite(wave_scale)))
-        return channel_fail("shadow_amp_db must be finite and wave_scale finite and > 0");
+        return fail("shadow_amp_db must be finite and wave_scale finite and > 0");
     if (fading == D2D_CHANNEL_FADING_RICIAN && (!(rician_mu >= 0.0f) || !(rician_s > 0.0f) || !std::isfinite(rician_mu) || !std::isfinite(rician_s)))
-        return channel_fail("rician_mu must be finite and >= 0, rician_s finite and > 0");
-    if (!pos_x || !pos_y || !link_tx || !link_rx || !a_tx_db || !a_rx_db || !exponent || !table) return channel_fail("null device pointer");
-    if (num_sinusoids && !phase_scratch) return channel_fail("null device pointer: phase_scratch is needed when num_sinusoids != 0");
-    if (((uintptr_t)table | (uintptr_t)phase_scratch) & 15u) return channel_fail("table and phase_scratch must be 16-byte aligned");
-    if (reset_env && (!elapsed_env || !start_env || !episode_env)) return channel_fail("the per-env clock needs elapsed_env, start_env and episode_env");
+        return fail("rician_mu must be finite and >= 0, rician_s finite and > 0");
+    if (!pos_x || !pos_y || !link_tx || !link_rx || !a_tx_db || !a_rx_db || !exponent || !table) return fail("null device pointer");
+    if (num_sinusoids && !phase_scratch) return fail("null device pointer: phase_scratch is needed when num_sinusoids != 0");
+    if (((uintptr_t)table | (uintptr_t)phase_scratch) & 15u) return fail("table and phase_scratch must be 16-byte aligned");
+    if (reset_env && (!elapsed_env || !start_env || !episode_env)) return fail("the per-env clock needs elapsed_env, start_env and episode_env");
     if (n_envs == 0) return 0;
     FillArgs a;
     a.pos_x = pos_x; a.pos_y = pos_y; a.link_tx = link_tx; a.link_rx = link_rx; a.a_tx = a_tx_db; a.a_rx = a_rx_db; a.expo = exponent;
@@ -274,7 +268,7 @@ extern "C" int d2d_channel_fill(const float* pos_x, const float* pos_y, const in
     a.step = step; a.episode = episode;
     a.amp = shadow_amp_db; a.mu = rician_mu; a.s = rician_s;
     const unsigned long long blocks = (unsigned long long)((a.B + 7u) / 8u) * 8ull * a.row_tiles * a.col_tiles;
-    if (blocks >= 0x7FFFFFFFull) return channel_fail("n_envs * tiles must stay below 2^31 workgroups");
+    if (blocks >= 0x7FFFFFFFull) return fail("n_envs * tiles must stay below 2^31 workgroups");
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     if (num_sinusoids) {
         const dim3 grid(((a.N + SLAB_LINKS - 1) / SLAB_LINKS) * a.B);       // fewer workgroups than the fill has
@@ -282,7 +276,7 @@ extern "C" int d2d_channel_fill(const float* pos_x, const float* pos_y, const in
         else if (num_sinusoids == 16) hipLaunchKernelGGL(channel_phase_kernel<16>, grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL(channel_phase_kernel<32>, grid, dim3(256), 0, s, a);
         const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return channel_fail(std::string("channel_phase_kernel launch: ") + hipGetErrorString(e));
+        if (e != hipSuccess) return fail(std::string("channel_phase_kernel launch: ") + hipGetErrorString(e));
     }
     switch (num_sinusoids) {
         case 0: launch_fill<0>(a, fading, table_dtype == D2D_CHANNEL_F64, (unsigned)blocks, s); break;
@@ -291,12 +285,8 @@ extern "C" int d2d_channel_fill(const float* pos_x, const float* pos_y, const in
         default: launch_fill<32>(a, fading, table_dtype == D2D_CHANNEL_F64, (unsigned)blocks, s); break;
     }
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return channel_fail(std::string("channel_fill_kernel launch: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(std::string("channel_fill_kernel launch: ") + hipGetErrorString(e));
     return 0;
-} catch (const std::exception& ex) {
-    return channel_fail(ex.what());
-} catch (...) {
-    return channel_fail("unknown exception");
-}
+} D2D_ADDON_CATCH
 
-extern "C" const char* d2d_channel_last_error(void) { return g_channel_error.c_str(); }
+D2D_ADDON_LAST_ERROR(d2d_channel_last_error)

@@ -10,16 +10,10 @@
 #include <string>
 #include <type_traits>
 
+#include "d2d_addon.h"
 #include "d2d_episode.h"
 
 namespace {
-
-thread_local std::string g_episode_error;
-
-int episode_fail(const std::string& msg) {
-    try { g_episode_error = msg; } catch (...) { }
-    return 1;
-}
 
 constexpr unsigned long long GOLDEN = 0x9E3779B97F4A7C15ull, M1 = 0xBF58476D1CE4E5B9ull, M2 = 0x94D049BB133111EBull;
 
@@ -142,9 +136,9 @@ int device_cus() {
 extern "C" int d2d_episode_merge_actions(const int32_t* actions_in, int32_t* actions_out, const int32_t* pending, const uint32_t* episode,
                                          const int32_t* high, int64_t n_envs, int32_t n_cols, uint64_t first_env, uint64_t seed,
                                          void* hip_stream) try {
-    if (n_envs < 0 || n_cols < 0) return episode_fail("n_envs and n_cols must be >= 0");
+    if (n_envs < 0 || n_cols < 0) return fail("n_envs and n_cols must be >= 0");
     if (n_envs == 0 || n_cols == 0) return 0;
-    if (!actions_in || !actions_out || !pending || !episode || !high) return episode_fail("null device pointer");
+    if (!actions_in || !actions_out || !pending || !episode || !high) return fail("null device pointer");
     MergeArgs a;
     a.total = (unsigned long long)n_envs * (unsigned long long)n_cols;
     a.first_env = first_env;
@@ -161,32 +155,24 @@ extern "C" int d2d_episode_merge_actions(const int32_t* actions_in, int32_t* act
     if (vec) hipLaunchKernelGGL(merge_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, actions_in, actions_out, pending, ep, high, a);
     else hipLaunchKernelGGL(merge_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, s, actions_in, actions_out, pending, ep, high, a);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return episode_fail(std::string("merge_kernel launch: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(std::string("merge_kernel launch: ") + hipGetErrorString(e));
     return 0;
-} catch (const std::exception& ex) {
-    return episode_fail(ex.what());
-} catch (...) {
-    return episode_fail("unknown exception");
-}
+} D2D_ADDON_CATCH
 
 extern "C" int d2d_episode_advance(int32_t* pending, uint32_t* episode, int32_t* elapsed, uint8_t* done, uint8_t* reset_out, float* reward,
                                    int32_t reward_cols, int64_t n_envs, int32_t episode_length, void* hip_stream) try {
-    if (n_envs < 0) return episode_fail("n_envs must be >= 0");
-    if (episode_length < 1) return episode_fail("episode_length must be >= 1");
-    if (reward && reward_cols < 1) return episode_fail("reward_cols must be >= 1 with a reward");
+    if (n_envs < 0) return fail("n_envs must be >= 0");
+    if (episode_length < 1) return fail("episode_length must be >= 1");
+    if (reward && reward_cols < 1) return fail("reward_cols must be >= 1 with a reward");
     if (n_envs == 0) return 0;
-    if (!pending || !episode || !elapsed || !done || !reset_out) return episode_fail("null device pointer");
+    if (!pending || !episode || !elapsed || !done || !reset_out) return fail("null device pointer");
     AdvanceArgs a{pending, reinterpret_cast<unsigned*>(episode), elapsed, done, reset_out, reward, reward ? (unsigned)reward_cols : 0u,
                   (unsigned long long)n_envs, episode_length};
     hipLaunchKernelGGL(advance_kernel, dim3((unsigned)(((unsigned long long)n_envs + 255) / 256)), dim3(256), 0,
                        static_cast<hipStream_t>(hip_stream), a);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return episode_fail(std::string("advance_kernel launch: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(std::string("advance_kernel launch: ") + hipGetErrorString(e));
     return 0;
-} catch (const std::exception& ex) {
-    return episode_fail(ex.what());
-} catch (...) {
-    return episode_fail("unknown exception");
-}
+} D2D_ADDON_CATCH
 
-extern "C" const char* d2d_episode_last_error(void) { return g_episode_error.c_str(); }
+D2D_ADDON_LAST_ERROR(d2d_episode_last_error)

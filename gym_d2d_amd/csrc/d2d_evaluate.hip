@@ -17,26 +17,20 @@
 
 #include <string>
 
+#include "d2d_addon.h"
 #include "d2d_evaluate.h"
+#include "d2d_same_rb.h"
 #include "d2d_step_device.h"
 
 namespace {
 
 using namespace d2d;
 
-thread_local std::string g_evaluate_error;
-
-int evaluate_fail(const std::string& msg) {
-    try { g_evaluate_error = msg; } catch (...) { }
-    return 1;
-}
-
 constexpr int EVAL_THREADS = 256;
 constexpr int EVAL_WAVES = EVAL_THREADS / 64;
 constexpr int EVAL_CHUNK = D2D_EVALUATE_CHUNK;
-constexpr unsigned KEY_SHIFT = 11;                               // key = rb << 11 | j, j < 2048
-static_assert((1 << KEY_SHIFT) == D2D_EVALUATE_MAX_LINKS, "the key packs the link index into KEY_SHIFT bits");
-static_assert((unsigned long long)(D2D_EVALUATE_MAX_RBS + 1) << KEY_SHIFT < 0xFFFFFFFFull, "keys are 32 bits, all ones is the padding");
+static_assert(D2D_EVALUATE_MAX_LINKS == SAME_RB_MAX_LINKS && D2D_EVALUATE_MAX_RBS == SAME_RB_MAX_RBS, "the limits of the shared sort (d2d_same_rb.h)");
+static_assert(D2D_EVALUATE_LAW_INV_SQUARE == LAW_INV_SQUARE && D2D_EVALUATE_LAW_POWER == LAW_POWER && D2D_EVALUATE_LAW_POW_K == LAW_POW_K, "the laws check_law() knows (d2d_addon.h)");
 static_assert(D2D_EVALUATE_MAX_CANDIDATES == 65535 * EVAL_CHUNK, "the grid's second dimension holds 65535 chunks");
 
 struct EvaluateArgs {
@@ -62,7 +56,6 @@ struct EvaluateArgs {
 // rewritten by every candidate, by sorted slot:
 //   txl float4[N] (tx x, tx y, linear EIRP incl. the tx constant, link index) | shh float2[N] (power laws) | key u32[N rounded up
 //   to 4] | srb int[N] | start int[R + 1] | wsum double[4]
-__host__ __device__ inline unsigned round16(unsigned x) { return (x + 15u) & ~15u; }
 
 template <int MODE>
 __global__ __launch_bounds__(EVAL_THREADS) void evaluate_kernel(const EvaluateArgs a) {
@@ -104,14 +97,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void evaluate_kernel(const EvaluateAr
 
         // ---- keys: (rb, link index); a link whose rb is outside [0, R) takes the pseudo RB R behind every real one.
         // key was last read by the sort of the candidate before, which lies behind two barriers.
-        for (int j = tid; j < n4; j += EVAL_THREADS) {
-            unsigned k = 0xFFFFFFFFu;
-            if (j < N) {
-                const int r = rb_row[j];
-                k = ((unsigned)((unsigned)r < (unsigned)R ? r : R) << KEY_SHIFT) | (unsigned)j;
-            }
-            key[j] = k;
-        }
+        same_rb_keys<EVAL_THREADS>(key, rb_row, N, n4, R);
         __syncthreads();
         // ---- rank sort: link j goes to slot #{keys below its own}; the keys are distinct, so the slots are a permutation and every
         // word of txl / shh / srb is rewritten.  Their last readers (the walk of the candidate before) lie behind barrier 4.
@@ -119,12 +105,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void evaluate_kernel(const EvaluateAr
             const float4 t = stx[j];
             const float pw = pow10_tenth(pwr_row[j]) * t.z;                          // the step's tuple.z (d2d_step.hip, pass 1)
             const unsigned mine = key[j];
-            int slot = 0;
-            const uint4* k4 = reinterpret_cast<const uint4*>(key);
-            for (int q = 0; q < (n4 >> 2); ++q) {
-                const uint4 k = k4[q];
-                slot += (k.x < mine) + (k.y < mine) + (k.z < mine) + (k.w < mine);
-            }
+            const int slot = same_rb_rank(key, n4, mine);
             txl[slot] = make_float4(t.x, t.y, pw, __int_as_float(j));
             if (POWLAW) shh[slot] = hh[j];
             srb[slot] = (int)(mine >> KEY_SHIFT);
@@ -132,11 +113,7 @@ __global__ __launch_bounds__(EVAL_THREADS) void evaluate_kernel(const EvaluateAr
         __syncthreads();
         // ---- start[r]: the first sorted entry whose RB is >= r, r in [0, R]; entries from start[R] on are on no RB.  Every word of
         // start[0..R] is rewritten: the ranges (prev, cur] of k = 0..N tile [0, R].
-        for (int k = tid; k <= N; k += EVAL_THREADS) {
-            const int prev = k == 0 ? -1 : srb[k - 1];
-            const int cur = k == N ? R : srb[k];
-            for (int r = prev + 1; r <= cur; ++r) start[r] = k;
-        }
+        same_rb_starts<EVAL_THREADS>(start, srb, N, R);
         __syncthreads();
 
         // ---- the walk: the slot's link as receiver (d2d_marginal.hip, phase 1)
@@ -191,33 +168,19 @@ __global__ __launch_bounds__(EVAL_THREADS) void evaluate_kernel(const EvaluateAr
     }
 }
 
-template <int MODE>
-hipError_t launch(const EvaluateArgs& a, dim3 grid, unsigned lds, hipStream_t s) {
-    if (lds > 64u * 1024u) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&evaluate_kernel<MODE>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((evaluate_kernel<MODE>), grid, dim3(EVAL_THREADS), lds, s, a);
-    return hipGetLastError();
-}
-
 }  // namespace
 
 extern "C" int d2d_evaluate(const float* pos_x, const float* pos_y, const int32_t* rb, const int32_t* pwr_dbm, const int32_t* link_tx,
                             const int32_t* link_rx, const float* dev_cols, const float* cap_cols, int32_t law, int32_t pow_k,
                             int64_t n_envs, int32_t n_cand, int32_t n_dev, int32_t n_links, int32_t n_rbs, float* sinr_db,
                             float* capacity_mbps, float* total_mbps, void* hip_stream) try {
-    if (n_envs < 0 || n_envs > 0x7FFFFFFFll) return evaluate_fail("n_envs must be in [0, 2^31)");
-    if (n_cand < 1 || n_cand > D2D_EVALUATE_MAX_CANDIDATES) return evaluate_fail("n_cand must be in [1, " + std::to_string(D2D_EVALUATE_MAX_CANDIDATES) + "]");
-    if (n_links < 1 || n_links > D2D_EVALUATE_MAX_LINKS) return evaluate_fail("n_links must be in [1, " + std::to_string(D2D_EVALUATE_MAX_LINKS) + "]");
-    if (n_rbs < 1 || n_rbs > D2D_EVALUATE_MAX_RBS) return evaluate_fail("n_rbs must be in [1, " + std::to_string(D2D_EVALUATE_MAX_RBS) + "]");
-    if (n_dev < 1) return evaluate_fail("n_dev must be >= 1");
-    if (law != D2D_EVALUATE_LAW_INV_SQUARE && law != D2D_EVALUATE_LAW_POWER && law != D2D_EVALUATE_LAW_POW_K) return evaluate_fail("unknown law");
-    if (law == D2D_EVALUATE_LAW_POW_K && (pow_k < 1 || pow_k > 8)) return evaluate_fail("pow_k must be in [1, 8]");
+    if (n_envs < 0 || n_envs > 0x7FFFFFFFll) return fail("n_envs must be in [0, 2^31)");
+    if (n_cand < 1 || n_cand > D2D_EVALUATE_MAX_CANDIDATES) return fail("n_cand must be in [1, " + std::to_string(D2D_EVALUATE_MAX_CANDIDATES) + "]");
+    if (const char* why = check_sizes(n_envs, n_links, D2D_EVALUATE_MAX_LINKS, n_rbs, D2D_EVALUATE_MAX_RBS, n_dev)) return fail(why);
+    if (const char* why = check_law(law, pow_k)) return fail(why);
     if (!pos_x || !pos_y || !rb || !pwr_dbm || !link_tx || !link_rx || !dev_cols || !cap_cols || !total_mbps)
-        return evaluate_fail("null device pointer");
-    if (sinr_db && sinr_db == capacity_mbps) return evaluate_fail("sinr_db and capacity_mbps must be two planes");
+        return fail("null device pointer");
+    if (sinr_db && sinr_db == capacity_mbps) return fail("sinr_db and capacity_mbps must be two planes");
     EvaluateArgs a;
     a.pos_x = pos_x; a.pos_y = pos_y; a.rb = rb; a.pwr = pwr_dbm; a.link_tx = link_tx; a.link_rx = link_rx; a.cols = dev_cols;
     a.cap_cols = cap_cols; a.sinr = sinr_db; a.cap = capacity_mbps; a.total = total_mbps;
@@ -235,21 +198,17 @@ extern "C" int d2d_evaluate(const float* pos_x, const float* pos_y, const int32_
     a.off_wsum = a.off_start + round16(((unsigned)n_rbs + 1u) * 4u);
     const unsigned lds = a.off_wsum + (unsigned)(EVAL_WAVES * sizeof(double));
     if (lds > (unsigned)D2D_EVALUATE_MAX_LDS_BYTES)
-        return evaluate_fail("n_links and n_rbs need " + std::to_string(lds) + " bytes of LDS, more than the " +
+        return fail("n_links and n_rbs need " + std::to_string(lds) + " bytes of LDS, more than the " +
                              std::to_string(D2D_EVALUATE_MAX_LDS_BYTES) + " a workgroup can have");
     if (n_envs == 0) return 0;
     const dim3 grid((unsigned)n_envs, (unsigned)((n_cand + EVAL_CHUNK - 1) / EVAL_CHUNK));
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     hipError_t e;
-    if (law == D2D_EVALUATE_LAW_INV_SQUARE) e = launch<PL_INV_SQUARE>(a, grid, lds, s);
-    else if (law == D2D_EVALUATE_LAW_POWER) e = launch<PL_POWER>(a, grid, lds, s);
-    else e = launch<PL_POWK>(a, grid, lds, s);
-    if (e != hipSuccess) return evaluate_fail(std::string("evaluate_kernel launch: ") + hipGetErrorString(e));
+    if (law == D2D_EVALUATE_LAW_INV_SQUARE) e = launch(&evaluate_kernel<PL_INV_SQUARE>, grid, dim3(EVAL_THREADS), lds, s, a);
+    else if (law == D2D_EVALUATE_LAW_POWER) e = launch(&evaluate_kernel<PL_POWER>, grid, dim3(EVAL_THREADS), lds, s, a);
+    else e = launch(&evaluate_kernel<PL_POWK>, grid, dim3(EVAL_THREADS), lds, s, a);
+    if (e != hipSuccess) return fail(std::string("evaluate_kernel launch: ") + hipGetErrorString(e));
     return 0;
-} catch (const std::exception& ex) {
-    return evaluate_fail(ex.what());
-} catch (...) {
-    return evaluate_fail("unknown exception");
-}
+} D2D_ADDON_CATCH
 
-extern "C" const char* d2d_evaluate_last_error(void) { return g_evaluate_error.c_str(); }
+D2D_ADDON_LAST_ERROR(d2d_evaluate_last_error)

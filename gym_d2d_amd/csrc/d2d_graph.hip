@@ -22,6 +22,7 @@
 
 #include <string>
 
+#include "d2d_addon.h"
 #include "d2d_graph.h"
 #include "d2d_sense.h"
 #include "d2d_step_device.h"
@@ -31,19 +32,13 @@ namespace {
 
 using namespace d2d;
 
-thread_local std::string g_graph_error;
-
-int graph_fail(const std::string& msg) {
-    try { g_graph_error = msg; } catch (...) { }
-    return 1;
-}
-
 constexpr int GRAPH_THREADS = 256;
 constexpr int GRAPH_WAVES = GRAPH_THREADS / 64;
 constexpr int COUPLING_ROWS = 128;                               // receivers per workgroup of coupling_kernel: 32 per wave
 constexpr int NEIGHBOR_ROWS = 64;                                // receivers per workgroup of neighbors_kernel: 16 per wave
 static_assert(D2D_GRAPH_MAX_K <= 64, "a lane holds one rank of the result");
 static_assert(D2D_GRAPH_MAX_LINKS == D2D_SENSE_MAX_LINKS, "one link limit");
+static_assert(D2D_SENSE_LAW_INV_SQUARE == LAW_INV_SQUARE && D2D_SENSE_LAW_POWER == LAW_POWER && D2D_SENSE_LAW_POW_K == LAW_POW_K, "the laws check_law() knows (d2d_addon.h)");
 
 struct GraphArgs {
     const float* pos_x;
@@ -260,29 +255,14 @@ __global__ __launch_bounds__(GRAPH_THREADS) void neighbor_obs_kernel(const Neigh
 }
 
 const char* check_common(int32_t law, int32_t pow_k, int64_t n_envs, int32_t n_dev, int32_t n_links) {
-    if (n_envs < 0 || n_envs > 0x7FFFFFFFll) return "n_envs must be in [0, 2^31)";
-    if (n_links < 1 || n_links > D2D_GRAPH_MAX_LINKS) return "n_links must be in [1, 2048]";
-    if (n_dev < 1) return "n_dev must be >= 1";
-    if (law != D2D_SENSE_LAW_INV_SQUARE && law != D2D_SENSE_LAW_POWER && law != D2D_SENSE_LAW_POW_K) return "unknown law";
-    if (law == D2D_SENSE_LAW_POW_K && (pow_k < 1 || pow_k > 8)) return "pow_k must be in [1, 8]";
-    return nullptr;
+    if (const char* why = check_sizes(n_envs, n_links, D2D_GRAPH_MAX_LINKS, 0, 0, n_dev)) return why;
+    return check_law(law, pow_k);
 }
 
 template <int MODE>
 hipError_t launch_coupling(const GraphArgs& a, float* out, bool vec, dim3 grid, hipStream_t s) {
     if (vec) hipLaunchKernelGGL((coupling_kernel<MODE, true>), grid, dim3(GRAPH_THREADS), 0, s, a, out);
     else hipLaunchKernelGGL((coupling_kernel<MODE, false>), grid, dim3(GRAPH_THREADS), 0, s, a, out);
-    return hipGetLastError();
-}
-
-template <int MODE>
-hipError_t launch_neighbors(const NeighborArgs& a, dim3 grid, unsigned lds, hipStream_t s) {
-    if (lds > 64u * 1024u) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&neighbors_kernel<MODE>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((neighbors_kernel<MODE>), grid, dim3(GRAPH_THREADS), lds, s, a);
     return hipGetLastError();
 }
 
@@ -299,8 +279,8 @@ GraphArgs graph_args(const float* pos_x, const float* pos_y, const int32_t* link
 extern "C" int d2d_graph_coupling(const float* pos_x, const float* pos_y, const int32_t* link_tx, const int32_t* link_rx,
                                   const float* dev_cols, int32_t law, int32_t pow_k, int64_t n_envs, int32_t n_dev, int32_t n_links,
                                   float* out, void* hip_stream) try {
-    if (const char* why = check_common(law, pow_k, n_envs, n_dev, n_links)) return graph_fail(why);
-    if (!pos_x || !pos_y || !link_tx || !link_rx || !dev_cols || !out) return graph_fail("null device pointer");
+    if (const char* why = check_common(law, pow_k, n_envs, n_dev, n_links)) return fail(why);
+    if (!pos_x || !pos_y || !link_tx || !link_rx || !dev_cols || !out) return fail("null device pointer");
     if (n_envs == 0) return 0;
     const GraphArgs a = graph_args(pos_x, pos_y, link_tx, link_rx, dev_cols, pow_k, n_dev, n_links);
     const bool vec = reinterpret_cast<uintptr_t>(out) % 16 == 0 && n_links % 4 == 0;
@@ -309,21 +289,17 @@ extern "C" int d2d_graph_coupling(const float* pos_x, const float* pos_y, const 
     const hipError_t e = law == D2D_SENSE_LAW_INV_SQUARE ? launch_coupling<PL_INV_SQUARE>(a, out, vec, grid, s)
                          : law == D2D_SENSE_LAW_POWER    ? launch_coupling<PL_POWER>(a, out, vec, grid, s)
                                                          : launch_coupling<PL_POWK>(a, out, vec, grid, s);
-    if (e != hipSuccess) return graph_fail(std::string("coupling_kernel launch: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(std::string("coupling_kernel launch: ") + hipGetErrorString(e));
     return 0;
-} catch (const std::exception& ex) {
-    return graph_fail(ex.what());
-} catch (...) {
-    return graph_fail("unknown exception");
-}
+} D2D_ADDON_CATCH
 
 extern "C" int d2d_graph_neighbors(const float* pos_x, const float* pos_y, const int32_t* link_tx, const int32_t* link_rx,
                                    const float* dev_cols, int32_t law, int32_t pow_k, int64_t n_envs, int32_t n_dev, int32_t n_links,
                                    int32_t k, const uint8_t* env_mask, int32_t* idx, float* coupling_db, void* hip_stream) try {
-    if (const char* why = check_common(law, pow_k, n_envs, n_dev, n_links)) return graph_fail(why);
+    if (const char* why = check_common(law, pow_k, n_envs, n_dev, n_links)) return fail(why);
     const int k_max = n_links - 1 < D2D_GRAPH_MAX_K ? n_links - 1 : D2D_GRAPH_MAX_K;
-    if (k < 1 || k > k_max) return graph_fail("k must be in [1, min(n_links - 1, " + std::to_string(D2D_GRAPH_MAX_K) + ")]");
-    if (!pos_x || !pos_y || !link_tx || !link_rx || !dev_cols || !idx || !coupling_db) return graph_fail("null device pointer");
+    if (k < 1 || k > k_max) return fail("k must be in [1, min(n_links - 1, " + std::to_string(D2D_GRAPH_MAX_K) + ")]");
+    if (!pos_x || !pos_y || !link_tx || !link_rx || !dev_cols || !idx || !coupling_db) return fail("null device pointer");
     if (n_envs == 0) return 0;
     NeighborArgs a;
     a.g = graph_args(pos_x, pos_y, link_tx, link_rx, dev_cols, pow_k, n_dev, n_links);
@@ -335,24 +311,21 @@ extern "C" int d2d_graph_neighbors(const float* pos_x, const float* pos_y, const
     const unsigned lds = a.off_keys + GRAPH_WAVES * a.n64 * 4u;          // 80 KiB at 2048 links
     const dim3 grid((unsigned)n_envs, (N + NEIGHBOR_ROWS - 1) / NEIGHBOR_ROWS);
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    const hipError_t e = law == D2D_SENSE_LAW_INV_SQUARE ? launch_neighbors<PL_INV_SQUARE>(a, grid, lds, s)
-                         : law == D2D_SENSE_LAW_POWER    ? launch_neighbors<PL_POWER>(a, grid, lds, s)
-                                                         : launch_neighbors<PL_POWK>(a, grid, lds, s);
-    if (e != hipSuccess) return graph_fail(std::string("neighbors_kernel launch: ") + hipGetErrorString(e));
+    const dim3 block(GRAPH_THREADS);
+    const hipError_t e = law == D2D_SENSE_LAW_INV_SQUARE ? launch(&neighbors_kernel<PL_INV_SQUARE>, grid, block, lds, s, a)
+                         : law == D2D_SENSE_LAW_POWER    ? launch(&neighbors_kernel<PL_POWER>, grid, block, lds, s, a)
+                                                         : launch(&neighbors_kernel<PL_POWK>, grid, block, lds, s, a);
+    if (e != hipSuccess) return fail(std::string("neighbors_kernel launch: ") + hipGetErrorString(e));
     return 0;
-} catch (const std::exception& ex) {
-    return graph_fail(ex.what());
-} catch (...) {
-    return graph_fail("unknown exception");
-}
+} D2D_ADDON_CATCH
 
 extern "C" int d2d_graph_neighbor_obs(const int32_t* idx, const float* coupling_db, const int32_t* rb, const int32_t* pwr_dbm,
                                       const float* sinr_db, const float* snr_db, int64_t n_envs, int32_t n_links, int32_t k, float* out,
                                       void* hip_stream) try {
-    if (n_envs < 0 || n_envs > 0x7FFFFFFFll) return graph_fail("n_envs must be in [0, 2^31)");
-    if (n_links < 1 || n_links > D2D_GRAPH_MAX_LINKS) return graph_fail("n_links must be in [1, 2048]");
-    if (k < 0 || k > D2D_GRAPH_MAX_K) return graph_fail("k must be in [0, " + std::to_string(D2D_GRAPH_MAX_K) + "]");
-    if (!rb || !pwr_dbm || !sinr_db || !snr_db || !out || (k > 0 && (!idx || !coupling_db))) return graph_fail("null device pointer");
+    if (n_envs < 0 || n_envs > 0x7FFFFFFFll) return fail("n_envs must be in [0, 2^31)");
+    if (n_links < 1 || n_links > D2D_GRAPH_MAX_LINKS) return fail("n_links must be in [1, 2048]");
+    if (k < 0 || k > D2D_GRAPH_MAX_K) return fail("k must be in [0, " + std::to_string(D2D_GRAPH_MAX_K) + "]");
+    if (!rb || !pwr_dbm || !sinr_db || !snr_db || !out || (k > 0 && (!idx || !coupling_db))) return fail("null device pointer");
     if (n_envs == 0) return 0;
     NeighborObsArgs a;
     a.idx = idx; a.coupling_db = coupling_db; a.rb = rb; a.pwr = pwr_dbm; a.sinr = sinr_db; a.snr = snr_db; a.out = out;
@@ -363,12 +336,8 @@ extern "C" int d2d_graph_neighbor_obs(const int32_t* idx, const float* coupling_
     const dim3 grid((unsigned)(blocks < (1ull << 20) ? blocks : (1ull << 20)));
     hipLaunchKernelGGL(neighbor_obs_kernel, grid, dim3(GRAPH_THREADS), 0, static_cast<hipStream_t>(hip_stream), a);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return graph_fail(std::string("neighbor_obs_kernel launch: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(std::string("neighbor_obs_kernel launch: ") + hipGetErrorString(e));
     return 0;
-} catch (const std::exception& ex) {
-    return graph_fail(ex.what());
-} catch (...) {
-    return graph_fail("unknown exception");
-}
+} D2D_ADDON_CATCH
 
-extern "C" const char* d2d_graph_last_error(void) { return g_graph_error.c_str(); }
+D2D_ADDON_LAST_ERROR(d2d_graph_last_error)

@@ -18,24 +18,18 @@
 
 #include <string>
 
+#include "d2d_addon.h"
 #include "d2d_marginal.h"
+#include "d2d_same_rb.h"
 #include "d2d_step_device.h"
 
 namespace {
 
 using namespace d2d;
 
-thread_local std::string g_marginal_error;
-
-int marginal_fail(const std::string& msg) {
-    try { g_marginal_error = msg; } catch (...) { }
-    return 1;
-}
-
 constexpr int MARG_THREADS = 256;
-constexpr unsigned KEY_SHIFT = 11;                               // key = rb << 11 | j, j < 2048
-static_assert((1 << KEY_SHIFT) == D2D_MARGINAL_MAX_LINKS, "the key packs the link index into KEY_SHIFT bits");
-static_assert((unsigned long long)(D2D_MARGINAL_MAX_RBS + 1) << KEY_SHIFT < 0xFFFFFFFFull, "keys are 32 bits, all ones is the padding");
+static_assert(D2D_MARGINAL_MAX_LINKS == SAME_RB_MAX_LINKS && D2D_MARGINAL_MAX_RBS == SAME_RB_MAX_RBS, "the limits of the shared sort (d2d_same_rb.h)");
+static_assert(D2D_MARGINAL_LAW_INV_SQUARE == LAW_INV_SQUARE && D2D_MARGINAL_LAW_POWER == LAW_POWER && D2D_MARGINAL_LAW_POW_K == LAW_POW_K, "the laws check_law() knows (d2d_addon.h)");
 
 struct MarginalArgs {
     const float* pos_x;
@@ -55,7 +49,6 @@ struct MarginalArgs {
 
 // dynamic LDS: tuples float4[N] | hh float2[N] (power laws) | v0 float4[N] | v1 float4[N] | acc double[N], whose bytes first hold the
 // sort's keys u32[N rounded up to 4] | cap float[N] | srb int[N] | start int[R + 1]
-__host__ __device__ inline unsigned round16(unsigned x) { return (x + 15u) & ~15u; }
 
 // log2(1 + x) with relative accuracy for small x: log2(u) * x / (u - 1), u = fl(1 + x) (the step's form of its Shannon term)
 __device__ __forceinline__ float log2_1p(float x) {
@@ -87,14 +80,7 @@ __global__ __launch_bounds__(MARG_THREADS) void marginal_kernel(const MarginalAr
     const float* py = a.pos_y + b * (size_t)D;
 
     // ---- keys: (rb, link index); a link whose rb is outside [0, R) takes the pseudo RB R behind every real one
-    for (int j = tid; j < n4; j += MARG_THREADS) {
-        unsigned k = 0xFFFFFFFFu;
-        if (j < N) {
-            const int r = rb_row[j];
-            k = ((unsigned)((unsigned)r < (unsigned)R ? r : R) << KEY_SHIFT) | (unsigned)j;
-        }
-        key[j] = k;
-    }
+    same_rb_keys<MARG_THREADS>(key, rb_row, N, n4, R);
     __syncthreads();
     // ---- rank sort: link j goes to slot #{keys below its own}; the keys are distinct, so the slots are a permutation
     for (int j = tid; j < N; j += MARG_THREADS) {
@@ -104,23 +90,14 @@ __global__ __launch_bounds__(MARG_THREADS) void marginal_kernel(const MarginalAr
         float2 h = make_float2(-1.0f, 0.0f);
         if (POWLAW) h = make_float2(a.cols[4 * D + txd], a.cols[5 * D + txd]);
         const unsigned mine = key[j];
-        int slot = 0;
-        const uint4* k4 = reinterpret_cast<const uint4*>(key);
-        for (int q = 0; q < (n4 >> 2); ++q) {
-            const uint4 k = k4[q];
-            slot += (k.x < mine) + (k.y < mine) + (k.z < mine) + (k.w < mine);
-        }
+        const int slot = same_rb_rank(key, n4, mine);
         txl[slot] = make_float4(x, y, pw, __int_as_float(j));
         if (POWLAW) hh[slot] = h;
         srb[slot] = (int)(mine >> KEY_SHIFT);
     }
     __syncthreads();                 // the last use of key: its bytes are the interference sums from here on
     // ---- start[r]: the first sorted entry whose RB is >= r, r in [0, R]; entries from start[R] on are on no RB
-    for (int k = tid; k <= N; k += MARG_THREADS) {
-        const int prev = k == 0 ? -1 : srb[k - 1];
-        const int cur = k == N ? R : srb[k];
-        for (int r = prev + 1; r <= cur; ++r) start[r] = k;
-    }
+    same_rb_starts<MARG_THREADS>(start, srb, N, R);
     __syncthreads();
 
     // ---- phase 1: the slot's link as receiver
@@ -198,32 +175,17 @@ __global__ __launch_bounds__(MARG_THREADS) void marginal_kernel(const MarginalAr
     }
 }
 
-template <int MODE>
-hipError_t launch(const MarginalArgs& a, dim3 grid, unsigned lds, hipStream_t s) {
-    if (lds > 64u * 1024u) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&marginal_kernel<MODE>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((marginal_kernel<MODE>), grid, dim3(MARG_THREADS), lds, s, a);
-    return hipGetLastError();
-}
-
 }  // namespace
 
 extern "C" int d2d_marginal_capacity(const float* pos_x, const float* pos_y, const int32_t* rb, const int32_t* pwr_dbm,
                                      const int32_t* link_tx, const int32_t* link_rx, const float* dev_cols, const float* cap_cols,
                                      int32_t law, int32_t pow_k, int64_t n_envs, int32_t n_dev, int32_t n_links, int32_t n_rbs,
                                      float* harm_mbps, float* difference_mbps, void* hip_stream) try {
-    if (n_envs < 0 || n_envs > 0x7FFFFFFFll) return marginal_fail("n_envs must be in [0, 2^31)");
-    if (n_links < 1 || n_links > D2D_MARGINAL_MAX_LINKS) return marginal_fail("n_links must be in [1, " + std::to_string(D2D_MARGINAL_MAX_LINKS) + "]");
-    if (n_rbs < 1 || n_rbs > D2D_MARGINAL_MAX_RBS) return marginal_fail("n_rbs must be in [1, " + std::to_string(D2D_MARGINAL_MAX_RBS) + "]");
-    if (n_dev < 1) return marginal_fail("n_dev must be >= 1");
-    if (law != D2D_MARGINAL_LAW_INV_SQUARE && law != D2D_MARGINAL_LAW_POWER && law != D2D_MARGINAL_LAW_POW_K) return marginal_fail("unknown law");
-    if (law == D2D_MARGINAL_LAW_POW_K && (pow_k < 1 || pow_k > 8)) return marginal_fail("pow_k must be in [1, 8]");
+    if (const char* why = check_sizes(n_envs, n_links, D2D_MARGINAL_MAX_LINKS, n_rbs, D2D_MARGINAL_MAX_RBS, n_dev)) return fail(why);
+    if (const char* why = check_law(law, pow_k)) return fail(why);
     if (!pos_x || !pos_y || !rb || !pwr_dbm || !link_tx || !link_rx || !dev_cols || !cap_cols || !harm_mbps || !difference_mbps)
-        return marginal_fail("null device pointer");
-    if (harm_mbps == difference_mbps) return marginal_fail("harm_mbps and difference_mbps must be two planes");
+        return fail("null device pointer");
+    if (harm_mbps == difference_mbps) return fail("harm_mbps and difference_mbps must be two planes");
     if (n_envs == 0) return 0;
     MarginalArgs a;
     a.pos_x = pos_x; a.pos_y = pos_y; a.rb = rb; a.pwr = pwr_dbm; a.link_tx = link_tx; a.link_rx = link_rx; a.cols = dev_cols;
@@ -238,19 +200,15 @@ extern "C" int d2d_marginal_capacity(const float* pos_x, const float* pos_y, con
     a.off_srb = a.off_cap + round16(N * 4u);
     a.off_start = a.off_srb + round16(N * 4u);
     const unsigned lds = a.off_start + round16(((unsigned)n_rbs + 1u) * 4u);
-    if (lds > 160u * 1024u) return marginal_fail("n_links and n_rbs need more than the 160 KiB of LDS a workgroup can have");
+    if (lds > 160u * 1024u) return fail("n_links and n_rbs need more than the 160 KiB of LDS a workgroup can have");
     const dim3 grid((unsigned)n_envs);
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     hipError_t e;
-    if (law == D2D_MARGINAL_LAW_INV_SQUARE) e = launch<PL_INV_SQUARE>(a, grid, lds, s);
-    else if (law == D2D_MARGINAL_LAW_POWER) e = launch<PL_POWER>(a, grid, lds, s);
-    else e = launch<PL_POWK>(a, grid, lds, s);
-    if (e != hipSuccess) return marginal_fail(std::string("marginal_kernel launch: ") + hipGetErrorString(e));
+    if (law == D2D_MARGINAL_LAW_INV_SQUARE) e = launch(&marginal_kernel<PL_INV_SQUARE>, grid, dim3(MARG_THREADS), lds, s, a);
+    else if (law == D2D_MARGINAL_LAW_POWER) e = launch(&marginal_kernel<PL_POWER>, grid, dim3(MARG_THREADS), lds, s, a);
+    else e = launch(&marginal_kernel<PL_POWK>, grid, dim3(MARG_THREADS), lds, s, a);
+    if (e != hipSuccess) return fail(std::string("marginal_kernel launch: ") + hipGetErrorString(e));
     return 0;
-} catch (const std::exception& ex) {
-    return marginal_fail(ex.what());
-} catch (...) {
-    return marginal_fail("unknown exception");
-}
+} D2D_ADDON_CATCH
 
-extern "C" const char* d2d_marginal_last_error(void) { return g_marginal_error.c_str(); }
+D2D_ADDON_LAST_ERROR(d2d_marginal_last_error)

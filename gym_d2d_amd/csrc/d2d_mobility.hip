@@ -10,17 +10,11 @@
 #include <cmath>
 #include <string>
 
+#include "d2d_addon.h"
 #include "d2d_mobility.h"
 #include "d2d_step_device.h"
 
 namespace {
-
-thread_local std::string g_mobility_error;
-
-int mobility_fail(const std::string& msg) {
-    try { g_mobility_error = msg; } catch (...) { }
-    return 1;
-}
 
 struct MoveArgs {
     float* pos_x;
@@ -123,17 +117,17 @@ extern "C" int d2d_mobility_move(float* pos_x, float* pos_y, float* vel_x, float
                                  float noise_scale, float speed_std, float dt_s, float cell_radius_m, float d2d_radius_m, uint32_t step,
                                  uint32_t episode, const int32_t* elapsed_env, int32_t* start_env, const uint32_t* episode_env,
                                  const int32_t* reset_env, void* hip_stream) try {
-    if (n_envs < 0 || n_envs > 0x7FFFFFFFll) return mobility_fail("n_envs must be in [0, 2^31)");
-    if (n_cues < 0 || n_due_pairs < 0 || n_cues > (1 << 24) || n_due_pairs > (1 << 24)) return mobility_fail("n_cues and n_due_pairs must be in [0, 2^24]");
-    if (first_env + (uint64_t)n_envs > (1ull << 32)) return mobility_fail("first_env + n_envs must not exceed 2^32 (the env counter word)");
-    if (!(memory >= 0.0f && memory < 1.0f)) return mobility_fail("memory must be in [0, 1)");
+    if (n_envs < 0 || n_envs > 0x7FFFFFFFll) return fail("n_envs must be in [0, 2^31)");
+    if (n_cues < 0 || n_due_pairs < 0 || n_cues > (1 << 24) || n_due_pairs > (1 << 24)) return fail("n_cues and n_due_pairs must be in [0, 2^24]");
+    if (first_env + (uint64_t)n_envs > (1ull << 32)) return fail("first_env + n_envs must not exceed 2^32 (the env counter word)");
+    if (!(memory >= 0.0f && memory < 1.0f)) return fail("memory must be in [0, 1)");
     if (!(noise_scale >= 0.0f) || !(speed_std >= 0.0f) || !std::isfinite(noise_scale) || !std::isfinite(speed_std) || !std::isfinite(dt_s))
-        return mobility_fail("noise_scale and speed_std must be finite and >= 0, dt_s finite");
-    if (!(cell_radius_m > 0.0f) || !std::isfinite(cell_radius_m)) return mobility_fail("cell_radius_m must be finite and > 0");
+        return fail("noise_scale and speed_std must be finite and >= 0, dt_s finite");
+    if (!(cell_radius_m > 0.0f) || !std::isfinite(cell_radius_m)) return fail("cell_radius_m must be finite and > 0");
     const float grid = std::nextafterf(cell_radius_m, HUGE_VALF) - cell_radius_m;             // ulp(cell_radius_m)
-    if (!(d2d_radius_m > grid) || !std::isfinite(d2d_radius_m)) return mobility_fail("d2d_radius_m must be finite and > ulp(cell_radius_m)");
-    if (!pos_x || !pos_y || !vel_x || !vel_y) return mobility_fail("null device pointer");
-    if (reset_env && (!elapsed_env || !start_env || !episode_env)) return mobility_fail("the per-env clock needs elapsed_env, start_env and episode_env");
+    if (!(d2d_radius_m > grid) || !std::isfinite(d2d_radius_m)) return fail("d2d_radius_m must be finite and > ulp(cell_radius_m)");
+    if (!pos_x || !pos_y || !vel_x || !vel_y) return fail("null device pointer");
+    if (reset_env && (!elapsed_env || !start_env || !episode_env)) return fail("the per-env clock needs elapsed_env, start_env and episode_env");
     if (n_envs == 0) return 0;
     MoveArgs a;
     a.pos_x = pos_x; a.pos_y = pos_y; a.vel_x = vel_x; a.vel_y = vel_y; a.fixed = fixed_mask;
@@ -142,7 +136,7 @@ extern "C" int d2d_mobility_move(float* pos_x, float* pos_y, float* vel_x, float
     a.units = 1u + (unsigned)n_cues + (unsigned)n_due_pairs;
     a.units_magic = a.units == 1u ? 0xFFFFFFFFu : (unsigned)(0x100000000ull / a.units);       // one short at most: the kernel corrects
     const unsigned long long total = (unsigned long long)n_envs * a.units;
-    if (total >= 0xFFFFFF00ull) return mobility_fail("n_envs * (1 + n_cues + n_due_pairs) must stay below 2^32 - 256");
+    if (total >= 0xFFFFFF00ull) return fail("n_envs * (1 + n_cues + n_due_pairs) must stay below 2^32 - 256");
     a.total = (unsigned)total;
     a.first_env = (unsigned)first_env;
     a.seed_lo = (unsigned)(seed & 0xFFFFFFFFull); a.seed_hi = (unsigned)(seed >> 32);
@@ -151,12 +145,8 @@ extern "C" int d2d_mobility_move(float* pos_x, float* pos_y, float* vel_x, float
     a.cell_r = cell_radius_m; a.d2d_r = d2d_radius_m; a.d2d_in = d2d_radius_m - grid;
     hipLaunchKernelGGL(mobility_move_kernel, dim3((a.total + 255u) / 256u), dim3(256), 0, static_cast<hipStream_t>(hip_stream), a);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return mobility_fail(std::string("mobility_move_kernel launch: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(std::string("mobility_move_kernel launch: ") + hipGetErrorString(e));
     return 0;
-} catch (const std::exception& ex) {
-    return mobility_fail(ex.what());
-} catch (...) {
-    return mobility_fail("unknown exception");
-}
+} D2D_ADDON_CATCH
 
-extern "C" const char* d2d_mobility_last_error(void) { return g_mobility_error.c_str(); }
+D2D_ADDON_LAST_ERROR(d2d_mobility_last_error)

@@ -10,17 +10,11 @@
 #include <mutex>
 #include <string>
 
+#include "d2d_addon.h"
 #include "d2d_plugin.h"
 #include "d2d_step_device.h"
 
 namespace {
-
-thread_local std::string g_plugin_error;
-
-int plugin_fail(const std::string& msg) {
-    try { g_plugin_error = msg; } catch (...) { }
-    return 1;
-}
 
 struct NormalArgs {
     unsigned long long total;     // n_envs * n_rows * n_cols
@@ -89,20 +83,20 @@ int device_cus(int dev) {
 
 extern "C" int d2d_plugin_normal(void* out_dev, int32_t dtype, int64_t n_envs, uint64_t first_env, int32_t n_rows, int32_t n_cols,
                                  uint64_t step, int32_t kind, uint64_t seed, void* hip_stream) try {
-    if (!out_dev) return plugin_fail("null out_dev");
-    if (dtype != D2D_PLUGIN_F32 && dtype != D2D_PLUGIN_F64) return plugin_fail("dtype must be D2D_PLUGIN_F32 or D2D_PLUGIN_F64");
-    if (kind != 0 && kind != 1) return plugin_fail("kind must be 0 or 1");
-    if (n_envs < 0 || n_rows < 1 || n_cols < 1 || n_rows > 65536 || n_cols > 65536) return plugin_fail("n_envs >= 0, 1 <= n_rows, n_cols <= 65536");
-    if (kind == 1 && n_rows != 1) return plugin_fail("kind 1 (own-link draws) takes n_rows == 1");
-    if (first_env + (uint64_t)n_envs > (1ull << 32)) return plugin_fail("first_env + n_envs must not exceed 2^32 (the env counter word)");
+    if (!out_dev) return fail("null out_dev");
+    if (dtype != D2D_PLUGIN_F32 && dtype != D2D_PLUGIN_F64) return fail("dtype must be D2D_PLUGIN_F32 or D2D_PLUGIN_F64");
+    if (kind != 0 && kind != 1) return fail("kind must be 0 or 1");
+    if (n_envs < 0 || n_rows < 1 || n_cols < 1 || n_rows > 65536 || n_cols > 65536) return fail("n_envs >= 0, 1 <= n_rows, n_cols <= 65536");
+    if (kind == 1 && n_rows != 1) return fail("kind 1 (own-link draws) takes n_rows == 1");
+    if (first_env + (uint64_t)n_envs > (1ull << 32)) return fail("first_env + n_envs must not exceed 2^32 (the env counter word)");
     if (n_envs == 0) return 0;
-    if (reinterpret_cast<uintptr_t>(out_dev) % 16 != 0) return plugin_fail("out_dev must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(out_dev) % 16 != 0) return fail("out_dev must be 16-byte aligned");
     int dev = 0;
     hipPointerAttribute_t attr;
     hipError_t e = hipPointerGetAttributes(&attr, out_dev);
     if (e != hipSuccess) (void)hipGetLastError();
-    if (e != hipSuccess || (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged)) return plugin_fail("out_dev must be device or managed memory");
-    if (hipGetDevice(&dev) != hipSuccess || dev != attr.device) return plugin_fail("out_dev must live on the current HIP device");
+    if (e != hipSuccess || (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged)) return fail("out_dev must be device or managed memory");
+    if (hipGetDevice(&dev) != hipSuccess || dev != attr.device) return fail("out_dev must live on the current HIP device");
     NormalArgs a;
     a.total = (unsigned long long)n_envs * (unsigned long long)n_rows * (unsigned long long)n_cols;
     a.n_rows = (unsigned)n_rows; a.n_cols = (unsigned)n_cols;
@@ -118,12 +112,8 @@ extern "C" int d2d_plugin_normal(void* out_dev, int32_t dtype, int64_t n_envs, u
     if (dtype == D2D_PLUGIN_F64) hipLaunchKernelGGL(normal_kernel<double>, dim3((unsigned)blocks), dim3(256), 0, s, static_cast<double*>(out_dev), a);
     else hipLaunchKernelGGL(normal_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s, static_cast<float*>(out_dev), a);
     e = hipGetLastError();
-    if (e != hipSuccess) return plugin_fail(std::string("normal_kernel launch: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(std::string("normal_kernel launch: ") + hipGetErrorString(e));
     return 0;
-} catch (const std::exception& ex) {
-    return plugin_fail(ex.what());
-} catch (...) {
-    return plugin_fail("unknown exception");
-}
+} D2D_ADDON_CATCH
 
-extern "C" const char* d2d_plugin_last_error(void) { return g_plugin_error.c_str(); }
+D2D_ADDON_LAST_ERROR(d2d_plugin_last_error)

@@ -2,8 +2,8 @@
 // of every env in one launch.  gfx950.
 //
 // Shape: ONE workgroup of 256 threads per env - the iteration couples exactly the links of one env - that stages the env once and
-// then sweeps in LDS.  Staging is the sensing / best-response kernels' (d2d_sense.hip, d2d_bestrb.hip), restated here so that their
-// ISA stays what it is: the rank sort of the packed keys rb * 2048 + j (four keys per ds_read_b128 at a wave-uniform address:
+// then sweeps in LDS.  Staging is the sensing / best-response kernels' (d2d_sense.hip, d2d_bestrb.hip), whose sort all
+// of them take from d2d_same_rb.h: the rank sort of the packed keys rb * 2048 + j (four keys per ds_read_b128 at a wave-uniform address:
 // stable, free of atomics, the same order on every call) puts every link's constants into its sorted slot - transmitter tuple (tx x,
 // tx y, the folded tx column, link index), the power-law head / tail, receiver tuple (rx x, rx y, rx side of the path-loss constant,
 // noise), (own-pair gain, rx gain), target, bounds, start power - and start[r] = the first slot of RB r, folded per slot into the
@@ -23,26 +23,20 @@
 
 #include <string>
 
+#include "d2d_addon.h"
 #include "d2d_powerctl.h"
+#include "d2d_same_rb.h"
 #include "d2d_step_device.h"
 
 namespace {
 
 using namespace d2d;
 
-thread_local std::string g_powerctl_error;
-
-int powerctl_fail(const std::string& msg) {
-    try { g_powerctl_error = msg; } catch (...) { }
-    return 1;
-}
-
 constexpr int PC_THREADS = 256;
 constexpr int PC_WAVES = PC_THREADS / 64;
-constexpr unsigned KEY_SHIFT = 11;                               // key = rb << 11 | j, j < 2048
 constexpr unsigned NO_RB = 0x80000000u;                          // range word of a link on no RB
-static_assert((1 << KEY_SHIFT) == D2D_POWERCTL_MAX_LINKS, "the key packs the link index into KEY_SHIFT bits");
-static_assert((unsigned long long)(D2D_POWERCTL_MAX_RBS + 1) << KEY_SHIFT < 0xFFFFFFFFull, "keys are 32 bits, all ones is the padding");
+static_assert(D2D_POWERCTL_MAX_LINKS == SAME_RB_MAX_LINKS && D2D_POWERCTL_MAX_RBS == SAME_RB_MAX_RBS, "the limits of the shared sort (d2d_same_rb.h)");
+static_assert(D2D_POWERCTL_LAW_INV_SQUARE == LAW_INV_SQUARE && D2D_POWERCTL_LAW_POWER == LAW_POWER && D2D_POWERCTL_LAW_POW_K == LAW_POW_K, "the laws check_law() knows (d2d_addon.h)");
 static_assert(D2D_POWERCTL_MAX_LINKS < (1 << 15), "a range word packs two slot indices into 16 bits each under the NO_RB bit");
 
 struct PowerArgs {
@@ -72,7 +66,6 @@ struct PowerArgs {
 // dynamic LDS, by sorted slot: tx float4[N] | rxa float4[N] | rxb float2[N] | lohi int2[N] | hh float2[N] (power laws) | target f32[n4]
 // | p i32[n4] | range u32[n4] (the sorted rb until start[] exists) | z0 f32[n4] | z1 f32[n4] (the sort's keys until the first sweep) |
 // start i32[R + 1] | flag i32[2][4]
-__host__ __device__ inline unsigned round16(unsigned x) { return (x + 15u) & ~15u; }
 
 struct Lds {
     float4* tx; float4* rxa; float2* rxb; int2* lohi; float2* hh; float* tgt; int* p; unsigned* range; float* z0; float* z1; int* start; int* flag;
@@ -133,14 +126,7 @@ __global__ __launch_bounds__(PC_THREADS) void powerctl_kernel(const PowerArgs a)
     const float* py = a.pos_y + b * (size_t)D;
 
     // ---- keys: (rb, link index); a link whose rb is outside [0, R) takes the pseudo RB R behind every real one
-    for (int j = tid; j < n4; j += PC_THREADS) {
-        unsigned k = 0xFFFFFFFFu;
-        if (j < N) {
-            const int r = rb_row[j];
-            k = ((unsigned)((unsigned)r < (unsigned)R ? r : R) << KEY_SHIFT) | (unsigned)j;
-        }
-        key[j] = k;
-    }
+    same_rb_keys<PC_THREADS>(key, rb_row, N, n4, R);
     __syncthreads();
     // ---- rank sort: link j goes to slot #{keys below its own}; the keys are distinct, so the slots are a permutation
     for (int j = tid; j < N; j += PC_THREADS) {
@@ -158,12 +144,7 @@ __global__ __launch_bounds__(PC_THREADS) void powerctl_kernel(const PowerArgs a)
         const int held = pwr_row[j];
         const int lo = adj ? a.p_min[j] : held, hi = adj ? a.p_max[j] : held;
         const float tgt = a.target[j];
-        int slot = 0;
-        const uint4* k4 = reinterpret_cast<const uint4*>(key);
-        for (int q = 0; q < (n4 >> 2); ++q) {
-            const uint4 k = k4[q];
-            slot += (k.x < mine) + (k.y < mine) + (k.z < mine) + (k.w < mine);
-        }
+        const int slot = same_rb_rank(key, n4, mine);
         s.tx[slot] = make_float4(tx_x, tx_y, c0, __int_as_float(j));
         s.rxa[slot] = make_float4(rx_x, rx_y, rx_pl, noise);
         s.rxb[slot] = make_float2(g_own, rx_lin);
@@ -176,11 +157,7 @@ __global__ __launch_bounds__(PC_THREADS) void powerctl_kernel(const PowerArgs a)
     }
     __syncthreads();
     // ---- start[r]: the first sorted entry whose RB is >= r, r in [0, R]; entries from start[R] on are on no RB
-    for (int k = tid; k <= N; k += PC_THREADS) {
-        const int prev = k == 0 ? -1 : (int)s.range[k - 1];
-        const int cur = k == N ? R : (int)s.range[k];
-        for (int r = prev + 1; r <= cur; ++r) s.start[r] = k;
-    }
+    same_rb_starts<PC_THREADS>(s.start, s.range, N, R);
     __syncthreads();
     // ---- every slot's own RB group as (first | last + 1 << 16); from here on a slot is touched by its owner lane only, z aside
     for (int k = tid; k < N; k += PC_THREADS) {
@@ -242,17 +219,6 @@ __global__ __launch_bounds__(PC_THREADS) void powerctl_kernel(const PowerArgs a)
     }
 }
 
-template <int MODE>
-hipError_t launch(const PowerArgs& a, dim3 grid, unsigned lds, hipStream_t s) {
-    if (lds > 64u * 1024u) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&powerctl_kernel<MODE>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((powerctl_kernel<MODE>), grid, dim3(PC_THREADS), lds, s, a);
-    return hipGetLastError();
-}
-
 }  // namespace
 
 extern "C" int d2d_power_control(const float* pos_x, const float* pos_y, const int32_t* rb, const int32_t* pwr_dbm, const int32_t* link_tx,
@@ -260,21 +226,16 @@ extern "C" int d2d_power_control(const float* pos_x, const float* pos_y, const i
                                  int32_t n_links, int32_t n_rbs, const float* target_db, const int32_t* p_min, const int32_t* p_max,
                                  const uint8_t* adjustable, int32_t max_iters, const uint8_t* env_mask, int32_t* power_dbm,
                                  float* sinr_db, int32_t* iters, uint8_t* converged, void* hip_stream) try {
-    if (n_envs < 0 || n_envs > 0x7FFFFFFFll) return powerctl_fail("n_envs must be in [0, 2^31)");
-    if (n_links < 1 || n_links > D2D_POWERCTL_MAX_LINKS)
-        return powerctl_fail("n_links must be in [1, " + std::to_string(D2D_POWERCTL_MAX_LINKS) + "]");
-    if (n_rbs < 1 || n_rbs > D2D_POWERCTL_MAX_RBS) return powerctl_fail("n_rbs must be in [1, " + std::to_string(D2D_POWERCTL_MAX_RBS) + "]");
-    if (n_dev < 1) return powerctl_fail("n_dev must be >= 1");
-    if (max_iters < 1) return powerctl_fail("max_iters must be >= 1");
-    if (law != D2D_POWERCTL_LAW_INV_SQUARE && law != D2D_POWERCTL_LAW_POWER && law != D2D_POWERCTL_LAW_POW_K) return powerctl_fail("unknown law");
-    if (law == D2D_POWERCTL_LAW_POW_K && (pow_k < 1 || pow_k > 8)) return powerctl_fail("pow_k must be in [1, 8]");
+    if (const char* why = check_sizes(n_envs, n_links, D2D_POWERCTL_MAX_LINKS, n_rbs, D2D_POWERCTL_MAX_RBS, n_dev)) return fail(why);
+    if (max_iters < 1) return fail("max_iters must be >= 1");
+    if (const char* why = check_law(law, pow_k)) return fail(why);
     if (!pos_x || !pos_y || !rb || !pwr_dbm || !link_tx || !link_rx || !dev_cols || !target_db || !p_min || !p_max || !power_dbm ||
         !sinr_db || !iters || !converged)
-        return powerctl_fail("null device pointer");
+        return fail("null device pointer");
     const void* outs[4] = {power_dbm, sinr_db, iters, converged};
     for (int x = 0; x < 4; ++x)
         for (int y = x + 1; y < 4; ++y)
-            if (outs[x] == outs[y]) return powerctl_fail("power_dbm, sinr_db, iters and converged must be four arrays");
+            if (outs[x] == outs[y]) return fail("power_dbm, sinr_db, iters and converged must be four arrays");
     PowerArgs a;
     a.pos_x = pos_x; a.pos_y = pos_y; a.rb = rb; a.pwr = pwr_dbm; a.link_tx = link_tx; a.link_rx = link_rx; a.cols = dev_cols;
     a.target = target_db; a.p_min = p_min; a.p_max = p_max; a.adjustable = adjustable; a.env_mask = env_mask;
@@ -293,20 +254,16 @@ extern "C" int d2d_power_control(const float* pos_x, const float* pos_y, const i
     a.off_start = a.off_z1 + n4 * 4u;
     a.off_flag = a.off_start + round16(((unsigned)n_rbs + 1u) * 4u);
     const unsigned lds = a.off_flag + 2u * PC_WAVES * 4u;
-    if (lds > 160u * 1024u) return powerctl_fail("n_links and n_rbs need more than the 160 KiB of LDS a workgroup can have");
+    if (lds > 160u * 1024u) return fail("n_links and n_rbs need more than the 160 KiB of LDS a workgroup can have");
     if (n_envs == 0) return 0;
     const dim3 grid((unsigned)n_envs);
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     hipError_t e;
-    if (law == D2D_POWERCTL_LAW_INV_SQUARE) e = launch<PL_INV_SQUARE>(a, grid, lds, st);
-    else if (law == D2D_POWERCTL_LAW_POWER) e = launch<PL_POWER>(a, grid, lds, st);
-    else e = launch<PL_POWK>(a, grid, lds, st);
-    if (e != hipSuccess) return powerctl_fail(std::string("powerctl_kernel launch: ") + hipGetErrorString(e));
+    if (law == D2D_POWERCTL_LAW_INV_SQUARE) e = launch(&powerctl_kernel<PL_INV_SQUARE>, grid, dim3(PC_THREADS), lds, st, a);
+    else if (law == D2D_POWERCTL_LAW_POWER) e = launch(&powerctl_kernel<PL_POWER>, grid, dim3(PC_THREADS), lds, st, a);
+    else e = launch(&powerctl_kernel<PL_POWK>, grid, dim3(PC_THREADS), lds, st, a);
+    if (e != hipSuccess) return fail(std::string("powerctl_kernel launch: ") + hipGetErrorString(e));
     return 0;
-} catch (const std::exception& ex) {
-    return powerctl_fail(ex.what());
-} catch (...) {
-    return powerctl_fail("unknown exception");
-}
+} D2D_ADDON_CATCH
 
-extern "C" const char* d2d_powerctl_last_error(void) { return g_powerctl_error.c_str(); }
+D2D_ADDON_LAST_ERROR(d2d_powerctl_last_error)

@@ -12,17 +12,11 @@
 #include <cmath>
 #include <string>
 
+#include "d2d_addon.h"
 #include "d2d_queue.h"
 #include "d2d_step_device.h"
 
 namespace {
-
-thread_local std::string g_queue_error;
-
-int queue_fail(const std::string& msg) {
-    try { g_queue_error = msg; } catch (...) { }
-    return 1;
-}
 
 constexpr int kTable = D2D_QUEUE_TABLE;
 
@@ -158,24 +152,24 @@ extern "C" int d2d_queue_step(const float* capacity_mbps, int32_t* ring, int32_t
                               double bits_per_mbps_step, uint32_t p_on_to_off, uint32_t p_off_to_on, uint32_t p_start_on,
                               uint64_t first_env, uint64_t seed, uint32_t step, uint32_t episode, const int32_t* elapsed_env,
                               int32_t* start_env, const uint32_t* episode_env, const int32_t* reset_env, void* hip_stream) try {
-    if (n_envs < 0 || n_envs > 0x7FFFFFFFll) return queue_fail("n_envs must be in [0, 2^31)");
-    if (n_cues < 0 || n_due_pairs < 0 || n_cues > (1 << 24) || n_due_pairs > (1 << 24)) return queue_fail("n_cues and n_due_pairs must be in [0, 2^24]");
-    if (first_env + (uint64_t)n_envs > (1ull << 32)) return queue_fail("first_env + n_envs must not exceed 2^32 (the env counter word)");
-    if (deadline_steps < 1 || deadline_steps > D2D_QUEUE_MAX_DEADLINE) return queue_fail("deadline_steps must be in [1, 32]");
-    if (packet_bits < 1 || packet_bits * kTable >= (1ll << 31)) return queue_fail("packet_bits must be >= 1 and 64 * packet_bits below 2^31");
-    if (buffer_bits < 0 || buffer_bits >= (1ll << 31)) return queue_fail("buffer_bits must be in [0, 2^31)");
-    if (!(bits_per_mbps_step > 0.0) || !std::isfinite(bits_per_mbps_step)) return queue_fail("bits_per_mbps_step must be finite and > 0");
-    if (!thresholds) return queue_fail("thresholds must be a host array of 2 x 64 words");
+    if (n_envs < 0 || n_envs > 0x7FFFFFFFll) return fail("n_envs must be in [0, 2^31)");
+    if (n_cues < 0 || n_due_pairs < 0 || n_cues > (1 << 24) || n_due_pairs > (1 << 24)) return fail("n_cues and n_due_pairs must be in [0, 2^24]");
+    if (first_env + (uint64_t)n_envs > (1ull << 32)) return fail("first_env + n_envs must not exceed 2^32 (the env counter word)");
+    if (deadline_steps < 1 || deadline_steps > D2D_QUEUE_MAX_DEADLINE) return fail("deadline_steps must be in [1, 32]");
+    if (packet_bits < 1 || packet_bits * kTable >= (1ll << 31)) return fail("packet_bits must be >= 1 and 64 * packet_bits below 2^31");
+    if (buffer_bits < 0 || buffer_bits >= (1ll << 31)) return fail("buffer_bits must be in [0, 2^31)");
+    if (!(bits_per_mbps_step > 0.0) || !std::isfinite(bits_per_mbps_step)) return fail("bits_per_mbps_step must be finite and > 0");
+    if (!thresholds) return fail("thresholds must be a host array of 2 x 64 words");
     for (int c = 0; c < 2; ++c)
         for (int k = 1; k < kTable; ++k)
-            if (thresholds[c * kTable + k] < thresholds[c * kTable + k - 1]) return queue_fail("thresholds: a table must not decrease");
+            if (thresholds[c * kTable + k] < thresholds[c * kTable + k - 1]) return fail("thresholds: a table must not decrease");
     if (!capacity_mbps || !ring || !arrived_bits || !served_bits || !expired_bits || !overflow_bits || !backlog_bits || !hol_age_steps ||
         !mean_delay_steps || !on)
-        return queue_fail("null device pointer");
-    if (reset_env && (!elapsed_env || !start_env || !episode_env)) return queue_fail("the per-env clock needs elapsed_env, start_env and episode_env");
+        return fail("null device pointer");
+    if (reset_env && (!elapsed_env || !start_env || !episode_env)) return fail("the per-env clock needs elapsed_env, start_env and episode_env");
     const unsigned links = (unsigned)n_cues + (unsigned)n_due_pairs;
     const unsigned long long total = (unsigned long long)n_envs * links;
-    if (total >= 0xFFFFFF00ull) return queue_fail("n_envs * (n_cues + n_due_pairs) must stay below 2^32 - 256");
+    if (total >= 0xFFFFFF00ull) return fail("n_envs * (n_cues + n_due_pairs) must stay below 2^32 - 256");
     if (total == 0) return 0;
     QueueArgs a;
     a.capacity = capacity_mbps; a.ring = ring; a.arrived = arrived_bits; a.served = served_bits; a.expired = expired_bits;
@@ -194,12 +188,8 @@ extern "C" int d2d_queue_step(const float* capacity_mbps, int32_t* ring, int32_t
     for (int k = 0; k < 2 * kTable; ++k) a.table[k] = thresholds[k];
     hipLaunchKernelGGL(queue_step_kernel, dim3((a.total + 255u) / 256u), dim3(256), 0, static_cast<hipStream_t>(hip_stream), a);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return queue_fail(std::string("queue_step_kernel launch: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(std::string("queue_step_kernel launch: ") + hipGetErrorString(e));
     return 0;
-} catch (const std::exception& ex) {
-    return queue_fail(ex.what());
-} catch (...) {
-    return queue_fail("unknown exception");
-}
+} D2D_ADDON_CATCH
 
-extern "C" const char* d2d_queue_last_error(void) { return g_queue_error.c_str(); }
+D2D_ADDON_LAST_ERROR(d2d_queue_last_error)

@@ -15,7 +15,9 @@
 
 #include <string>
 
+#include "d2d_addon.h"
 #include "d2d_sense.h"
+#include "d2d_same_rb.h"
 #include "d2d_step_device.h"
 #include "d2d_store.h"
 
@@ -23,21 +25,13 @@ namespace {
 
 using namespace d2d;
 
-thread_local std::string g_sense_error;
-
-int sense_fail(const std::string& msg) {
-    try { g_sense_error = msg; } catch (...) { }
-    return 1;
-}
-
 constexpr int SENSE_THREADS = 256;
 constexpr int SENSE_WAVES = SENSE_THREADS / 64;
 constexpr int TILE_RBS = 32;
 constexpr int TILE_PITCH = 65;                                   // floats per RB row of a wave's tile: 64 receivers + 1
 constexpr unsigned TILE_BYTES = TILE_RBS * TILE_PITCH * 4u;      // per wave
-constexpr unsigned KEY_SHIFT = 11;                               // key = rb << 11 | j, j < 2048
-static_assert((1 << KEY_SHIFT) == D2D_SENSE_MAX_LINKS, "the key packs the link index into KEY_SHIFT bits");
-static_assert((unsigned long long)(D2D_SENSE_MAX_RBS + 1) << KEY_SHIFT < 0xFFFFFFFFull, "keys are 32 bits, all ones is the padding");
+static_assert(D2D_SENSE_MAX_LINKS == SAME_RB_MAX_LINKS && D2D_SENSE_MAX_RBS == SAME_RB_MAX_RBS, "the limits of the shared sort (d2d_same_rb.h)");
+static_assert(D2D_SENSE_LAW_INV_SQUARE == LAW_INV_SQUARE && D2D_SENSE_LAW_POWER == LAW_POWER && D2D_SENSE_LAW_POW_K == LAW_POW_K, "the laws check_law() knows (d2d_addon.h)");
 
 struct SenseArgs {
     const float* pos_x;
@@ -56,7 +50,6 @@ struct SenseArgs {
 
 // dynamic LDS: tuples float4[N] | hh float2[N] (power laws) | start int[R + 1] | tiles float[4][32 * 65], whose bytes first hold the
 // sort's keys u32[N rounded up to 4] and the sorted rb values int[N]
-__host__ __device__ inline unsigned round16(unsigned x) { return (x + 15u) & ~15u; }
 
 template <int MODE, int WHAT>
 __global__ __launch_bounds__(SENSE_THREADS) void sense_kernel(const SenseArgs a) {
@@ -77,14 +70,7 @@ __global__ __launch_bounds__(SENSE_THREADS) void sense_kernel(const SenseArgs a)
     const float* py = a.pos_y + b * (size_t)D;
 
     // ---- keys: (rb, link index); a link whose rb is outside [0, R) takes the pseudo RB R behind every real one
-    for (int j = tid; j < n4; j += SENSE_THREADS) {
-        unsigned k = 0xFFFFFFFFu;
-        if (j < N) {
-            const int r = rb_row[j];
-            k = ((unsigned)((unsigned)r < (unsigned)R ? r : R) << KEY_SHIFT) | (unsigned)j;
-        }
-        key[j] = k;
-    }
+    same_rb_keys<SENSE_THREADS>(key, rb_row, N, n4, R);
     __syncthreads();
     // ---- rank sort: link j goes to slot #{keys below its own}; the keys are distinct, so the slots are a permutation
     for (int j = tid; j < N; j += SENSE_THREADS) {
@@ -94,23 +80,14 @@ __global__ __launch_bounds__(SENSE_THREADS) void sense_kernel(const SenseArgs a)
         float2 h = make_float2(-1.0f, 0.0f);
         if (POWLAW) h = make_float2(a.cols[4 * D + txd], a.cols[5 * D + txd]);
         const unsigned mine = key[j];
-        int slot = 0;
-        const uint4* k4 = reinterpret_cast<const uint4*>(key);
-        for (int q = 0; q < (n4 >> 2); ++q) {
-            const uint4 k = k4[q];
-            slot += (k.x < mine) + (k.y < mine) + (k.z < mine) + (k.w < mine);
-        }
+        const int slot = same_rb_rank(key, n4, mine);
         txl[slot] = make_float4(x, y, pw, __int_as_float(j));
         if (POWLAW) hh[slot] = h;
         srb[slot] = (int)(mine >> KEY_SHIFT);
     }
     __syncthreads();
     // ---- start[r]: the first sorted entry whose RB is >= r, r in [0, R]; entries from start[R] on are on no RB
-    for (int k = tid; k <= N; k += SENSE_THREADS) {
-        const int prev = k == 0 ? -1 : srb[k - 1];
-        const int cur = k == N ? R : srb[k];
-        for (int r = prev + 1; r <= cur; ++r) start[r] = k;
-    }
+    same_rb_starts<SENSE_THREADS>(start, srb, N, R);
     __syncthreads();                 // the last use of key / srb: their bytes are the tiles from here on
 
     // ---- lanes own receivers
@@ -180,30 +157,15 @@ __global__ __launch_bounds__(SENSE_THREADS) void sense_kernel(const SenseArgs a)
     }
 }
 
-template <int MODE, int WHAT>
-hipError_t launch(const SenseArgs& a, dim3 grid, unsigned lds, hipStream_t s) {
-    if (lds > 64u * 1024u) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&sense_kernel<MODE, WHAT>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((sense_kernel<MODE, WHAT>), grid, dim3(SENSE_THREADS), lds, s, a);
-    return hipGetLastError();
-}
-
 }  // namespace
 
 extern "C" int d2d_sense_rb(const float* pos_x, const float* pos_y, const int32_t* rb, const int32_t* pwr_dbm, const int32_t* link_tx,
                             const int32_t* link_rx, const float* dev_cols, int32_t law, int32_t pow_k, int64_t n_envs, int32_t n_dev,
                             int32_t n_links, int32_t n_rbs, int32_t what, float* out, void* hip_stream) try {
-    if (n_envs < 0 || n_envs > 0x7FFFFFFFll) return sense_fail("n_envs must be in [0, 2^31)");
-    if (n_links < 1 || n_links > D2D_SENSE_MAX_LINKS) return sense_fail("n_links must be in [1, " + std::to_string(D2D_SENSE_MAX_LINKS) + "]");
-    if (n_rbs < 1 || n_rbs > D2D_SENSE_MAX_RBS) return sense_fail("n_rbs must be in [1, " + std::to_string(D2D_SENSE_MAX_RBS) + "]");
-    if (n_dev < 1) return sense_fail("n_dev must be >= 1");
-    if (what != D2D_SENSE_SINR_DB && what != D2D_SENSE_INTERFERENCE_MW) return sense_fail("what must be D2D_SENSE_SINR_DB or D2D_SENSE_INTERFERENCE_MW");
-    if (law != D2D_SENSE_LAW_INV_SQUARE && law != D2D_SENSE_LAW_POWER && law != D2D_SENSE_LAW_POW_K) return sense_fail("unknown law");
-    if (law == D2D_SENSE_LAW_POW_K && (pow_k < 1 || pow_k > 8)) return sense_fail("pow_k must be in [1, 8]");
-    if (!pos_x || !pos_y || !rb || !pwr_dbm || !link_tx || !link_rx || !dev_cols || !out) return sense_fail("null device pointer");
+    if (const char* why = check_sizes(n_envs, n_links, D2D_SENSE_MAX_LINKS, n_rbs, D2D_SENSE_MAX_RBS, n_dev)) return fail(why);
+    if (what != D2D_SENSE_SINR_DB && what != D2D_SENSE_INTERFERENCE_MW) return fail("what must be D2D_SENSE_SINR_DB or D2D_SENSE_INTERFERENCE_MW");
+    if (const char* why = check_law(law, pow_k)) return fail(why);
+    if (!pos_x || !pos_y || !rb || !pwr_dbm || !link_tx || !link_rx || !dev_cols || !out) return fail("null device pointer");
     if (n_envs == 0) return 0;
     SenseArgs a;
     a.pos_x = pos_x; a.pos_y = pos_y; a.rb = rb; a.pwr = pwr_dbm; a.link_tx = link_tx; a.link_rx = link_rx; a.cols = dev_cols; a.out = out;
@@ -215,23 +177,17 @@ extern "C" int d2d_sense_rb(const float* pos_x, const float* pos_y, const int32_
     a.off_tile = a.off_start + round16(((unsigned)n_rbs + 1u) * 4u);
     const unsigned sort_bytes = n4 * 4u + N * 4u, tile_bytes = SENSE_WAVES * TILE_BYTES;
     const unsigned lds = a.off_tile + (sort_bytes > tile_bytes ? sort_bytes : tile_bytes);
-    if (lds > 160u * 1024u) return sense_fail("n_links and n_rbs need more than the 160 KiB of LDS a workgroup can have");
+    if (lds > 160u * 1024u) return fail("n_links and n_rbs need more than the 160 KiB of LDS a workgroup can have");
     const dim3 grid((unsigned)n_envs, (N + SENSE_THREADS - 1) / SENSE_THREADS);
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    hipError_t e;
     const bool sinr = what == D2D_SENSE_SINR_DB;
-    if (law == D2D_SENSE_LAW_INV_SQUARE)
-        e = sinr ? launch<PL_INV_SQUARE, D2D_SENSE_SINR_DB>(a, grid, lds, s) : launch<PL_INV_SQUARE, D2D_SENSE_INTERFERENCE_MW>(a, grid, lds, s);
-    else if (law == D2D_SENSE_LAW_POWER)
-        e = sinr ? launch<PL_POWER, D2D_SENSE_SINR_DB>(a, grid, lds, s) : launch<PL_POWER, D2D_SENSE_INTERFERENCE_MW>(a, grid, lds, s);
-    else
-        e = sinr ? launch<PL_POWK, D2D_SENSE_SINR_DB>(a, grid, lds, s) : launch<PL_POWK, D2D_SENSE_INTERFERENCE_MW>(a, grid, lds, s);
-    if (e != hipSuccess) return sense_fail(std::string("sense_kernel launch: ") + hipGetErrorString(e));
+    void (*kernel)(SenseArgs);
+    if (law == D2D_SENSE_LAW_INV_SQUARE) kernel = sinr ? &sense_kernel<PL_INV_SQUARE, D2D_SENSE_SINR_DB> : &sense_kernel<PL_INV_SQUARE, D2D_SENSE_INTERFERENCE_MW>;
+    else if (law == D2D_SENSE_LAW_POWER) kernel = sinr ? &sense_kernel<PL_POWER, D2D_SENSE_SINR_DB> : &sense_kernel<PL_POWER, D2D_SENSE_INTERFERENCE_MW>;
+    else kernel = sinr ? &sense_kernel<PL_POWK, D2D_SENSE_SINR_DB> : &sense_kernel<PL_POWK, D2D_SENSE_INTERFERENCE_MW>;
+    const hipError_t e = launch(kernel, grid, dim3(SENSE_THREADS), lds, s, a);
+    if (e != hipSuccess) return fail(std::string("sense_kernel launch: ") + hipGetErrorString(e));
     return 0;
-} catch (const std::exception& ex) {
-    return sense_fail(ex.what());
-} catch (...) {
-    return sense_fail("unknown exception");
-}
+} D2D_ADDON_CATCH
 
-extern "C" const char* d2d_sense_last_error(void) { return g_sense_error.c_str(); }
+D2D_ADDON_LAST_ERROR(d2d_sense_last_error)
