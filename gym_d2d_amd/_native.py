@@ -1,7 +1,5 @@
-"""ctypes binding of libd2d_hip.so (include/d2d_hip.h), libd2d_plugin.so (include/d2d_plugin.h), libd2d_episode.so
-(include/d2d_episode.h), libd2d_sense.so (include/d2d_sense.h), libd2d_graph.so (include/d2d_graph.h), libd2d_marginal.so (include/d2d_marginal.h), libd2d_mobility.so
-(include/d2d_mobility.h), libd2d_channel.so (include/d2d_channel.h), libd2d_queue.so (include/d2d_queue.h) libd2d_bestrb.so
-(include/d2d_bestrb.h), libd2d_powerctl.so (include/d2d_powerctl.h), libd2d_brdyn.so (include/d2d_brdyn.h) and libd2d_evaluate.so (include/d2d_evaluate.h).  There is no CPU fallback: if a library or a gfx950 GPU is missing, the calls below raise."""
+"""ctypes binding of libd2d_hip.so (include/d2d_hip.h) and of the side libraries `SIDE` lists (libd2d_<name>.so, include/d2d_<name>.h).
+There is no CPU fallback: if a library or a gfx950 GPU is missing, the calls below raise."""
 from __future__ import annotations
 
 import ctypes as C
@@ -11,18 +9,6 @@ from typing import Optional
 import numpy as np
 
 LIB_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_hip.so'
-PLUGIN_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_plugin.so'
-EPISODE_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_episode.so'
-SENSE_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_sense.so'
-GRAPH_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_graph.so'
-MARGINAL_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_marginal.so'
-MOBILITY_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_mobility.so'
-CHANNEL_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_channel.so'
-QUEUE_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_queue.so'
-BESTRB_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_bestrb.so'
-POWERCTL_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_powerctl.so'
-BRDYN_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_brdyn.so'
-EVALUATE_PATH = Path(__file__).resolve().parent / 'lib' / 'libd2d_evaluate.so'
 ABI_VERSION = 7
 MAX_LINKS = 2048
 
@@ -242,29 +228,24 @@ EVALUATE_SIGNATURES = {
     'd2d_evaluate_last_error': (C.c_char_p, []),
 }
 
+# the side libraries: name -> every symbol include/d2d_<name>.h declares; libd2d_<name>.so, its error text in d2d_<name>_last_error
+SIDE = {'plugin': PLUGIN_SIGNATURES, 'episode': EPISODE_SIGNATURES, 'sense': SENSE_SIGNATURES, 'graph': GRAPH_SIGNATURES,
+        'marginal': MARGINAL_SIGNATURES, 'mobility': MOBILITY_SIGNATURES, 'channel': CHANNEL_SIGNATURES, 'queue': QUEUE_SIGNATURES,
+        'bestrb': BESTRB_SIGNATURES, 'powerctl': POWERCTL_SIGNATURES, 'brdyn': BRDYN_SIGNATURES, 'evaluate': EVALUATE_SIGNATURES}
+
 _lib: Optional[C.CDLL] = None
-_plugin: Optional[C.CDLL] = None
-_episode: Optional[C.CDLL] = None
-_sense: Optional[C.CDLL] = None
-sense_launches = 0                  # d2d_sense_rb calls made through sense_rb() in this process
-_graph: Optional[C.CDLL] = None
-graph_launches = {'coupling': 0, 'neighbors': 0, 'neighbor_obs': 0}     # launches made through the graph_*() wrappers in this process
-_marginal: Optional[C.CDLL] = None
-marginal_launches = 0               # d2d_marginal_capacity calls made through marginal_capacity() in this process
-_bestrb: Optional[C.CDLL] = None
-bestrb_launches = 0                 # d2d_best_rb calls made through best_rb() in this process
-_powerctl: Optional[C.CDLL] = None
-powerctl_launches = 0               # d2d_power_control calls made through power_control() in this process
-_brdyn: Optional[C.CDLL] = None
-brdyn_launches = 0                  # d2d_best_response_dynamics launches made through best_response_dynamics() in this process
-_evaluate: Optional[C.CDLL] = None
-evaluate_launches = 0               # d2d_evaluate launches made through evaluate() in this process
-_mobility: Optional[C.CDLL] = None
-mobility_launches = 0               # d2d_mobility_move calls made through mobility_move() in this process
-_channel: Optional[C.CDLL] = None
-channel_launches = 0                # d2d_channel_fill calls made through channel_fill() in this process
-_queue: Optional[C.CDLL] = None
-queue_launches = 0                  # d2d_queue_step calls made through queue_step() in this process
+_side: dict = {}                    # name -> the opened, typed side library
+# launches made through the wrappers below in this process
+sense_launches = 0                  # d2d_sense_rb calls made through sense_rb()
+graph_launches = {'coupling': 0, 'neighbors': 0, 'neighbor_obs': 0}     # launches made through the graph_*() wrappers
+marginal_launches = 0               # d2d_marginal_capacity calls made through marginal_capacity()
+bestrb_launches = 0                 # d2d_best_rb calls made through best_rb()
+powerctl_launches = 0               # d2d_power_control launches made through power_control()
+brdyn_launches = 0                  # d2d_best_response_dynamics launches made through best_response_dynamics()
+evaluate_launches = 0               # d2d_evaluate launches made through evaluate()
+mobility_launches = 0               # d2d_mobility_move calls made through mobility_move()
+channel_launches = 0                # d2d_channel_fill calls made through channel_fill()
+queue_launches = 0                  # d2d_queue_step calls made through queue_step()
 
 
 def load_library() -> C.CDLL:
@@ -286,126 +267,88 @@ def load_library() -> C.CDLL:
     return lib
 
 
-def load_plugin_library() -> C.CDLL:
-    """dlopen libd2d_plugin.so and type its entry points.  Raises if it has not been built."""
-    global _plugin
-    if _plugin is not None:
-        return _plugin
-    if not PLUGIN_PATH.exists():
-        raise ImportError(f'{PLUGIN_PATH} is missing - build it with `python -m gym_d2d_amd.build`')
-    lib = C.CDLL(str(PLUGIN_PATH))
-    for name, (res, args) in PLUGIN_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _plugin = lib
+def side_path(name: str) -> Path:
+    return Path(__file__).resolve().parent / 'lib' / f'libd2d_{name}.so'
+
+
+def side_library(name: str) -> C.CDLL:
+    """dlopen libd2d_<name>.so once and type the entry points SIDE[name] lists.  Raises if it has not been built."""
+    lib = _side.get(name)
+    if lib is None:
+        path = side_path(name)
+        if not path.exists():
+            raise ImportError(f'{path} is missing - build it with `python -m gym_d2d_amd.build`')
+        lib = C.CDLL(str(path))
+        for symbol, (res, args) in SIDE[name].items():
+            fn = getattr(lib, symbol)
+            fn.restype = res
+            fn.argtypes = args
+        _side[name] = lib
     return lib
 
 
+def _check_side(name: str, rc: int) -> None:
+    if rc != 0:
+        raise NativeError(rc, getattr(side_library(name), f'd2d_{name}_last_error')().decode(errors='replace'))
+
+
+# the public loaders: a caller that wants a missing library to fail early calls one (mobility.py, queues.py); the wrappers below
+# go through them too, so replacing one intercepts every use of its library
+def load_plugin_library() -> C.CDLL: return side_library('plugin')
+def load_episode_library() -> C.CDLL: return side_library('episode')
+def load_sense_library() -> C.CDLL: return side_library('sense')
+def load_graph_library() -> C.CDLL: return side_library('graph')
+def load_marginal_library() -> C.CDLL: return side_library('marginal')
+def load_mobility_library() -> C.CDLL: return side_library('mobility')
+def load_channel_library() -> C.CDLL: return side_library('channel')
+def load_queue_library() -> C.CDLL: return side_library('queue')
+def load_bestrb_library() -> C.CDLL: return side_library('bestrb')
+def load_powerctl_library() -> C.CDLL: return side_library('powerctl')
+def load_brdyn_library() -> C.CDLL: return side_library('brdyn')
+def load_evaluate_library() -> C.CDLL: return side_library('evaluate')
+
+
+# Pointer arguments are passed as the ints they are: every argtype is c_void_p, which takes 0 as the null pointer and any int up to
+# 2^64 - 1 as that address.  The c_uint64(... & (2 ** 64 - 1)) and & 0xFFFFFFFF maskings define the wrap-around and stay.
 def plugin_normal(out_ptr: int, dtype: int, n_envs: int, first_env: int, n_rows: int, n_cols: int, step: int, kind: int,
                   seed: int, stream_ptr: int = 0) -> None:
     """d2d_plugin_normal: standard normals of the built-in shadowing stream into device memory [n_envs, n_rows, n_cols]."""
-    lib = load_plugin_library()
-    rc = lib.d2d_plugin_normal(_P(out_ptr), dtype, n_envs, C.c_uint64(first_env), n_rows, n_cols, C.c_uint64(step & (2 ** 64 - 1)),
-                               kind, C.c_uint64(seed & (2 ** 64 - 1)), _P(stream_ptr or None))
-    if rc != 0:
-        raise NativeError(rc, lib.d2d_plugin_last_error().decode(errors='replace'))
-
-
-def load_episode_library() -> C.CDLL:
-    """dlopen libd2d_episode.so and type its entry points.  Raises if it has not been built."""
-    global _episode
-    if _episode is not None:
-        return _episode
-    if not EPISODE_PATH.exists():
-        raise ImportError(f'{EPISODE_PATH} is missing - build it with `python -m gym_d2d_amd.build`')
-    lib = C.CDLL(str(EPISODE_PATH))
-    for name, (res, args) in EPISODE_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _episode = lib
-    return lib
-
-
-def _check_episode(rc: int) -> None:
-    if rc != 0:
-        raise NativeError(rc, load_episode_library().d2d_episode_last_error().decode(errors='replace'))
+    _check_side('plugin', load_plugin_library().d2d_plugin_normal(
+        out_ptr, dtype, n_envs, C.c_uint64(first_env), n_rows, n_cols, C.c_uint64(step & (2 ** 64 - 1)), kind,
+        C.c_uint64(seed & (2 ** 64 - 1)), stream_ptr))
 
 
 def episode_merge_actions(in_ptr: int, out_ptr: int, pending_ptr: int, episode_ptr: int, high_ptr: int, n_envs: int, n_cols: int,
                           first_env: int, seed: int, stream_ptr: int = 0) -> None:
     """d2d_episode_merge_actions: out[b] = pending[b] ? the reset's random actions at episode[b] : in[b] (device pointers)."""
-    _check_episode(load_episode_library().d2d_episode_merge_actions(
-        _P(in_ptr), _P(out_ptr), _P(pending_ptr), _P(episode_ptr), _P(high_ptr), n_envs, n_cols, C.c_uint64(first_env),
-        C.c_uint64(seed & (2 ** 64 - 1)), _P(stream_ptr or None)))
+    _check_side('episode', load_episode_library().d2d_episode_merge_actions(
+        in_ptr, out_ptr, pending_ptr, episode_ptr, high_ptr, n_envs, n_cols, C.c_uint64(first_env), C.c_uint64(seed & (2 ** 64 - 1)),
+        stream_ptr))
 
 
 def episode_advance(pending_ptr: int, episode_ptr: int, elapsed_ptr: int, done_ptr: int, reset_ptr: int, reward_ptr: int,
                     reward_cols: int, n_envs: int, episode_length: int, stream_ptr: int = 0) -> None:
     """d2d_episode_advance: per-env counters after a step; zeroes the reward rows of the envs that were reset (reward_ptr 0: none)."""
-    _check_episode(load_episode_library().d2d_episode_advance(
-        _P(pending_ptr), _P(episode_ptr), _P(elapsed_ptr), _P(done_ptr), _P(reset_ptr), _P(reward_ptr or None), reward_cols, n_envs,
-        episode_length, _P(stream_ptr or None)))
-
-
-def load_sense_library() -> C.CDLL:
-    """dlopen libd2d_sense.so and type its entry points.  Raises if it has not been built."""
-    global _sense
-    if _sense is not None:
-        return _sense
-    if not SENSE_PATH.exists():
-        raise ImportError(f'{SENSE_PATH} is missing - build it with `python -m gym_d2d_amd.build`')
-    lib = C.CDLL(str(SENSE_PATH))
-    for name, (res, args) in SENSE_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _sense = lib
-    return lib
+    _check_side('episode', load_episode_library().d2d_episode_advance(
+        pending_ptr, episode_ptr, elapsed_ptr, done_ptr, reset_ptr, reward_ptr, reward_cols, n_envs, episode_length, stream_ptr))
 
 
 def sense_rb(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, link_tx_ptr: int, link_rx_ptr: int, cols_ptr: int, law: int,
              pow_k: int, n_envs: int, n_dev: int, n_links: int, n_rbs: int, what: int, out_ptr: int, stream_ptr: int = 0) -> None:
     """d2d_sense_rb: every link's SINR (dB) or interference (mW) on every RB into out [n_envs, n_links, n_rbs] (device pointers)."""
     global sense_launches
-    lib = load_sense_library()
-    rc = lib.d2d_sense_rb(_P(pos_x_ptr or None), _P(pos_y_ptr or None), _P(rb_ptr or None), _P(pwr_ptr or None), _P(link_tx_ptr or None),
-                          _P(link_rx_ptr or None), _P(cols_ptr or None), law, pow_k, n_envs, n_dev, n_links, n_rbs, what,
-                          _P(out_ptr or None), _P(stream_ptr or None))
-    if rc != 0:
-        raise NativeError(rc, lib.d2d_sense_last_error().decode(errors='replace'))
+    _check_side('sense', load_sense_library().d2d_sense_rb(
+        pos_x_ptr, pos_y_ptr, rb_ptr, pwr_ptr, link_tx_ptr, link_rx_ptr, cols_ptr, law, pow_k, n_envs, n_dev, n_links, n_rbs, what,
+        out_ptr, stream_ptr))
     sense_launches += 1
-
-
-def load_graph_library() -> C.CDLL:
-    """dlopen libd2d_graph.so and type its entry points.  Raises if it has not been built."""
-    global _graph
-    if _graph is not None:
-        return _graph
-    if not GRAPH_PATH.exists():
-        raise ImportError(f'{GRAPH_PATH} is missing - build it with `python -m gym_d2d_amd.build`')
-    lib = C.CDLL(str(GRAPH_PATH))
-    for name, (res, args) in GRAPH_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _graph = lib
-    return lib
-
-
-def _graph_call(which: str, rc: int) -> None:
-    if rc != 0:
-        raise NativeError(rc, load_graph_library().d2d_graph_last_error().decode(errors='replace'))
-    graph_launches[which] += 1
 
 
 def graph_coupling(pos_x_ptr: int, pos_y_ptr: int, link_tx_ptr: int, link_rx_ptr: int, cols_ptr: int, law: int, pow_k: int,
                    n_envs: int, n_dev: int, n_links: int, out_ptr: int, stream_ptr: int = 0) -> None:
     """d2d_graph_coupling: coupling_db [n_envs, n_links (receiver i), n_links (transmitter j)] into out (device pointers)."""
-    _graph_call('coupling', load_graph_library().d2d_graph_coupling(
-        _P(pos_x_ptr or None), _P(pos_y_ptr or None), _P(link_tx_ptr or None), _P(link_rx_ptr or None), _P(cols_ptr or None), law,
-        pow_k, n_envs, n_dev, n_links, _P(out_ptr or None), _P(stream_ptr or None)))
+    _check_side('graph', load_graph_library().d2d_graph_coupling(
+        pos_x_ptr, pos_y_ptr, link_tx_ptr, link_rx_ptr, cols_ptr, law, pow_k, n_envs, n_dev, n_links, out_ptr, stream_ptr))
+    graph_launches['coupling'] += 1
 
 
 def graph_neighbors(pos_x_ptr: int, pos_y_ptr: int, link_tx_ptr: int, link_rx_ptr: int, cols_ptr: int, law: int, pow_k: int,
@@ -413,34 +356,18 @@ def graph_neighbors(pos_x_ptr: int, pos_y_ptr: int, link_tx_ptr: int, link_rx_pt
                     stream_ptr: int = 0) -> None:
     """d2d_graph_neighbors: every receiver's k strongest interferers, idx / coupling_db [n_envs, n_links (receiver i), k] (device
     pointers; env_mask_ptr 0: every env, else uint8 [n_envs] and the envs whose byte is 0 keep their rows)."""
-    _graph_call('neighbors', load_graph_library().d2d_graph_neighbors(
-        _P(pos_x_ptr or None), _P(pos_y_ptr or None), _P(link_tx_ptr or None), _P(link_rx_ptr or None), _P(cols_ptr or None), law,
-        pow_k, n_envs, n_dev, n_links, k, _P(env_mask_ptr or None), _P(idx_ptr or None), _P(coupling_ptr or None),
-        _P(stream_ptr or None)))
+    _check_side('graph', load_graph_library().d2d_graph_neighbors(
+        pos_x_ptr, pos_y_ptr, link_tx_ptr, link_rx_ptr, cols_ptr, law, pow_k, n_envs, n_dev, n_links, k, env_mask_ptr, idx_ptr,
+        coupling_ptr, stream_ptr))
+    graph_launches['neighbors'] += 1
 
 
 def graph_neighbor_obs(idx_ptr: int, coupling_ptr: int, rb_ptr: int, pwr_ptr: int, sinr_ptr: int, snr_ptr: int, n_envs: int,
                        n_links: int, k: int, out_ptr: int, stream_ptr: int = 0) -> None:
     """d2d_graph_neighbor_obs: the per-step gather, out [n_envs, n_links (receiver i), k + 1, 4] (device pointers)."""
-    _graph_call('neighbor_obs', load_graph_library().d2d_graph_neighbor_obs(
-        _P(idx_ptr or None), _P(coupling_ptr or None), _P(rb_ptr or None), _P(pwr_ptr or None), _P(sinr_ptr or None),
-        _P(snr_ptr or None), n_envs, n_links, k, _P(out_ptr or None), _P(stream_ptr or None)))
-
-
-def load_marginal_library() -> C.CDLL:
-    """dlopen libd2d_marginal.so and type its entry points.  Raises if it has not been built."""
-    global _marginal
-    if _marginal is not None:
-        return _marginal
-    if not MARGINAL_PATH.exists():
-        raise ImportError(f'{MARGINAL_PATH} is missing - build it with `python -m gym_d2d_amd.build`')
-    lib = C.CDLL(str(MARGINAL_PATH))
-    for name, (res, args) in MARGINAL_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _marginal = lib
-    return lib
+    _check_side('graph', load_graph_library().d2d_graph_neighbor_obs(
+        idx_ptr, coupling_ptr, rb_ptr, pwr_ptr, sinr_ptr, snr_ptr, n_envs, n_links, k, out_ptr, stream_ptr))
+    graph_launches['neighbor_obs'] += 1
 
 
 def marginal_capacity(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, link_tx_ptr: int, link_rx_ptr: int, cols_ptr: int,
@@ -448,30 +375,10 @@ def marginal_capacity(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int,
                       diff_ptr: int, stream_ptr: int = 0) -> None:
     """d2d_marginal_capacity: every link's harm and difference reward (Mbps) into two planes [n_envs, n_links] (device pointers)."""
     global marginal_launches
-    lib = load_marginal_library()
-    rc = lib.d2d_marginal_capacity(_P(pos_x_ptr or None), _P(pos_y_ptr or None), _P(rb_ptr or None), _P(pwr_ptr or None),
-                                   _P(link_tx_ptr or None), _P(link_rx_ptr or None), _P(cols_ptr or None), _P(cap_cols_ptr or None),
-                                   law, pow_k, n_envs, n_dev, n_links, n_rbs, _P(harm_ptr or None), _P(diff_ptr or None),
-                                   _P(stream_ptr or None))
-    if rc != 0:
-        raise NativeError(rc, lib.d2d_marginal_last_error().decode(errors='replace'))
+    _check_side('marginal', load_marginal_library().d2d_marginal_capacity(
+        pos_x_ptr, pos_y_ptr, rb_ptr, pwr_ptr, link_tx_ptr, link_rx_ptr, cols_ptr, cap_cols_ptr, law, pow_k, n_envs, n_dev, n_links,
+        n_rbs, harm_ptr, diff_ptr, stream_ptr))
     marginal_launches += 1
-
-
-def load_bestrb_library() -> C.CDLL:
-    """dlopen libd2d_bestrb.so and type its entry points.  Raises if it has not been built."""
-    global _bestrb
-    if _bestrb is not None:
-        return _bestrb
-    if not BESTRB_PATH.exists():
-        raise ImportError(f'{BESTRB_PATH} is missing - build it with `python -m gym_d2d_amd.build`')
-    lib = C.CDLL(str(BESTRB_PATH))
-    for name, (res, args) in BESTRB_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _bestrb = lib
-    return lib
 
 
 def best_rb(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, link_tx_ptr: int, link_rx_ptr: int, cols_ptr: int, law: int,
@@ -481,30 +388,10 @@ def best_rb(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, link_tx_p
     (device pointers; allowed_ptr 0: every RB, else uint32 [n_links, ceil(n_rbs / 32)]; env_mask_ptr 0: every env, else uint8
     [n_envs] and the envs whose byte is 0 keep their rows)."""
     global bestrb_launches
-    lib = load_bestrb_library()
-    rc = lib.d2d_best_rb(_P(pos_x_ptr or None), _P(pos_y_ptr or None), _P(rb_ptr or None), _P(pwr_ptr or None), _P(link_tx_ptr or None),
-                         _P(link_rx_ptr or None), _P(cols_ptr or None), law, pow_k, n_envs, n_dev, n_links, n_rbs,
-                         _P(allowed_ptr or None), _P(env_mask_ptr or None), _P(best_rb_ptr or None), _P(best_sinr_ptr or None),
-                         _P(gain_ptr or None), _P(stream_ptr or None))
-    if rc != 0:
-        raise NativeError(rc, lib.d2d_bestrb_last_error().decode(errors='replace'))
+    _check_side('bestrb', load_bestrb_library().d2d_best_rb(
+        pos_x_ptr, pos_y_ptr, rb_ptr, pwr_ptr, link_tx_ptr, link_rx_ptr, cols_ptr, law, pow_k, n_envs, n_dev, n_links, n_rbs,
+        allowed_ptr, env_mask_ptr, best_rb_ptr, best_sinr_ptr, gain_ptr, stream_ptr))
     bestrb_launches += 1
-
-
-def load_powerctl_library() -> C.CDLL:
-    """dlopen libd2d_powerctl.so and type its entry points.  Raises if it has not been built."""
-    global _powerctl
-    if _powerctl is not None:
-        return _powerctl
-    if not POWERCTL_PATH.exists():
-        raise ImportError(f'{POWERCTL_PATH} is missing - build it with `python -m gym_d2d_amd.build`')
-    lib = C.CDLL(str(POWERCTL_PATH))
-    for name, (res, args) in POWERCTL_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _powerctl = lib
-    return lib
 
 
 def power_control(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, link_tx_ptr: int, link_rx_ptr: int, cols_ptr: int,
@@ -516,32 +403,12 @@ def power_control(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, lin
     adjustable_ptr 0: every link, else uint8 [n_links]; env_mask_ptr 0: every env, else uint8 [n_envs] and the envs whose byte is 0
     keep their rows)."""
     global powerctl_launches
-    lib = load_powerctl_library()
-    rc = lib.d2d_power_control(_P(pos_x_ptr or None), _P(pos_y_ptr or None), _P(rb_ptr or None), _P(pwr_ptr or None),
-                               _P(link_tx_ptr or None), _P(link_rx_ptr or None), _P(cols_ptr or None), law, pow_k, n_envs, n_dev,
-                               n_links, n_rbs, _P(target_ptr or None), _P(p_min_ptr or None), _P(p_max_ptr or None),
-                               _P(adjustable_ptr or None), max_iters, _P(env_mask_ptr or None), _P(power_ptr or None),
-                               _P(sinr_ptr or None), _P(iters_ptr or None), _P(converged_ptr or None), _P(stream_ptr or None))
-    if rc != 0:
-        raise NativeError(rc, lib.d2d_powerctl_last_error().decode(errors='replace'))
+    _check_side('powerctl', load_powerctl_library().d2d_power_control(
+        pos_x_ptr, pos_y_ptr, rb_ptr, pwr_ptr, link_tx_ptr, link_rx_ptr, cols_ptr, law, pow_k, n_envs, n_dev, n_links, n_rbs,
+        target_ptr, p_min_ptr, p_max_ptr, adjustable_ptr, max_iters, env_mask_ptr, power_ptr, sinr_ptr, iters_ptr, converged_ptr,
+        stream_ptr))
     if n_envs:
         powerctl_launches += 1
-
-
-def load_brdyn_library() -> C.CDLL:
-    """dlopen libd2d_brdyn.so and type its entry points.  Raises if it has not been built."""
-    global _brdyn
-    if _brdyn is not None:
-        return _brdyn
-    if not BRDYN_PATH.exists():
-        raise ImportError(f'{BRDYN_PATH} is missing - build it with `python -m gym_d2d_amd.build`')
-    lib = C.CDLL(str(BRDYN_PATH))
-    for name, (res, args) in BRDYN_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _brdyn = lib
-    return lib
 
 
 def best_response_dynamics(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, link_tx_ptr: int, link_rx_ptr: int, cols_ptr: int,
@@ -553,33 +420,12 @@ def best_response_dynamics(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr:
     [n_links, ceil(n_rbs / 32)]; movable_ptr 0: every link, else uint8 [n_links]; env_mask_ptr 0: every env, else uint8 [n_envs]
     and the envs whose byte is 0 keep their rows)."""
     global brdyn_launches
-    lib = load_brdyn_library()
-    rc = lib.d2d_best_response_dynamics(_P(pos_x_ptr or None), _P(pos_y_ptr or None), _P(rb_ptr or None), _P(pwr_ptr or None),
-                                        _P(link_tx_ptr or None), _P(link_rx_ptr or None), _P(cols_ptr or None), law, pow_k, n_envs,
-                                        n_dev, n_links, n_rbs, _P(allowed_ptr or None), _P(movable_ptr or None), min_gain_db,
-                                        max_rounds, _P(env_mask_ptr or None), _P(rb_out_ptr or None), _P(sinr_ptr or None),
-                                        _P(rounds_ptr or None), _P(moves_ptr or None), _P(converged_ptr or None),
-                                        _P(stream_ptr or None))
-    if rc != 0:
-        raise NativeError(rc, lib.d2d_brdyn_last_error().decode(errors='replace'))
+    _check_side('brdyn', load_brdyn_library().d2d_best_response_dynamics(
+        pos_x_ptr, pos_y_ptr, rb_ptr, pwr_ptr, link_tx_ptr, link_rx_ptr, cols_ptr, law, pow_k, n_envs, n_dev, n_links, n_rbs,
+        allowed_ptr, movable_ptr, min_gain_db, max_rounds, env_mask_ptr, rb_out_ptr, sinr_ptr, rounds_ptr, moves_ptr, converged_ptr,
+        stream_ptr))
     if n_envs:
         brdyn_launches += 1
-
-
-def load_evaluate_library() -> C.CDLL:
-    """dlopen libd2d_evaluate.so and type its entry points.  Raises if it has not been built."""
-    global _evaluate
-    if _evaluate is not None:
-        return _evaluate
-    if not EVALUATE_PATH.exists():
-        raise ImportError(f'{EVALUATE_PATH} is missing - build it with `python -m gym_d2d_amd.build`')
-    lib = C.CDLL(str(EVALUATE_PATH))
-    for name, (res, args) in EVALUATE_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _evaluate = lib
-    return lib
 
 
 def evaluate(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, link_tx_ptr: int, link_rx_ptr: int, cols_ptr: int,
@@ -589,30 +435,11 @@ def evaluate(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, link_tx_
     n_links] (either pointer 0: not written) and total_mbps float32 [n_envs, n_cand] (device pointers; rb_ptr / pwr_ptr int32
     [n_envs, n_cand, n_links])."""
     global evaluate_launches
-    lib = load_evaluate_library()
-    rc = lib.d2d_evaluate(_P(pos_x_ptr or None), _P(pos_y_ptr or None), _P(rb_ptr or None), _P(pwr_ptr or None), _P(link_tx_ptr or None),
-                          _P(link_rx_ptr or None), _P(cols_ptr or None), _P(cap_cols_ptr or None), law, pow_k, n_envs, n_cand, n_dev,
-                          n_links, n_rbs, _P(sinr_ptr or None), _P(capacity_ptr or None), _P(total_ptr or None), _P(stream_ptr or None))
-    if rc != 0:
-        raise NativeError(rc, lib.d2d_evaluate_last_error().decode(errors='replace'))
+    _check_side('evaluate', load_evaluate_library().d2d_evaluate(
+        pos_x_ptr, pos_y_ptr, rb_ptr, pwr_ptr, link_tx_ptr, link_rx_ptr, cols_ptr, cap_cols_ptr, law, pow_k, n_envs, n_cand, n_dev,
+        n_links, n_rbs, sinr_ptr, capacity_ptr, total_ptr, stream_ptr))
     if n_envs:
         evaluate_launches += 1
-
-
-def load_mobility_library() -> C.CDLL:
-    """dlopen libd2d_mobility.so and type its entry points.  Raises if it has not been built."""
-    global _mobility
-    if _mobility is not None:
-        return _mobility
-    if not MOBILITY_PATH.exists():
-        raise ImportError(f'{MOBILITY_PATH} is missing - build it with `python -m gym_d2d_amd.build`')
-    lib = C.CDLL(str(MOBILITY_PATH))
-    for name, (res, args) in MOBILITY_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _mobility = lib
-    return lib
 
 
 def mobility_move(pos_x_ptr: int, pos_y_ptr: int, vel_x_ptr: int, vel_y_ptr: int, fixed_mask_ptr: int, n_envs: int, n_cues: int,
@@ -622,31 +449,11 @@ def mobility_move(pos_x_ptr: int, pos_y_ptr: int, vel_x_ptr: int, vel_y_ptr: int
     """d2d_mobility_move: one Gauss-Markov move of the position / velocity planes [n_envs, n_dev] in place (device pointers), or the
     start-of-episode velocities (step 0); reset_ptr != 0: the per-env clock of the four [n_envs] arrays."""
     global mobility_launches
-    lib = load_mobility_library()
-    rc = lib.d2d_mobility_move(_P(pos_x_ptr or None), _P(pos_y_ptr or None), _P(vel_x_ptr or None), _P(vel_y_ptr or None),
-                               _P(fixed_mask_ptr or None), n_envs, n_cues, n_due_pairs, C.c_uint64(first_env),
-                               C.c_uint64(seed & (2 ** 64 - 1)), memory, noise_scale, speed_std, dt_s, cell_radius_m, d2d_radius_m,
-                               step & 0xFFFFFFFF, episode & 0xFFFFFFFF, _P(elapsed_ptr or None), _P(start_ptr or None),
-                               _P(episode_ptr or None), _P(reset_ptr or None), _P(stream_ptr or None))
-    if rc != 0:
-        raise NativeError(rc, lib.d2d_mobility_last_error().decode(errors='replace'))
+    _check_side('mobility', load_mobility_library().d2d_mobility_move(
+        pos_x_ptr, pos_y_ptr, vel_x_ptr, vel_y_ptr, fixed_mask_ptr, n_envs, n_cues, n_due_pairs, C.c_uint64(first_env),
+        C.c_uint64(seed & (2 ** 64 - 1)), memory, noise_scale, speed_std, dt_s, cell_radius_m, d2d_radius_m, step & 0xFFFFFFFF,
+        episode & 0xFFFFFFFF, elapsed_ptr, start_ptr, episode_ptr, reset_ptr, stream_ptr))
     mobility_launches += 1
-
-
-def load_channel_library() -> C.CDLL:
-    """dlopen libd2d_channel.so and type its entry points.  Raises if it has not been built."""
-    global _channel
-    if _channel is not None:
-        return _channel
-    if not CHANNEL_PATH.exists():
-        raise ImportError(f'{CHANNEL_PATH} is missing - build it with `python -m gym_d2d_amd.build`')
-    lib = C.CDLL(str(CHANNEL_PATH))
-    for name, (res, args) in CHANNEL_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _channel = lib
-    return lib
 
 
 def channel_fill(pos_x_ptr: int, pos_y_ptr: int, link_tx_ptr: int, link_rx_ptr: int, a_tx_ptr: int, a_rx_ptr: int, exponent_ptr: int,
@@ -657,33 +464,13 @@ def channel_fill(pos_x_ptr: int, pos_y_ptr: int, link_tx_ptr: int, link_rx_ptr: 
     """d2d_channel_fill: the spatial channel's live dB table [n_envs, n_links + 1, n_links] of table_dtype (F32 / F64; device pointers) at the clock
     (episode, step); reset_ptr != 0: the per-env clock of the four [n_envs] arrays."""
     global channel_launches
-    lib = load_channel_library()
     u64 = 2 ** 64 - 1
-    rc = lib.d2d_channel_fill(_P(pos_x_ptr or None), _P(pos_y_ptr or None), _P(link_tx_ptr or None), _P(link_rx_ptr or None),
-                              _P(a_tx_ptr or None), _P(a_rx_ptr or None), _P(exponent_ptr or None), n_envs, n_dev, n_links,
-                              C.c_uint64(first_env), num_sinusoids, shadow_amp_db, wave_scale, fading, rician_mu, rician_s,
-                              C.c_uint64(shadow_seed & u64), C.c_uint64(fading_seed & u64), step & 0xFFFFFFFF, episode & 0xFFFFFFFF,
-                              _P(elapsed_ptr or None), _P(start_ptr or None), _P(episode_ptr or None), _P(reset_ptr or None),
-                              _P(scratch_ptr or None), _P(table_ptr or None), table_dtype, _P(stream_ptr or None))
-    if rc != 0:
-        raise NativeError(rc, lib.d2d_channel_last_error().decode(errors='replace'))
+    _check_side('channel', load_channel_library().d2d_channel_fill(
+        pos_x_ptr, pos_y_ptr, link_tx_ptr, link_rx_ptr, a_tx_ptr, a_rx_ptr, exponent_ptr, n_envs, n_dev, n_links, C.c_uint64(first_env),
+        num_sinusoids, shadow_amp_db, wave_scale, fading, rician_mu, rician_s, C.c_uint64(shadow_seed & u64),
+        C.c_uint64(fading_seed & u64), step & 0xFFFFFFFF, episode & 0xFFFFFFFF, elapsed_ptr, start_ptr, episode_ptr, reset_ptr,
+        scratch_ptr, table_ptr, table_dtype, stream_ptr))
     channel_launches += 1
-
-
-def load_queue_library() -> C.CDLL:
-    """dlopen libd2d_queue.so and type its entry points.  Raises if it has not been built."""
-    global _queue
-    if _queue is not None:
-        return _queue
-    if not QUEUE_PATH.exists():
-        raise ImportError(f'{QUEUE_PATH} is missing - build it with `python -m gym_d2d_amd.build`')
-    lib = C.CDLL(str(QUEUE_PATH))
-    for name, (res, args) in QUEUE_SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    _queue = lib
-    return lib
 
 
 def queue_step(capacity_ptr: int, ring_ptr: int, arrived_ptr: int, served_ptr: int, expired_ptr: int, overflow_ptr: int, backlog_ptr: int,
@@ -698,15 +485,11 @@ def queue_step(capacity_ptr: int, ring_ptr: int, arrived_ptr: int, served_ptr: i
     tab = np.ascontiguousarray(thresholds, dtype=np.uint32)
     if tab.shape != (2, QUEUE_TABLE):
         raise ValueError(f'thresholds must be uint32 [2, {QUEUE_TABLE}], got {tab.shape}')
-    rc = lib.d2d_queue_step(_P(capacity_ptr or None), _P(ring_ptr or None), _P(arrived_ptr or None), _P(served_ptr or None),
-                            _P(expired_ptr or None), _P(overflow_ptr or None), _P(backlog_ptr or None), _P(hol_age_ptr or None),
-                            _P(mean_delay_ptr or None), _P(on_ptr or None), _P(tab.ctypes.data), n_envs, n_cues, n_due_pairs,
-                            deadline_steps, packet_bits, buffer_bits, bits_per_mbps_step, p_on_to_off, p_off_to_on, p_start_on,
-                            C.c_uint64(first_env), C.c_uint64(seed & (2 ** 64 - 1)), step & 0xFFFFFFFF, episode & 0xFFFFFFFF,
-                            _P(elapsed_ptr or None), _P(start_ptr or None), _P(episode_ptr or None), _P(reset_ptr or None),
-                            _P(stream_ptr or None))
-    if rc != 0:
-        raise NativeError(rc, lib.d2d_queue_last_error().decode(errors='replace'))
+    _check_side('queue', lib.d2d_queue_step(
+        capacity_ptr, ring_ptr, arrived_ptr, served_ptr, expired_ptr, overflow_ptr, backlog_ptr, hol_age_ptr, mean_delay_ptr, on_ptr,
+        tab.ctypes.data, n_envs, n_cues, n_due_pairs, deadline_steps, packet_bits, buffer_bits, bits_per_mbps_step, p_on_to_off,
+        p_off_to_on, p_start_on, C.c_uint64(first_env), C.c_uint64(seed & (2 ** 64 - 1)), step & 0xFFFFFFFF, episode & 0xFFFFFFFF,
+        elapsed_ptr, start_ptr, episode_ptr, reset_ptr, stream_ptr))
     queue_launches += 1
 
 

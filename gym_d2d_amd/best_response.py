@@ -11,7 +11,7 @@ from typing import Optional
 import numpy as np
 
 from . import _native
-from .sensing import fold_columns, unserved
+from .sensing import PairKernel, unserved
 
 
 def refusal(sim, export_actions: bool, use_torch: bool = True) -> Optional[str]:
@@ -65,33 +65,25 @@ def encode_actions(rb, pwr, best_rb, gain_db, levels, min_gain_db: float, first_
     return (torch.where(move, best_rb, rb) * levels + pwr).to(torch.int32)
 
 
-class BestRb:
+def words(kernel, allowed):
+    """None, or the packed words of `allowed` (bool [N, R], tensor or array) as an int32 tensor on the device of `kernel` (a
+    PairKernel with an RB count).  BestRb and BestResponseDynamics carry it as their method `words`."""
+    if allowed is None:
+        return None
+    torch = kernel.torch
+    mask = torch.as_tensor(allowed, device=kernel.device) if not torch.is_tensor(allowed) else allowed.to(kernel.device)
+    if tuple(mask.shape) != (kernel.n, kernel.r) or mask.dtype != torch.bool:
+        raise ValueError(f'allowed must be bool [{kernel.n}, {kernel.r}] (link, RB) or None')
+    return pack_allowed(mask, torch).contiguous()
+
+
+class BestRb(PairKernel):
     """The best-response kernel bound to one env object: constants uploaded once, one launch per call."""
+    words = words                                # best_response.words, as a method: self.words(allowed)
 
     def __init__(self, sim, num_links: int, torch, device) -> None:
-        from .device import link_budget_columns
-        self.sim, self.torch, self.device = sim, torch, device
-        h = sim.handle
-        self.b, self.d, self.n, self.r = sim.num_envs, h.num_devices, int(num_links), int(sim.config.num_rbs)
-        if self.r > _native.BESTRB_MAX_RBS:
-            raise ValueError(f'best_rb() serves at most {_native.BESTRB_MAX_RBS} RBs (num_rbs = {self.r})')
-        tx, rx = np.asarray(sim.link_tx, dtype=np.int32), np.asarray(sim.link_rx, dtype=np.int32)
-        if len(tx) != self.n or tx.min() < 0 or tx.max() >= self.d or rx.min() < 0 or rx.max() >= self.d:
-            raise ValueError('the link list does not match the env')
-        cols, self.law, self.pow_k = fold_columns(link_budget_columns(sim._dev_list), sim.path_loss_table.law, tx)
+        super().__init__(sim, num_links, torch, device, api='best_rb', max_rbs=_native.BESTRB_MAX_RBS)
         self.own = None                              # the three planes this object owns, allocated by the first call without out=
-        self.tx, self.rx, self.cols = (torch.as_tensor(a, device=device) for a in (tx, rx, cols))
-        self.ptrs = tuple(t.data_ptr() for t in (self.tx, self.rx, self.cols))
-
-    def words(self, allowed):
-        """None, or the packed words of `allowed` (bool [N, R], tensor or array) as an int32 tensor on the device."""
-        if allowed is None:
-            return None
-        torch = self.torch
-        mask = torch.as_tensor(allowed, device=self.device) if not torch.is_tensor(allowed) else allowed.to(self.device)
-        if tuple(mask.shape) != (self.n, self.r) or mask.dtype != torch.bool:
-            raise ValueError(f'allowed must be bool [{self.n}, {self.r}] (link, RB) or None')
-        return pack_allowed(mask, torch).contiguous()
 
     def planes(self, t: dict, allowed, out, stream: int, env_mask=None):
         torch = self.torch
@@ -116,6 +108,3 @@ class BestRb:
                         self.pow_k, self.b, self.d, self.n, self.r, 0 if words is None else words.data_ptr(),
                         0 if env_mask is None else env_mask.data_ptr(), best.data_ptr(), sinr.data_ptr(), gain.data_ptr(), stream)
         return best, sinr, gain
-
-    def close(self) -> None:
-        pass

@@ -1,7 +1,7 @@
 """Sequential best-response RB dynamics: the host side of libd2d_brdyn.so (include/d2d_brdyn.h, csrc/d2d_brdyn.hip).
 
 `BestResponseDynamics` owns the device-side constants of one env object (link lists, the columns sensing.fold_columns folds,
-unchanged) and launches the kernel on torch's device pointers; the allowed mask goes through best_response.pack_allowed.
+unchanged) and launches the kernel on torch's device pointers; the allowed mask goes through best_response.words / pack_allowed.
 `encode_actions` turns the solved RBs into the action tensor VecD2DEnv.step() takes.  Torch path only.
 """
 from __future__ import annotations
@@ -12,8 +12,8 @@ from typing import NamedTuple, Optional
 import numpy as np
 
 from . import _native
-from .best_response import pack_allowed
-from .sensing import fold_columns, unserved
+from .best_response import words
+from .sensing import PairKernel, unserved
 
 
 class BestResponseDynamicsResult(NamedTuple):
@@ -66,52 +66,20 @@ def encode_actions(rb, pwr, levels, first_agent: int = 0):
     return act.to(torch.int32)
 
 
-class BestResponseDynamics:
+class BestResponseDynamics(PairKernel):
     """The dynamics kernel bound to one env object: constants uploaded once, one launch per call."""
+    words = words                                # best_response.words, as a method: self.words(allowed)
 
     def __init__(self, sim, num_links: int, agent, torch, device) -> None:
-        from .device import link_budget_columns
-        self.sim, self.torch, self.device = sim, torch, device
-        h = sim.handle
-        self.b, self.d, self.n, self.r = sim.num_envs, h.num_devices, int(num_links), int(sim.config.num_rbs)
-        if self.r > _native.BRDYN_MAX_RBS:
-            raise ValueError(f'best_response_dynamics() serves at most {_native.BRDYN_MAX_RBS} RBs (num_rbs = {self.r})')
-        tx, rx = np.asarray(sim.link_tx, dtype=np.int32), np.asarray(sim.link_rx, dtype=np.int32)
-        if len(tx) != self.n or tx.min() < 0 or tx.max() >= self.d or rx.min() < 0 or rx.max() >= self.d:
-            raise ValueError('the link list does not match the env')
-        cols, self.law, self.pow_k = fold_columns(link_budget_columns(sim._dev_list), sim.path_loss_table.law, tx)
+        super().__init__(sim, num_links, torch, device, api='best_response_dynamics', max_rbs=_native.BRDYN_MAX_RBS)
         self.agent = np.asarray(agent, dtype=bool)                   # links that have an action column: the only ones ever moved
         if self.agent.shape != (self.n,):
             raise ValueError('the agent mask does not match the env')
         self.own = None                              # the five outputs this object owns, allocated by the first call without out=
-        self.tx, self.rx, self.cols = (torch.as_tensor(a, device=device) for a in (tx, rx, cols))
-        self.ptrs = tuple(t.data_ptr() for t in (self.tx, self.rx, self.cols))
-        self._movable = None                         # (key, tensor) of the last call: a repeated mask is not uploaded again
-
-    def words(self, allowed):
-        """None, or the packed words of `allowed` (bool [N, R], tensor or array) as an int32 tensor on the device."""
-        if allowed is None:
-            return None
-        torch = self.torch
-        mask = torch.as_tensor(allowed, device=self.device) if not torch.is_tensor(allowed) else allowed.to(self.device)
-        if tuple(mask.shape) != (self.n, self.r) or mask.dtype != torch.bool:
-            raise ValueError(f'allowed must be bool [{self.n}, {self.r}] (link, RB) or None')
-        return pack_allowed(mask, torch).contiguous()
 
     def movable(self, movable):
         """uint8 [N] on the device: the agent links (None), or those of them `movable` (bool [N], array or tensor) marks."""
-        torch = self.torch
-        if movable is None:
-            host = self.agent
-        else:
-            host = movable.cpu().numpy() if torch.is_tensor(movable) else np.asarray(movable)
-            if host.shape != (self.n,) or host.dtype != np.bool_:
-                raise ValueError(f'movable must be bool [{self.n}] (link) or None')
-            host = host & self.agent
-        key = host.tobytes()
-        if self._movable is None or self._movable[0] != key:
-            self._movable = (key, torch.as_tensor(host.astype(np.uint8), device=self.device))
-        return self._movable[1]
+        return self.agent_subset(movable, 'movable')
 
     def outputs(self, out):
         torch = self.torch
@@ -129,15 +97,6 @@ class BestResponseDynamics:
                              f'{list(shapes[1])}, int32 [{self.b}], int32 [{self.b}] and uint8 [{self.b}] tensors on {self.device} '
                              'that do not share memory')
         return tuple(out)
-
-    def env_mask(self, env_mask):
-        torch = self.torch
-        if env_mask is None:
-            return None
-        m = env_mask if torch.is_tensor(env_mask) else torch.as_tensor(np.asarray(env_mask))
-        if tuple(m.shape) != (self.b,) or m.dtype not in (torch.bool, torch.uint8):
-            raise ValueError(f'env_mask must be bool or uint8 [{self.b}] or None')
-        return m.to(device=self.device, dtype=torch.uint8).contiguous()
 
     def solve(self, t: dict, allowed, movable, min_gain_db: float, max_rounds: int, out, stream: int,
               env_mask=None) -> BestResponseDynamicsResult:
@@ -159,6 +118,3 @@ class BestResponseDynamics:
                                        movable.data_ptr(), float(min_gain_db), int(max_rounds), 0 if mask is None else mask.data_ptr(),
                                        rb.data_ptr(), sinr.data_ptr(), rounds.data_ptr(), moves.data_ptr(), conv.data_ptr(), stream)
         return BestResponseDynamicsResult(rb, sinr, rounds, moves, conv)
-
-    def close(self) -> None:
-        pass

@@ -1,15 +1,9 @@
-"""Build libd2d_hip.so (the product: the C ABI of include/d2d_hip.h), libd2d_plugin.so (the stateless helpers of
-include/d2d_plugin.h behind ArrayPathLoss's view.normal()), libd2d_episode.so (the stateless autoreset kernels of
-include/d2d_episode.h), libd2d_sense.so (the stateless per-RB sensing kernel of include/d2d_sense.h), libd2d_graph.so (the stateless interference-graph kernels of
-include/d2d_graph.h), libd2d_marginal.so (the stateless difference-reward kernel of include/d2d_marginal.h), libd2d_mobility.so (the stateless
-Gauss-Markov move kernel of include/d2d_mobility.h), libd2d_channel.so (the stateless spatial-channel fill of
-include/d2d_channel.h), libd2d_queue.so (the stateless packet-queue step of
-include/d2d_queue.h), libd2d_bestrb.so (the stateless best-response RB selection of
-include/d2d_bestrb.h), libd2d_powerctl.so (the stateless target-SINR power control of
-include/d2d_powerctl.h), libd2d_brdyn.so (the stateless sequential best-response dynamics of
-include/d2d_brdyn.h), libd2d_evaluate.so (the stateless what-if evaluation of candidate joint actions of
-include/d2d_evaluate.h) and libd2d_probe.so (measurement equipment: the write-ceiling probe
-of include/d2d_hip_diag.h) for gfx950 with hipcc - in-tree, so the .so files travel with the repo snapshot.
+"""Build every shared library of `LIBRARIES` for gfx950 with hipcc - in-tree, so the .so files travel with the repo snapshot.
+
+    stem      libd2d_<stem>.so                                        public header
+    hip       the product: the C ABI                                  include/d2d_hip.h
+    probe     measurement equipment: the write-ceiling probe          include/d2d_hip_diag.h
+    the rest  one stateless add-on kernel family each   include/d2d_<stem>.h
 
     python -m gym_d2d_amd.build [--force] [--verbose]
     D2D_BUILD_DIAG=1 python -m gym_d2d_amd.build      # diagnostic build of libd2d_hip.so: the A/B tuning keys and the ablation
@@ -27,39 +21,25 @@ from pathlib import Path
 PKG = Path(__file__).resolve().parent
 CSRC = PKG / 'csrc'
 LIB_DIR = PKG / 'lib'
-LIB_PATH = LIB_DIR / 'libd2d_hip.so'
-PROBE_PATH = LIB_DIR / 'libd2d_probe.so'
-PLUGIN_PATH = LIB_DIR / 'libd2d_plugin.so'
-EPISODE_PATH = LIB_DIR / 'libd2d_episode.so'
-SENSE_PATH = LIB_DIR / 'libd2d_sense.so'
-GRAPH_PATH = LIB_DIR / 'libd2d_graph.so'
-MARGINAL_PATH = LIB_DIR / 'libd2d_marginal.so'
-MOBILITY_PATH = LIB_DIR / 'libd2d_mobility.so'
-CHANNEL_PATH = LIB_DIR / 'libd2d_channel.so'
-QUEUE_PATH = LIB_DIR / 'libd2d_queue.so'
-BESTRB_PATH = LIB_DIR / 'libd2d_bestrb.so'
-POWERCTL_PATH = LIB_DIR / 'libd2d_powerctl.so'
-BRDYN_PATH = LIB_DIR / 'libd2d_brdyn.so'
-EVALUATE_PATH = LIB_DIR / 'libd2d_evaluate.so'
 INCLUDE = PKG.parent / 'include'
 ARCH = 'gfx950'
 
 SOURCES = ['d2d_step.hip', 'd2d_rollout.hip', 'd2d_obs.hip', 'd2d_reset.hip', 'd2d_gain.hip', 'd2d_plan.hip', 'd2d_capi.hip']
-PROBE_SOURCES = ['d2d_probe.hip']
-PLUGIN_SOURCES = ['d2d_plugin.hip']
-EPISODE_SOURCES = ['d2d_episode.hip']
-SENSE_SOURCES = ['d2d_sense.hip']
-GRAPH_SOURCES = ['d2d_graph.hip']
-MARGINAL_SOURCES = ['d2d_marginal.hip']
-MOBILITY_SOURCES = ['d2d_mobility.hip']
-CHANNEL_SOURCES = ['d2d_channel.hip']
-QUEUE_SOURCES = ['d2d_queue.hip']
-BESTRB_SOURCES = ['d2d_bestrb.hip']
-POWERCTL_SOURCES = ['d2d_powerctl.hip']
-BRDYN_SOURCES = ['d2d_brdyn.hip']
-EVALUATE_SOURCES = ['d2d_evaluate.hip']
+# library stem -> its sources, in build order: the one table the digest, the up-to-date test, the compile and the link iterate
+LIBRARIES = {'hip': SOURCES, 'probe': ['d2d_probe.hip'],
+             **{stem: [f'd2d_{stem}.hip'] for stem in ('plugin', 'episode', 'sense', 'graph', 'marginal', 'mobility', 'channel', 'queue',
+                                                       'bestrb', 'powerctl', 'brdyn', 'evaluate')}}
 HEADERS = [CSRC / 'd2d_internal.h', CSRC / 'd2d_plan.h', CSRC / 'd2d_step_device.h', CSRC / 'd2d_store.h', CSRC / 'd2d_same_rb.h', CSRC / 'd2d_addon.h', INCLUDE / 'd2d_hip.h', INCLUDE / 'd2d_hip_diag.h',
-           INCLUDE / 'd2d_plugin.h', INCLUDE / 'd2d_episode.h', INCLUDE / 'd2d_sense.h', INCLUDE / 'd2d_graph.h', INCLUDE / 'd2d_marginal.h', INCLUDE / 'd2d_mobility.h', INCLUDE / 'd2d_channel.h', INCLUDE / 'd2d_queue.h', INCLUDE / 'd2d_bestrb.h', INCLUDE / 'd2d_powerctl.h', INCLUDE / 'd2d_brdyn.h', INCLUDE / 'd2d_evaluate.h']
+           *(INCLUDE / f'd2d_{stem}.h' for stem in LIBRARIES if stem not in ('hip', 'probe'))]
+
+
+def lib_path(stem: str, lib_dir: Path = LIB_DIR) -> Path:
+    return lib_dir / f'libd2d_{stem}.so'
+
+
+LIB_PATH = lib_path('hip')
+PROBE_PATH = lib_path('probe')
+STAMP = 'libd2d_hip.sha256'
 FLAGS = ['-O3', '-std=c++17', '-fPIC', f'--offload-arch={ARCH}', '-fno-gpu-rdc', '-Wall', '-Wno-unused-function', '-Wno-unused-value',
          # the kernels already issue their uniform-address LDS atomics from one lane (or on rare paths): LLVM's atomic optimizer
          # only wraps them in mbcnt / readlane / popcount-multiply sequences
@@ -76,26 +56,37 @@ def _hipcc() -> str:
     raise RuntimeError('hipcc not found: libd2d_hip.so cannot be built (there is no CPU fallback)')
 
 
+def digest_files() -> list:
+    """The files source_digest() hashes, in order: every library's sources, then the headers."""
+    return [p for p in [CSRC / s for sources in LIBRARIES.values() for s in sources] + HEADERS if p.exists()]
+
+
 def source_digest() -> str:
     """sha256 over the kernel / C-ABI sources, headers and compile flags: identifies what a profile was taken on."""
     h = hashlib.sha256()
-    for p in [CSRC / s for s in SOURCES + PROBE_SOURCES + PLUGIN_SOURCES + EPISODE_SOURCES + SENSE_SOURCES + GRAPH_SOURCES + MARGINAL_SOURCES + MOBILITY_SOURCES + CHANNEL_SOURCES + QUEUE_SOURCES + BESTRB_SOURCES + POWERCTL_SOURCES + BRDYN_SOURCES + EVALUATE_SOURCES if (CSRC / s).exists()] + [h for h in HEADERS if h.exists()]:
+    for p in digest_files():
         h.update(p.name.encode()); h.update(p.read_bytes())
     h.update(' '.join(FLAGS).encode())
     return h.hexdigest()
 
 
+def up_to_date(digest: str, lib_dir: Path = LIB_DIR) -> bool:
+    """Every library the package loads (all but the probe) is there and the stamp holds `digest`."""
+    stamp = lib_dir / STAMP
+    return all(p.exists() for p in [lib_path(stem, lib_dir) for stem in LIBRARIES if stem != 'probe'] + [stamp]) \
+        and stamp.read_text().strip() == digest
+
+
 def build(force: bool = False, verbose: bool = False) -> Path:
     LIB_DIR.mkdir(exist_ok=True)
-    stamp = LIB_DIR / 'libd2d_hip.sha256'
     digest = source_digest()
-    if not force and LIB_PATH.exists() and PLUGIN_PATH.exists() and EPISODE_PATH.exists() and SENSE_PATH.exists() and GRAPH_PATH.exists() and MARGINAL_PATH.exists() and MOBILITY_PATH.exists() and CHANNEL_PATH.exists() and QUEUE_PATH.exists() and BESTRB_PATH.exists() and POWERCTL_PATH.exists() and BRDYN_PATH.exists() and EVALUATE_PATH.exists() and stamp.exists() and stamp.read_text().strip() == digest:
+    if not force and up_to_date(digest):
         return LIB_PATH
     hipcc = _hipcc()
     obj_dir = LIB_DIR / 'obj'
     obj_dir.mkdir(exist_ok=True)
     procs = []
-    for s in SOURCES + PROBE_SOURCES + PLUGIN_SOURCES + EPISODE_SOURCES + SENSE_SOURCES + GRAPH_SOURCES + MARGINAL_SOURCES + MOBILITY_SOURCES + CHANNEL_SOURCES + QUEUE_SOURCES + BESTRB_SOURCES + POWERCTL_SOURCES + BRDYN_SOURCES + EVALUATE_SOURCES:
+    for s in [s for sources in LIBRARIES.values() for s in sources]:
         src = CSRC / s
         obj = obj_dir / (src.stem + '.o')
         cmd = [hipcc, *FLAGS, '-I', str(INCLUDE), '-c', str(src), '-o', str(obj)]
@@ -108,20 +99,15 @@ def build(force: bool = False, verbose: bool = False) -> Path:
             raise RuntimeError(f'hipcc failed on {s}:\n{out}')
         if verbose and out.strip():
             print(out)
-    for lib, sources in ((LIB_PATH, SOURCES), (PROBE_PATH, PROBE_SOURCES), (PLUGIN_PATH, PLUGIN_SOURCES),
-                         (EPISODE_PATH, EPISODE_SOURCES), (SENSE_PATH, SENSE_SOURCES), (GRAPH_PATH, GRAPH_SOURCES),
-                         (MARGINAL_PATH, MARGINAL_SOURCES), (MOBILITY_PATH, MOBILITY_SOURCES), (CHANNEL_PATH, CHANNEL_SOURCES),
-                         (QUEUE_PATH, QUEUE_SOURCES), (BESTRB_PATH, BESTRB_SOURCES),
-                         (POWERCTL_PATH, POWERCTL_SOURCES), (BRDYN_PATH, BRDYN_SOURCES),
-                         (EVALUATE_PATH, EVALUATE_SOURCES)):
+    for stem, sources in LIBRARIES.items():
         objs = [str(obj_dir / (Path(s).stem + '.o')) for s in sources]
-        cmd = [hipcc, '-shared', '-fPIC', f'--offload-arch={ARCH}', '-o', str(lib), *objs]
+        cmd = [hipcc, '-shared', '-fPIC', f'--offload-arch={ARCH}', '-o', str(lib_path(stem)), *objs]
         if verbose:
             print(' '.join(cmd), flush=True)
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
         if r.returncode != 0:
             raise RuntimeError(f'link failed:\n{r.stdout}')
-    stamp.write_text(digest)
+    (LIB_DIR / STAMP).write_text(digest)
     return LIB_PATH
 
 

@@ -658,15 +658,25 @@ class VecD2DEnv:
         self._follow_torch_stream()
         self._t['pending'].masked_fill_(m, 1)
 
-    # ------------------------------------------------------------------ per-RB sensing
-    def _rb_sensor(self):
-        if self._sensor is None:
-            why = sensing.refusal(self.simulator, self.export_actions)
+    # ------------------------------------------------------------------ the add-on kernels' objects
+    def _kernel(self, slot: str, module, cls, extra=tuple, torch_only: bool = True):
+        """The add-on kernel object in self.<slot>, opened on first use: module.refusal() says why this env cannot have one
+        (ValueError), else cls(simulator, num_links, *extra(), torch, device) - torch / device None on the NumPy path."""
+        if getattr(self, slot) is None:
+            why = module.refusal(self.simulator, self.export_actions, *((self.use_torch,) if torch_only else ()))
             if why:
                 raise ValueError(why)
-            self._sensor = sensing.RbSensor(self.simulator, self.num_links, torch if self.use_torch else None,
-                                            self.device if self.use_torch else None)
-        return self._sensor
+            where = (torch, self.device) if self.use_torch else (None, None)
+            setattr(self, slot, cls(self.simulator, self.num_links, *extra(), *where))
+        return getattr(self, slot)
+
+    def _agent_links(self):
+        """bool [N]: the links that have an action column (links on fixed actions come first and have none)."""
+        return np.arange(self.num_links) >= self.num_links - self.num_agents
+
+    # ------------------------------------------------------------------ per-RB sensing
+    def _rb_sensor(self):
+        return self._kernel('_sensor', sensing, sensing.RbSensor, torch_only=False)
 
     def sense(self, what: str = 'sinr_db', out=None):
         """What every link would see on every resource block, with everything else as the last step left it: float32 [B, N, R].
@@ -696,13 +706,7 @@ class VecD2DEnv:
 
     # ------------------------------------------------------------------ the neighbour graph
     def _neighbor_graph(self):
-        if self._graph is None:
-            why = graph.refusal(self.simulator, self.export_actions)
-            if why:
-                raise ValueError(why)
-            self._graph = graph.NeighborGraph(self.simulator, self.num_links, torch if self.use_torch else None,
-                                              self.device if self.use_torch else None)
-        return self._graph
+        return self._kernel('_graph', graph, graph.NeighborGraph, torch_only=False)
 
     def coupling(self, out=None):
         """The dense interference graph, float32 [B, N, N]: coupling[b, i, j] = eirp_off_db[tx_j] - PL(tx_j -> rx_i), the dBm link
@@ -752,13 +756,7 @@ class VecD2DEnv:
 
     # ------------------------------------------------------------------ difference rewards
     def _marginal_kernel(self):
-        if self._marginal is None:
-            why = marginal.refusal(self.simulator, self.export_actions)
-            if why:
-                raise ValueError(why)
-            self._marginal = marginal.MarginalCapacity(self.simulator, self.num_links, torch if self.use_torch else None,
-                                                       self.device if self.use_torch else None)
-        return self._marginal
+        return self._kernel('_marginal', marginal, marginal.MarginalCapacity, torch_only=False)
 
     def marginal_capacity(self, out=None):
         """What every link costs the others, with everything as the last step left it: (difference_mbps, harm_mbps), float32 [B, N].
@@ -790,12 +788,7 @@ class VecD2DEnv:
 
     # ------------------------------------------------------------------ best-response RB selection
     def _best_rb_kernel(self):
-        if self._bestrb is None:
-            why = best_response.refusal(self.simulator, self.export_actions, self.use_torch)
-            if why:
-                raise ValueError(why)
-            self._bestrb = best_response.BestRb(self.simulator, self.num_links, torch, self.device)
-        return self._bestrb
+        return self._kernel('_bestrb', best_response, best_response.BestRb)
 
     def best_rb(self, allowed=None, out=None):
         """Where every link would be best off, with everything else as the last step left it: (best_rb int32, best_sinr_db float32,
@@ -842,14 +835,8 @@ class VecD2DEnv:
 
     # ------------------------------------------------------------------ target-SINR power control
     def _power_control_kernel(self):
-        if self._powerctl is None:
-            why = power_control.refusal(self.simulator, self.export_actions, self.use_torch)
-            if why:
-                raise ValueError(why)
-            p_min, p_max = power_control.class_bounds(self.num_pwr_actions, self._cue_kind, self.num_cues, self.num_due_pairs)
-            agent = np.arange(self.num_links) >= self.num_links - self.num_agents
-            self._powerctl = power_control.PowerControl(self.simulator, self.num_links, p_min, p_max, agent, torch, self.device)
-        return self._powerctl
+        return self._kernel('_powerctl', power_control, power_control.PowerControl, lambda: (*power_control.class_bounds(
+            self.num_pwr_actions, self._cue_kind, self.num_cues, self.num_due_pairs), self._agent_links()))
 
     def power_control(self, target_sinr_db, adjustable=None, max_iters: int = 64, out=None, env_mask=None):
         """The least powers that meet a target SINR, with positions and RBs as the last step left them: (power_dbm int32 [B, N],
@@ -893,13 +880,8 @@ class VecD2DEnv:
 
     # ------------------------------------------------------------------ sequential best-response dynamics
     def _best_response_dynamics_kernel(self):
-        if self._brdyn is None:
-            why = best_response_dynamics.refusal(self.simulator, self.export_actions, self.use_torch)
-            if why:
-                raise ValueError(why)
-            agent = np.arange(self.num_links) >= self.num_links - self.num_agents
-            self._brdyn = best_response_dynamics.BestResponseDynamics(self.simulator, self.num_links, agent, torch, self.device)
-        return self._brdyn
+        return self._kernel('_brdyn', best_response_dynamics, best_response_dynamics.BestResponseDynamics,
+                            lambda: (self._agent_links(),))
 
     def best_response_dynamics(self, allowed=None, movable=None, min_gain_db: float = 3.0, max_rounds: int = 16, out=None,
                                env_mask=None):
@@ -945,12 +927,7 @@ class VecD2DEnv:
 
     # ------------------------------------------------------------------ what-if evaluation of candidate joint actions
     def _evaluate_kernel(self):
-        if self._evaluate is None:
-            why = evaluate_mod.refusal(self.simulator, self.export_actions, self.use_torch)
-            if why:
-                raise ValueError(why)
-            self._evaluate = evaluate_mod.Evaluate(self.simulator, self.num_links, torch, self.device)
-        return self._evaluate
+        return self._kernel('_evaluate', evaluate_mod, evaluate_mod.Evaluate)
 
     def evaluate(self, rb, power_dbm, planes=('sinr_db', 'capacity_mbps'), out=None):
         """What K complete joint assignments per env would give, at the current positions: a dict with 'total_mbps' float32 [B, K]

@@ -1,7 +1,7 @@
 """What-if evaluation of candidate joint actions: the host side of libd2d_evaluate.so (include/d2d_evaluate.h, csrc/d2d_evaluate.hip).
 
 `Evaluate` owns the device-side constants of one env object (link lists, the columns sensing.fold_columns folds and the capacity
-columns marginal.fold_capacity_columns folds, both unchanged) and launches the kernel on torch's device pointers.  `decode_actions`
+columns sensing.fold_capacity_columns folds, both unchanged) and launches the kernel on torch's device pointers.  `decode_actions`
 turns action tensors [B, K, num_agents] in step()'s layout into the (rb, tx power) planes [B, K, N] the kernel reads - the inverse of
 best_response.encode_actions / power_control.encode_actions.  Torch path only.
 """
@@ -12,8 +12,7 @@ from typing import Optional
 import numpy as np
 
 from . import _native
-from .marginal import fold_capacity_columns
-from .sensing import fold_columns, unserved
+from .sensing import PairKernel, unserved
 
 PLANES = ('sinr_db', 'capacity_mbps')
 
@@ -73,26 +72,13 @@ def decode_actions(actions, levels, fixed_rb=None, fixed_pwr=None):
     return rb.to(torch.int32).contiguous(), pwr.to(torch.int32).contiguous()
 
 
-class Evaluate:
+class Evaluate(PairKernel):
     """The what-if kernel bound to one env object: constants uploaded once, one launch per call."""
 
     def __init__(self, sim, num_links: int, torch, device) -> None:
-        from .device import link_budget_columns
-        self.sim, self.torch, self.device = sim, torch, device
-        h = sim.handle
-        self.b, self.d, self.n, self.r = sim.num_envs, h.num_devices, int(num_links), int(sim.config.num_rbs)
-        if self.r > _native.EVALUATE_MAX_RBS:
-            raise ValueError(f'evaluate() serves at most {_native.EVALUATE_MAX_RBS} RBs (num_rbs = {self.r})')
-        tx, rx = np.asarray(sim.link_tx, dtype=np.int32), np.asarray(sim.link_rx, dtype=np.int32)
-        if len(tx) != self.n or tx.min() < 0 or tx.max() >= self.d or rx.min() < 0 or rx.max() >= self.d:
-            raise ValueError('the link list does not match the env')
-        budget = link_budget_columns(sim._dev_list)
-        cols, self.law, self.pow_k = fold_columns(budget, sim.path_loss_table.law, tx)
-        cap_cols = fold_capacity_columns(budget)
+        super().__init__(sim, num_links, torch, device, api='evaluate', max_rbs=_native.EVALUATE_MAX_RBS, capacity=True)
         self.own = {}                                # the tensors this object owns, by name; reallocated when K changes
         self.own_k = 0
-        self.tx, self.rx, self.cols, self.cap_cols = (torch.as_tensor(a, device=device) for a in (tx, rx, cols, cap_cols))
-        self.ptrs = tuple(t.data_ptr() for t in (self.tx, self.rx, self.cols, self.cap_cols))
 
     def _check_in(self, x, name: str):
         torch = self.torch
@@ -133,6 +119,3 @@ class Evaluate:
                          self.b, k, self.d, self.n, self.r, res['sinr_db'].data_ptr() if 'sinr_db' in res else 0,
                          res['capacity_mbps'].data_ptr() if 'capacity_mbps' in res else 0, res['total_mbps'].data_ptr(), stream)
         return res
-
-    def close(self) -> None:
-        pass

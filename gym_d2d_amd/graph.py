@@ -14,7 +14,7 @@ from typing import Optional
 import numpy as np
 
 from . import _native
-from .sensing import _HipMemory, fold_columns, unserved
+from .sensing import PairKernel, unserved
 
 
 def refusal(sim, export_actions: bool) -> Optional[str]:
@@ -43,26 +43,13 @@ def check_k(k, num_links: int) -> int:
     return int(k)
 
 
-class NeighborGraph:
+class NeighborGraph(PairKernel):
     """The graph kernels bound to one env object: constants uploaded once, one launch per call.  Index order [b, i, j] / [b, i, m]:
     receiver i first (module docstring)."""
 
     def __init__(self, sim, num_links: int, torch=None, device=None) -> None:
-        from .device import link_budget_columns
-        self.sim, self.torch, self.device = sim, torch, device
-        h = sim.handle
-        self.b, self.d, self.n = sim.num_envs, h.num_devices, int(num_links)
-        tx, rx = np.asarray(sim.link_tx, dtype=np.int32), np.asarray(sim.link_rx, dtype=np.int32)
-        if len(tx) != self.n or tx.min() < 0 or tx.max() >= self.d or rx.min() < 0 or rx.max() >= self.d:
-            raise ValueError('the link list does not match the env')
-        cols, self.law, self.pow_k = fold_columns(link_budget_columns(sim._dev_list), sim.path_loss_table.law, tx)
+        super().__init__(sim, num_links, torch, device)              # no RB cap: the graph reads no RB
         self.own = {}                                # the result blocks this object owns, by name, allocated on first use
-        if torch is not None:
-            self.tx, self.rx, self.cols = (torch.as_tensor(a, device=device) for a in (tx, rx, cols))
-            self.ptrs = tuple(t.data_ptr() for t in (self.tx, self.rx, self.cols))
-        else:
-            self.mem = _HipMemory()
-            self.ptrs = tuple(self.mem.upload(a) for a in (tx, rx, cols))
 
     # ------------------------------------------------------------------ torch path
     def _out_torch(self, name: str, out, shape, dtype):
@@ -152,6 +139,5 @@ class NeighborGraph:
         return res
 
     def close(self) -> None:
-        if self.torch is None:
-            self.mem.close()
+        super().close()
         self.own.clear()

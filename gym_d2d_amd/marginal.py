@@ -1,8 +1,8 @@
 """Difference rewards (leave-one-out capacity): the host side of libd2d_marginal.so (include/d2d_marginal.h, csrc/d2d_marginal.hip).
 
-`fold_capacity_columns` lowers what the capacity needs beyond sensing.fold_columns' block - the transmitter's bandwidth and the
-receiver's threshold - by the rules the step's own records follow (csrc/d2d_capi.hip, refresh_tables), so that the capacity the
-kernel forms for a link is the step's plane.  `MarginalCapacity` owns the device-side constants of one env object and launches the
+`fold_capacity_columns` (stated in sensing.py, next to fold_columns) lowers what the capacity needs beyond sensing.fold_columns'
+block - the transmitter's bandwidth and the receiver's threshold - by the rules the step's own records follow (csrc/d2d_capi.hip,
+refresh_tables), so that the capacity the kernel forms for a link is the step's plane.  `MarginalCapacity` owns the device-side constants of one env object and launches the
 kernel on device pointers: torch tensors on the torch path, plain HIP allocations on the NumPy path.
 """
 from __future__ import annotations
@@ -12,17 +12,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 from . import _native
-from .sensing import _HipMemory, fold_columns, unserved
-
-
-def fold_capacity_columns(budget: dict) -> np.ndarray:
-    """cap_cols float32 [2, D] of d2d_marginal_capacity from link_budget_columns(): bw_mhz (1e-6 * Hz, in double, rounded once) and
-    sens_db."""
-    bw = np.asarray(budget['bw_hz'], dtype=np.float64)
-    cols = np.zeros((2, len(bw)), dtype=np.float32)
-    cols[0] = 1e-6 * bw
-    cols[1] = np.asarray(budget['sens_dbm'], dtype=np.float64)
-    return cols
+from .sensing import PairKernel, fold_capacity_columns, unserved      # fold_capacity_columns stays a name of this module too
 
 
 def refusal(sim, export_actions: bool) -> Optional[str]:
@@ -43,29 +33,12 @@ def refusal(sim, export_actions: bool) -> Optional[str]:
     }[kind]
 
 
-class MarginalCapacity:
+class MarginalCapacity(PairKernel):
     """The difference-reward kernel bound to one env object: constants uploaded once, one launch per call."""
 
     def __init__(self, sim, num_links: int, torch=None, device=None) -> None:
-        from .device import link_budget_columns
-        self.sim, self.torch, self.device = sim, torch, device
-        h = sim.handle
-        self.b, self.d, self.n, self.r = sim.num_envs, h.num_devices, int(num_links), int(sim.config.num_rbs)
-        if self.r > _native.MARGINAL_MAX_RBS:
-            raise ValueError(f'marginal_capacity() serves at most {_native.MARGINAL_MAX_RBS} RBs (num_rbs = {self.r})')
-        tx, rx = np.asarray(sim.link_tx, dtype=np.int32), np.asarray(sim.link_rx, dtype=np.int32)
-        if len(tx) != self.n or tx.min() < 0 or tx.max() >= self.d or rx.min() < 0 or rx.max() >= self.d:
-            raise ValueError('the link list does not match the env')
-        budget = link_budget_columns(sim._dev_list)
-        cols, self.law, self.pow_k = fold_columns(budget, sim.path_loss_table.law, tx)
-        cap_cols = fold_capacity_columns(budget)
+        super().__init__(sim, num_links, torch, device, api='marginal_capacity', max_rbs=_native.MARGINAL_MAX_RBS, capacity=True)
         self.own = None                              # the (difference, harm) pair this object owns, allocated by the first call without out=
-        if torch is not None:
-            self.tx, self.rx, self.cols, self.cap_cols = (torch.as_tensor(a, device=device) for a in (tx, rx, cols, cap_cols))
-            self.ptrs = tuple(t.data_ptr() for t in (self.tx, self.rx, self.cols, self.cap_cols))
-        else:
-            self.mem = _HipMemory()
-            self.ptrs = tuple(self.mem.upload(a) for a in (tx, rx, cols, cap_cols))
 
     def launch(self, pos_x: int, pos_y: int, rb: int, pwr: int, harm: int, diff: int, stream: int = 0) -> None:
         _native.marginal_capacity(pos_x, pos_y, rb, pwr, *self.ptrs, self.law, self.pow_k, self.b, self.d, self.n, self.r, harm, diff,
@@ -109,7 +82,3 @@ class MarginalCapacity:
         for dev, host in zip(self.own, res):
             self.mem.download(dev, host)              # synchronous on the null stream: behind the kernel
         return res
-
-    def close(self) -> None:
-        if self.torch is None:
-            self.mem.close()

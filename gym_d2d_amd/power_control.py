@@ -11,7 +11,7 @@ from typing import NamedTuple, Optional
 import numpy as np
 
 from . import _native
-from .sensing import fold_columns, unserved
+from .sensing import PairKernel, unserved
 
 
 class PowerControlResult(NamedTuple):
@@ -65,28 +65,18 @@ def encode_actions(rb, power_dbm, p_min, levels, first_agent: int = 0):
     return act.to(torch.int32)
 
 
-class PowerControl:
+class PowerControl(PairKernel):
     """The power-control kernel bound to one env object: constants uploaded once, one launch per call."""
 
     def __init__(self, sim, num_links: int, p_min, p_max, agent, torch, device) -> None:
-        from .device import link_budget_columns
-        self.sim, self.torch, self.device = sim, torch, device
-        h = sim.handle
-        self.b, self.d, self.n, self.r = sim.num_envs, h.num_devices, int(num_links), int(sim.config.num_rbs)
-        if self.r > _native.POWERCTL_MAX_RBS:
-            raise ValueError(f'power_control() serves at most {_native.POWERCTL_MAX_RBS} RBs (num_rbs = {self.r})')
-        tx, rx = np.asarray(sim.link_tx, dtype=np.int32), np.asarray(sim.link_rx, dtype=np.int32)
-        if len(tx) != self.n or tx.min() < 0 or tx.max() >= self.d or rx.min() < 0 or rx.max() >= self.d:
-            raise ValueError('the link list does not match the env')
-        cols, self.law, self.pow_k = fold_columns(link_budget_columns(sim._dev_list), sim.path_loss_table.law, tx)
+        super().__init__(sim, num_links, torch, device, api='power_control', max_rbs=_native.POWERCTL_MAX_RBS)
         p_min, p_max = np.asarray(p_min, dtype=np.int32), np.asarray(p_max, dtype=np.int32)
         self.agent = np.asarray(agent, dtype=bool)                   # links that have an action column: the only ones ever adjusted
         if not (p_min.shape == p_max.shape == self.agent.shape == (self.n,)) or (p_min > p_max).any() or np.abs(p_max).max() >= 4096:
             raise ValueError('the power bounds do not match the env')
         self.own = None                              # the four outputs this object owns, allocated by the first call without out=
-        self.tx, self.rx, self.cols, self.p_min, self.p_max = (torch.as_tensor(a, device=device) for a in (tx, rx, cols, p_min, p_max))
-        self.ptrs = tuple(t.data_ptr() for t in (self.tx, self.rx, self.cols))
-        self._target = self._adjustable = None       # (key, tensor) of the last call: a repeated target is not uploaded again
+        self.p_min, self.p_max = (torch.as_tensor(a, device=device) for a in (p_min, p_max))
+        self._target = None                          # (key, tensor) of the last call: a repeated target is not uploaded again
 
     def target(self, target_sinr_db, num_cues: int):
         """float32 [N] on the device from a scalar, {'cue': x, 'due': y} or [N] values (array or tensor)."""
@@ -113,18 +103,7 @@ class PowerControl:
 
     def adjustable(self, adjustable):
         """uint8 [N] on the device: the agent links (None), or those of them `adjustable` (bool [N], array or tensor) marks."""
-        torch = self.torch
-        if adjustable is None:
-            host = self.agent
-        else:
-            host = adjustable.cpu().numpy() if torch.is_tensor(adjustable) else np.asarray(adjustable)
-            if host.shape != (self.n,) or host.dtype != np.bool_:
-                raise ValueError(f'adjustable must be bool [{self.n}] (link) or None')
-            host = host & self.agent
-        key = host.tobytes()
-        if self._adjustable is None or self._adjustable[0] != key:
-            self._adjustable = (key, torch.as_tensor(host.astype(np.uint8), device=self.device))
-        return self._adjustable[1]
+        return self.agent_subset(adjustable, 'adjustable')
 
     def outputs(self, out):
         torch = self.torch
@@ -143,15 +122,6 @@ class PowerControl:
                              'memory')
         return tuple(out)
 
-    def env_mask(self, env_mask):
-        torch = self.torch
-        if env_mask is None:
-            return None
-        m = env_mask if torch.is_tensor(env_mask) else torch.as_tensor(np.asarray(env_mask))
-        if tuple(m.shape) != (self.b,) or m.dtype not in (torch.bool, torch.uint8):
-            raise ValueError(f'env_mask must be bool or uint8 [{self.b}] or None')
-        return m.to(device=self.device, dtype=torch.uint8).contiguous()
-
     def solve(self, t: dict, target, adjustable, max_iters: int, out, stream: int, env_mask=None) -> PowerControlResult:
         """target, adjustable: the tensors target() and adjustable() return."""
         if isinstance(max_iters, bool) or not isinstance(max_iters, (int, np.integer)) or max_iters < 1:
@@ -163,6 +133,3 @@ class PowerControl:
                               self.p_max.data_ptr(), adjustable.data_ptr(), int(max_iters), 0 if mask is None else mask.data_ptr(),
                               power.data_ptr(), sinr.data_ptr(), iters.data_ptr(), conv.data_ptr(), stream)
         return PowerControlResult(power, sinr, iters, conv)
-
-    def close(self) -> None:
-        pass

@@ -2,8 +2,9 @@
 
 `fold_columns` lowers the per-device link-budget and power-law columns to the float32 block the kernel reads, in double precision
 and by the rules the step's own records follow (csrc/d2d_capi.hip, refresh_tables), so that the sensed column of a link's own RB is
-the step's sinr_db.  `RbSensor` owns the device-side constants of one env object (link lists, columns) and launches the kernel on
-device pointers: torch tensors on the torch path, plain HIP allocations on the NumPy path.
+the step's sinr_db.  `PairKernel` is the opening every stateless pair kernel's class shares: it owns the device-side constants of one
+env object (link lists, columns) - torch tensors on the torch path, plain HIP allocations on the NumPy path.  `RbSensor` derives
+from it and launches the sensing kernel on device pointers.
 """
 from __future__ import annotations
 
@@ -45,6 +46,16 @@ def fold_columns(budget: dict, law: dict, link_tx: np.ndarray) -> Tuple[np.ndarr
     cols[4] = head
     cols[5] = hd - head.astype(np.float64)
     return cols, _native.SENSE_LAW_POWER, 0
+
+
+def fold_capacity_columns(budget: dict) -> np.ndarray:
+    """cap_cols float32 [2, D] of d2d_marginal_capacity from link_budget_columns(): bw_mhz (1e-6 * Hz, in double, rounded once) and
+    sens_db."""
+    bw = np.asarray(budget['bw_hz'], dtype=np.float64)
+    cols = np.zeros((2, len(bw)), dtype=np.float32)
+    cols[0] = 1e-6 * bw
+    cols[1] = np.asarray(budget['sens_dbm'], dtype=np.float64)
+    return cols
 
 
 def unserved(sim, export_actions: bool) -> Optional[Tuple[str, str]]:
@@ -119,27 +130,72 @@ class _HipMemory:
             self.free(p)
 
 
-class RbSensor:
-    """The sensing kernel bound to one env object: constants uploaded once, one launch per call."""
+class PairKernel:
+    """What the class of every stateless pair kernel opens with, bound to one env object: the env's shape (b, d, n and, with an RB
+    cap, r), the link lists and the folded columns, uploaded once - tx, rx, cols[, cap_cols] tensors on the torch path, plain HIP
+    allocations of `mem` on the NumPy path (torch None) - and their device pointers in `ptrs`, in the kernels' argument order."""
 
-    def __init__(self, sim, num_links: int, torch=None, device=None) -> None:
+    def __init__(self, sim, num_links: int, torch, device, *, api: Optional[str] = None, max_rbs: Optional[int] = None,
+                 capacity: bool = False) -> None:
         from .device import link_budget_columns
         self.sim, self.torch, self.device = sim, torch, device
-        h = sim.handle
-        self.b, self.d, self.n, self.r = sim.num_envs, h.num_devices, int(num_links), int(sim.config.num_rbs)
-        if self.r > _native.SENSE_MAX_RBS:
-            raise ValueError(f'sense() serves at most {_native.SENSE_MAX_RBS} RBs (num_rbs = {self.r})')
+        self.b, self.d, self.n = sim.num_envs, sim.handle.num_devices, int(num_links)
+        if max_rbs is not None:
+            self.r = int(sim.config.num_rbs)
+            if self.r > max_rbs:
+                raise ValueError(f'{api}() serves at most {max_rbs} RBs (num_rbs = {self.r})')
         tx, rx = np.asarray(sim.link_tx, dtype=np.int32), np.asarray(sim.link_rx, dtype=np.int32)
         if len(tx) != self.n or tx.min() < 0 or tx.max() >= self.d or rx.min() < 0 or rx.max() >= self.d:
             raise ValueError('the link list does not match the env')
-        cols, self.law, self.pow_k = fold_columns(link_budget_columns(sim._dev_list), sim.path_loss_table.law, tx)
-        self.own = None                              # the result block this object owns, allocated by the first call without out=
+        budget = link_budget_columns(sim._dev_list)
+        cols, self.law, self.pow_k = fold_columns(budget, sim.path_loss_table.law, tx)
+        host = {'tx': tx, 'rx': rx, 'cols': cols, **({'cap_cols': fold_capacity_columns(budget)} if capacity else {})}
         if torch is not None:
-            self.tx, self.rx, self.cols = (torch.as_tensor(a, device=device) for a in (tx, rx, cols))
-            self.ptrs = tuple(t.data_ptr() for t in (self.tx, self.rx, self.cols))
+            for name, a in host.items():
+                setattr(self, name, torch.as_tensor(a, device=device))
+            self.ptrs = tuple(getattr(self, name).data_ptr() for name in host)
         else:
             self.mem = _HipMemory()
-            self.ptrs = tuple(self.mem.upload(a) for a in (tx, rx, cols))
+            self.ptrs = tuple(self.mem.upload(a) for a in host.values())
+        self._subset = None                          # (key, tensor) of the last agent_subset(): a repeated mask is not uploaded again
+
+    def env_mask(self, env_mask):
+        """None, or `env_mask` (bool / uint8 [B], tensor or array) as a contiguous uint8 tensor on the device."""
+        torch = self.torch
+        if env_mask is None:
+            return None
+        m = env_mask if torch.is_tensor(env_mask) else torch.as_tensor(np.asarray(env_mask))
+        if tuple(m.shape) != (self.b,) or m.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f'env_mask must be bool or uint8 [{self.b}] or None')
+        return m.to(device=self.device, dtype=torch.uint8).contiguous()
+
+    def agent_subset(self, subset, name: str):
+        """uint8 [N] on the device: the links of `self.agent` (None), or those of them `subset` (bool [N], array or tensor) marks;
+        `name` is what a refusal calls the argument."""
+        torch = self.torch
+        if subset is None:
+            host = self.agent
+        else:
+            host = subset.cpu().numpy() if torch.is_tensor(subset) else np.asarray(subset)
+            if host.shape != (self.n,) or host.dtype != np.bool_:
+                raise ValueError(f'{name} must be bool [{self.n}] (link) or None')
+            host = host & self.agent
+        key = host.tobytes()
+        if self._subset is None or self._subset[0] != key:
+            self._subset = (key, torch.as_tensor(host.astype(np.uint8), device=self.device))
+        return self._subset[1]
+
+    def close(self) -> None:
+        if self.torch is None:
+            self.mem.close()
+
+
+class RbSensor(PairKernel):
+    """The sensing kernel bound to one env object: constants uploaded once, one launch per call."""
+
+    def __init__(self, sim, num_links: int, torch=None, device=None) -> None:
+        super().__init__(sim, num_links, torch, device, api='sense', max_rbs=_native.SENSE_MAX_RBS)
+        self.own = None                              # the result block this object owns, allocated by the first call without out=
 
     def launch(self, pos_x: int, pos_y: int, rb: int, pwr: int, what: int, out: int, stream: int = 0) -> None:
         _native.sense_rb(pos_x, pos_y, rb, pwr, *self.ptrs, self.law, self.pow_k, self.b, self.d, self.n, self.r, what, out, stream)
@@ -171,7 +227,3 @@ class RbSensor:
         res = out if out is not None else np.empty(shape, dtype=np.float32)
         self.mem.download(self.own, res)              # synchronous on the null stream: behind the kernel
         return res
-
-    def close(self) -> None:
-        if self.torch is None:
-            self.mem.close()

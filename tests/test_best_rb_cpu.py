@@ -36,8 +36,8 @@ def test_bestrb_library_exports_exactly_its_header():
     assert (_native.BESTRB_LAW_INV_SQUARE, _native.BESTRB_LAW_POWER, _native.BESTRB_LAW_POW_K, _native.BESTRB_MAX_RBS) == \
         (_native.SENSE_LAW_INV_SQUARE, _native.SENSE_LAW_POWER, _native.SENSE_LAW_POW_K, _native.SENSE_MAX_RBS)
     # built like the other side libraries; the step library keeps its 43 symbols
-    assert build.BESTRB_SOURCES == ['d2d_bestrb.hip'] and ROOT / 'include' / 'd2d_bestrb.h' in build.HEADERS
-    assert build.BESTRB_PATH == LIB_DIR / 'libd2d_bestrb.so'
+    assert build.LIBRARIES['bestrb'] == ['d2d_bestrb.hip'] and ROOT / 'include' / 'd2d_bestrb.h' in build.HEADERS
+    assert build.lib_path('bestrb') == LIB_DIR / 'libd2d_bestrb.so'
     assert len(_exports('libd2d_hip.so')) == 43 == len(_native.SIGNATURES)
     assert _exports('libd2d_sense.so') == set(_native.SENSE_SIGNATURES)
 

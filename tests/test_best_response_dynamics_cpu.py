@@ -38,8 +38,8 @@ def test_brdyn_library_exports_exactly_its_header():
     assert (_native.BRDYN_LAW_INV_SQUARE, _native.BRDYN_LAW_POWER, _native.BRDYN_LAW_POW_K) == \
         (_native.SENSE_LAW_INV_SQUARE, _native.SENSE_LAW_POWER, _native.SENSE_LAW_POW_K)
     # built like the other side libraries, and part of the source digest
-    assert build.BRDYN_SOURCES == ['d2d_brdyn.hip'] and ROOT / 'include' / 'd2d_brdyn.h' in build.HEADERS
-    assert build.BRDYN_PATH == LIB_DIR / 'libd2d_brdyn.so'
+    assert build.LIBRARIES['brdyn'] == ['d2d_brdyn.hip'] and ROOT / 'include' / 'd2d_brdyn.h' in build.HEADERS
+    assert build.lib_path('brdyn') == LIB_DIR / 'libd2d_brdyn.so'
 
 
 def test_entry_point_refuses_bad_arguments_without_a_launch():

@@ -40,8 +40,8 @@ def test_evaluate_library_exports_exactly_its_header():
     assert (_native.EVALUATE_LAW_INV_SQUARE, _native.EVALUATE_LAW_POWER, _native.EVALUATE_LAW_POW_K, _native.EVALUATE_MAX_RBS) == \
         (_native.SENSE_LAW_INV_SQUARE, _native.SENSE_LAW_POWER, _native.SENSE_LAW_POW_K, _native.SENSE_MAX_RBS)
     # built like the other side libraries; the step library keeps its 43 symbols
-    assert build.EVALUATE_SOURCES == ['d2d_evaluate.hip'] and ROOT / 'include' / 'd2d_evaluate.h' in build.HEADERS
-    assert build.EVALUATE_PATH == LIB_DIR / 'libd2d_evaluate.so' == _native.EVALUATE_PATH
+    assert build.LIBRARIES['evaluate'] == ['d2d_evaluate.hip'] and ROOT / 'include' / 'd2d_evaluate.h' in build.HEADERS
+    assert build.lib_path('evaluate') == LIB_DIR / 'libd2d_evaluate.so' == _native.side_path('evaluate')
     assert len(_exports('libd2d_hip.so')) == 43 == len(_native.SIGNATURES)
     assert _exports('libd2d_marginal.so') == set(_native.MARGINAL_SIGNATURES)
 

@@ -38,8 +38,8 @@ def test_powerctl_library_exports_exactly_its_header():
     assert (_native.POWERCTL_LAW_INV_SQUARE, _native.POWERCTL_LAW_POWER, _native.POWERCTL_LAW_POW_K) == \
         (_native.SENSE_LAW_INV_SQUARE, _native.SENSE_LAW_POWER, _native.SENSE_LAW_POW_K)
     # built like the other side libraries, and part of the source digest
-    assert build.POWERCTL_SOURCES == ['d2d_powerctl.hip'] and ROOT / 'include' / 'd2d_powerctl.h' in build.HEADERS
-    assert build.POWERCTL_PATH == LIB_DIR / 'libd2d_powerctl.so'
+    assert build.LIBRARIES['powerctl'] == ['d2d_powerctl.hip'] and ROOT / 'include' / 'd2d_powerctl.h' in build.HEADERS
+    assert build.lib_path('powerctl') == LIB_DIR / 'libd2d_powerctl.so'
 
 
 def test_entry_point_refuses_bad_arguments_without_a_launch():

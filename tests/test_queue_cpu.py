@@ -52,13 +52,21 @@ def test_step_library_still_exports_its_43():
     assert len({ln.split()[-1] for ln in nm.splitlines() if ' T d2d_' in ln}) == 43 == len(_native.SIGNATURES)
 
 
-def test_queue_library_is_registered_in_the_build():
+def test_queue_library_is_registered_in_the_build(tmp_path):
     from gym_d2d_amd import build
-    assert build.QUEUE_SOURCES == ['d2d_queue.hip'] and HEADER in build.HEADERS and build.QUEUE_PATH == LIB_DIR / 'libd2d_queue.so'
-    names = {p.name for p in build.HEADERS} | set(build.QUEUE_SOURCES)
+    assert build.LIBRARIES['queue'] == ['d2d_queue.hip'] and HEADER in build.HEADERS and build.lib_path('queue') == LIB_DIR / 'libd2d_queue.so'
+    names = {p.name for p in build.HEADERS} | set(build.LIBRARIES['queue'])
     assert {'d2d_queue.hip', 'd2d_queue.h'} <= names
-    src = Path(build.__file__).read_text()
-    assert src.count('QUEUE_SOURCES') >= 4 and 'QUEUE_PATH.exists()' in src      # compiled, linked, in the digest, in the up-to-date test
+    # compiled and linked (the build iterates LIBRARIES and nothing else), in the digest, in the up-to-date test
+    assert SOURCE in build.digest_files() and HEADER in build.digest_files()
+    digest = build.source_digest()
+    for stem in build.LIBRARIES:
+        if stem != 'probe':
+            build.lib_path(stem, tmp_path).touch()
+    (tmp_path / 'libd2d_hip.sha256').write_text(digest)
+    assert build.up_to_date(digest, tmp_path) and not build.up_to_date('0' * 64, tmp_path)
+    build.lib_path('queue', tmp_path).unlink()
+    assert not build.up_to_date(digest, tmp_path)
 
 
 def test_queue_entry_point_refuses_bad_arguments_without_a_launch():
