@@ -22,7 +22,7 @@ from typing import Optional
 
 import numpy as np
 
-from .. import _native, best_response, best_response_dynamics, graph, marginal, power_control, sensing
+from .. import _native, assignment, best_response, best_response_dynamics, graph, marginal, power_control, sensing
 from .. import evaluate as evaluate_mod
 from .. import mobility as mobility_mod
 from .. import queues as queues_mod
@@ -278,6 +278,8 @@ class VecD2DEnv:
         self._brdyn = None
         # what-if evaluation of candidate joint actions (evaluate()): likewise nothing unless it is called
         self._evaluate = None
+        # optimal one-to-one RB matching (assign_rbs()): likewise nothing unless it is called
+        self._assign = None
 
     def _setup_autoreset(self) -> None:
         """Refuse what a device-side per-env reset cannot serve, then allocate the per-env bookkeeping: pending / episode are bound
@@ -972,6 +974,71 @@ class VecD2DEnv:
         rb, pwr = evaluate_mod.decode_actions(actions, self._action_levels, *fixed)
         return k.planes(self._t, rb, pwr, planes, None, self._stream_ptr)
 
+    # ------------------------------------------------------------------ optimal one-to-one RB matching
+    def _assignment_kernel(self):
+        return self._kernel('_assign', assignment, assignment.Assignment,
+                            lambda: (self._agent_links(), np.arange(self.num_links) >= self.num_links - self.num_due_pairs))
+
+    def assignment_weights(self, movable=None, allowed=None, objective: str = 'total', harm: bool = False, out=None):
+        """What every movable link is worth on every RB, with the background as the last step left it: (weights float32 [B, M, R],
+        links int32 [M]), and harm float32 [B, M, R] behind them if harm=True.
+
+        movable: bool [N] (tensor or array), the same for every env; None: the DUE-pair links.  Row a is the a-th movable link in
+        ascending link index, links[a].  Every other link is background: it stays on its current RB and power (an rb outside
+        [0, R) is on no RB).  The movable links are taken off the air: their current RB plays no part, their current power is the
+        power they are placed with.  own[b, a, r] is link a's capacity (Mbps, the step's definition) alone with the background
+        members of r; harm[b, a, r] what those members lose to it, 0.0 exactly on an RB without them, a victim pushed under its
+        sensitivity losing its whole capacity.  weights = own - harm under objective='total', own under objective='own' (bit for
+        bit evaluate()'s capacity_mbps of link a for the candidate that puts a on r and every other movable link on rb -1);
+        -inf where allowed (bool [N, R], as best_rb() takes it) forbids.  Movable links on DISTINCT RBs do not interfere with each
+        other, so the total capacity of a one-to-one placement is evaluate(background) + the sum of its 'total' weights.
+
+        One kernel launch (csrc/d2d_assign.hip).  The env is left untouched.  Valid after reset() and after every step(), autoreset
+        and mobility included, as sense() is.  Torch path only: enqueued on torch's current stream, nothing is synchronised; the
+        tensors the env owns (4 B M R bytes each, rewritten by every call), or `out`: one contiguous float32 [B, M, R] tensor, or
+        (weights, harm) with harm=True.  ValueError for a `movable` that marks a link without an action column, and for what
+        evaluate() refuses."""
+        k = self._assignment_kernel()
+        self._follow_torch_stream()
+        return k.weights(self._t, movable, allowed, objective, harm, out, self._stream_ptr)
+
+    def solve_assignment(self, weights, out=None):
+        """The maximum-weight one-to-one matching of ANY float32 [B, M, R] tensor on the env's device, M <= R: (col int32 [B, M],
+        value_mbps float32 [B], feasible uint8 [B]).  col[b, a] is the column row a takes, value_mbps[b] the matched weights summed
+        in double in ascending row.  Entries that are not finite are never matched; an env without a complete matching is
+        infeasible - feasible 0, every col -1, value 0.0 - and does not disturb the others.  One kernel launch (csrc/d2d_assign.hip):
+        the shortest-augmenting-path method in double, one workgroup per env.  The env's own tensors, rewritten by every call, or
+        `out` = (col, value_mbps, feasible).  M > R is a ValueError."""
+        k = self._assignment_kernel()
+        self._follow_torch_stream()
+        return k.solve(weights, out, self._stream_ptr)
+
+    def assign_rbs(self, movable=None, allowed=None, objective: str = 'total', out=None):
+        """The one-to-one placement of the movable links that maximises the TOTAL capacity of the env (objective='total'; 'own':
+        the movable links' own capacities), the background staying where it is: (rb int32 [B, N], value_mbps float32 [B],
+        feasible uint8 [B]), a tuple with those names.
+
+        rb is the current plane with every movable link on its matched RB, all distinct; an infeasible env (allowed leaves some
+        link no RB of its own) keeps its row, with value 0.0.  Because the weights separate exactly over one-to-one placements
+        (assignment_weights()), evaluate(rb)['total_mbps'] = evaluate(background) + value_mbps and no other such placement gives
+        more: a certificate, not a heuristic.  Two kernel launches, assignment_weights() and solve_assignment(), and the scatter
+        of the columns; the weights block, 4 B M R bytes, is owned by the env.  movable, allowed, validity and refusals as
+        assignment_weights(); more movable links than RBs is a ValueError.  `out` = (rb, value_mbps, feasible)."""
+        k = self._assignment_kernel()
+        self._follow_torch_stream()
+        return k.assign(self._t, movable, allowed, objective, out, self._stream_ptr)
+
+    def assign_rbs_actions(self, movable=None, allowed=None, objective: str = 'total'):
+        """assign_rbs() as an action tensor, int32 [B, num_agents], ready for step(): every agent link on its RB of assign_rbs() at
+        its current power level, encoded rb * power levels + level.  Links on fixed actions (cue_actions='traffic') have no
+        column.  Composes with power_control_actions() the way best_response_dynamics_actions() does."""
+        rb = self.assign_rbs(movable, allowed, objective)[0]
+        if self._action_levels is None:
+            p = self.num_pwr_actions
+            levels = ([p[self._cue_kind]] * self.num_cues if self.cue_actions == 'agent' else []) + [p['due']] * self.num_due_pairs
+            self._action_levels = torch.as_tensor(np.asarray(levels, dtype=np.int32), device=self.device)
+        return best_response_dynamics.encode_actions(rb, self._t['pwr'], self._action_levels, self.num_links - self.num_agents)
+
     def _observe(self, view):
         extra = {}
         if self._senses:
@@ -1044,4 +1111,7 @@ class VecD2DEnv:
         if self._evaluate is not None:
             self._evaluate.close()
             self._evaluate = None
+        if self._assign is not None:
+            self._assign.close()
+            self._assign = None
         self.simulator.handle.close()
