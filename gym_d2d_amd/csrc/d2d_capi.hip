@@ -975,14 +975,14 @@ int d2d_set_tuning(d2d_handle* h, int32_t key, int32_t value) try {
 #if !(defined(D2D_DIAG) && D2D_DIAG)
     // the A/B shapes and the ablation switch of d2d_hip_diag.h exist in diagnostic builds only
     const bool diag_key = key == D2D_TUNE_OBS_VARIANT || key == D2D_TUNE_OBS_STAGGER || key == D2D_TUNE_STEP_ABLATE;
-    const bool diag_value = (key == D2D_TUNE_OBS_NONTEMPORAL && value > 1) || (key == D2D_TUNE_STEP_WALK && value == 1);
+    const bool diag_value = (key == D2D_TUNE_OBS_NONTEMPORAL && value > 1 && value != 5) || (key == D2D_TUNE_STEP_WALK && value == 1);
     if ((diag_key && value != 0) || diag_value)
         return fail(D2D_ERR_UNSUPPORTED, "this tuning key / value needs the diagnostic build (D2D_BUILD_DIAG=1 python -m gym_d2d_amd.build; include/d2d_hip_diag.h)");
 #endif
     switch (key) {
         case D2D_TUNE_OBS_ROWS_PER_WG: h->tune_obs.rows = value; break;
         case D2D_TUNE_OBS_NONTEMPORAL:
-            if (value < 0 || value > 5) return fail(D2D_ERR_INVALID, "obs store policy must be in [0, 5]");
+            if (value < -1 || value > 5) return fail(D2D_ERR_INVALID, "obs store policy must be in [0, 5], or -1 for the planner's choice");
             h->tune_obs.nt = value;
             break;
         case D2D_TUNE_OBS_XCD_REMAP: h->tune_obs.xcd = value < 0 ? 0 : value; break;

@@ -5,7 +5,9 @@
 //
 // This is the HBM-dominant kernel of the path: 24*N bytes written per agent-step against 24 read.  It is a
 // pure streaming store, so the design is about the store side only:
-//   * T[b] (6N floats) is staged once per workgroup in LDS;
+//   * T[b] (6N floats) is staged once per workgroup in LDS - in the flat kernels in ONE round trip: 16-byte loads, all issued before
+//     the first wait, the kernel arguments read in one scalar trip and every piece's index arithmetic done under the loads
+//     (round 7: what a workgroup does before its first store decides which store policy is the fastest, see plan_obs);
 //   * the output block of an env is contiguous ([N][6N] floats), so a workgroup walks a contiguous slab of it
 //     with one 16-byte store per lane per iteration - every wave-instruction writes 1 KiB of consecutive
 //     addresses (full 128-B lines, no partial-line read-modify-write); since round 4 the slab is FLAT (two
@@ -16,7 +18,8 @@
 //     straddles the shift boundary, and the lanes on either side of a row end, hit the same banks - SQ_LDS_BANK_CONFLICT /
 //     SQ_LDS_IDX_ACTIVE = 0.37, profiles/r5_pmc_stress_linear.json.  It costs nothing measurable: SQ_WAIT_INST_LDS is 0.04 %
 //     of the wave cycles of a kernel that runs at 0.977 of the box's best store-only kernel.)
-//   * stores are nontemporal (written once, never re-read by this kernel);
+//   * stores are nontemporal (written once, never re-read by this kernel), in the flat kernels also written through (sc1 nt) at the
+//     default shape: store16's policy, chosen per shape by plan_obs;
 //   * blockIdx is remapped so the chunks of one env share an XCD (its T stays in that XCD's L2).
 #include "d2d_internal.h"
 #include "d2d_store.h"
@@ -27,6 +30,41 @@ namespace d2d {
 __device__ __forceinline__ unsigned src_col(unsigned f, unsigned i) {
     const unsigned head = 6u * i;
     return f < 6u ? head + f : (f < head + 6u ? f - 6u : f);
+}
+
+// Stage T[env] in LDS in ONE round trip (the flat kernels when 6N % 4 == 0: table + env * 6N is 16-byte aligned and T is n4 = 6N / 4
+// whole float4).  A thread issues all the loads of a group of three pieces (three cover N = 2048 with 1024 threads; smaller
+// blocks loop) before it waits for the first, then writes them with ds_write_b128.  Whether the workgroup has a piece at all is a
+// scalar branch; within a piece the load address is clamped into T instead of predicated and only the LDS write is guarded.  The
+// 8-byte loop this replaces waited for each piece before it asked for the next: at N = 512 (1536 float2, 1024 threads) half the
+// waves made two dependent trips.
+struct StagedPieces { f32x4 r[3]; };
+__device__ __forceinline__ void stage_load16(StagedPieces& s, const float* table_env, unsigned n4, unsigned first, unsigned tid, unsigned T) {
+    const f32x4* src = reinterpret_cast<const f32x4*>(table_env);
+#pragma unroll
+    for (unsigned j = 0; j < 3u; ++j)
+        if (first + j * T < n4) s.r[j] = src[min(first + j * T + tid, n4 - 1u)];
+}
+__device__ __forceinline__ void stage_write16(float* t_flat, const StagedPieces& s, unsigned n4, unsigned first, unsigned tid, unsigned T) {
+    f32x4* dst = reinterpret_cast<f32x4*>(t_flat);
+#pragma unroll
+    for (unsigned j = 0; j < 3u; ++j)
+        if (first + j * T + tid < n4) dst[first + j * T + tid] = s.r[j];
+}
+// the pieces behind the first three: blocks smaller than 6N / 12 threads only
+__device__ __forceinline__ void stage_rest16(float* t_flat, const float* table_env, unsigned n4, unsigned tid, unsigned T) {
+    for (unsigned first = 3u * T; first < n4; first += 3u * T) {
+        StagedPieces s;
+        stage_load16(s, table_env, n4, first, tid, T);
+        stage_write16(t_flat, s, n4, first, tid, T);
+    }
+}
+
+// src_col as LDS byte offset, written with selects only (no divergent branch in the address arithmetic ahead of the barrier)
+__device__ __forceinline__ unsigned src_byte(unsigned f, unsigned i) {
+    const unsigned head = 6u * i;
+    const unsigned behind = f - (f < head + 6u ? 6u : 0u);
+    return (f < 6u ? head + f : behind) * 4u;
 }
 
 template <int VEC, int NT>           // NT: the store policy of store16 (0 plain, 1 nt, 2 .. 5 scope variants; VEC == 2: 0 / 1 only)
@@ -116,46 +154,83 @@ __global__ __launch_bounds__(1024) void obs_expand_kernel(const ObsArgs a) {
 // of T threads writes `flat_passes` x T consecutive float4 of it, whatever the row length - the shape of the fastest fill of the
 // probe family (1024 threads x 2 passes = 32 KB per workgroup, 16 KB contiguous per pass), where the row-aligned default writes
 // 2 x 12 KB.  A lane's (row, column) differs per pass: two multiply-shift divisions per lane and launch.
+
+// (env, chunk) of a flat workgroup and the kernel arguments its pieces need, all in SGPRs before the first table load goes out: the
+// arguments are read in ONE scalar round trip (the compiler otherwise fetches half of them behind the env computation - a second
+// dependent trip ahead of the staging loads) and the division by `chunks` is a multiply-shift wherever plan_obs found it exact.
+struct FlatHead {
+    unsigned env, chunk, T, q_per_row, stagger;
+    unsigned long long q_magic;
+    const float* table;
+    float* obs;
+};
+__device__ __forceinline__ FlatHead flat_head(const ObsArgs& a) {
+    FlatHead h;
+    h.T = blockDim.x; h.q_per_row = a.q_per_row; h.stagger = (unsigned)a.stagger; h.q_magic = a.q_magic; h.table = a.table; h.obs = a.obs;
+    unsigned chunks = (unsigned)a.chunks, remap = (unsigned)a.xcd_remap;
+    unsigned long long magic = a.chunk_magic;
+    asm volatile("" : "+s"(h.T), "+s"(h.q_per_row), "+s"(h.stagger), "+s"(h.q_magic), "+s"(h.table), "+s"(h.obs), "+s"(chunks), "+s"(remap), "+s"(magic));
+    // blocks b, b + 8, b + 16, ... share an XCD (round-robin dispatch): with xcd_remap they are the chunks of one env
+    const unsigned bid = blockIdx.x, rest = remap ? bid >> 3 : bid;
+    const unsigned e = magic ? (unsigned)(((unsigned long long)rest * magic) >> 40) : rest / chunks;
+    h.chunk = rest - e * chunks;
+    h.env = remap ? e * 8u + (bid & 7u) : e;
+    return h;
+}
+
+// What a workgroup does before its first store decides how long it lives, and under the write-through policies that, not HBM, is
+// what bounds the kernel: the staging loads go out first; every piece's (row, column) and LDS addresses - which
+// depend on the thread, the block and the arguments only - are worked out while the loads are under way; behind the barrier only
+// the LDS reads, one wait and the stores are left.  PASSES is the workgroup's piece count as a constant, so the reads need no guard.
+template <int NT, int PASSES>
+__device__ __forceinline__ void obs_flat_pieces(const ObsArgs& a, const FlatHead& h, float* t_flat) {
+    const unsigned N = a.N, tid = threadIdx.x, T = h.T, env = h.env, chunk = h.chunk;
+    const unsigned row_floats = 6u * N, q_per_row = h.q_per_row, total = N * q_per_row, n4 = row_floats / 4u;
+    const float* table_env = h.table + (size_t)env * row_floats;
+    StagedPieces st;
+    stage_load16(st, table_env, n4, 0u, tid, T);
+    const unsigned base = chunk * (unsigned)PASSES * T;
+    unsigned idx[PASSES], b0[PASSES], b1[PASSES];
+#pragma unroll
+    for (int p = 0; p < PASSES; ++p) {
+        idx[p] = base + (unsigned)p * T + tid;
+        const unsigned at = min(idx[p], total - 1u);                      // (a piece past the env's end reads the last one and stores nothing)
+        const unsigned i = (unsigned)(((unsigned long long)at * h.q_magic) >> 40), q = at - i * q_per_row;
+        const unsigned f = q * 4u;
+        b0[p] = src_byte(f, i); b1[p] = src_byte(f + 2u, i);
+        asm volatile("" : "+v"(b0[p]), "+v"(b1[p]));                      // computed HERE: the compiler otherwise sinks it to its use, behind the barrier
+    }
+    f32x4* out = reinterpret_cast<f32x4*>(h.obs + (size_t)env * N * row_floats);
+    stage_write16(t_flat, st, n4, 0u, tid, T);
+    stage_rest16(t_flat, table_env, n4, tid, T);
+    __builtin_amdgcn_sched_barrier(0);                                    // none of the above sinks behind the barrier
+    __syncthreads();
+    if (h.stagger > 0) {                                                  // D2D_TUNE_OBS_STAGGER (A/B)
+        const int n = (int)((tid >> 6) * h.stagger);
+        for (int k = 0; k < n; ++k) __builtin_amdgcn_s_sleep(1);
+    }
+    const char* lds = reinterpret_cast<const char*>(t_flat);
+    f32x2 lo[PASSES], hi[PASSES];
+#pragma unroll
+    for (int p = 0; p < PASSES; ++p) {
+        lo[p] = *reinterpret_cast<const f32x2*>(lds + b0[p]);
+        hi[p] = *reinterpret_cast<const f32x2*>(lds + b1[p]);
+    }
+#pragma unroll
+    for (int p = 0; p < PASSES; ++p)
+        if (idx[p] < total) store16<NT>(out + idx[p], f32x4{lo[p].x, lo[p].y, hi[p].x, hi[p].y});
+}
+
 template <int NT>
 __global__ __launch_bounds__(1024) void obs_expand_flat_kernel(const ObsArgs a) {
     extern __shared__ __align__(16) float t_flat[];          // [6N]
-    const unsigned N = a.N, tid = threadIdx.x, T = blockDim.x;
-    unsigned env, chunk;
-    if (a.xcd_remap) {
-        const unsigned bid = blockIdx.x, lane8 = bid & 7u, rest = bid >> 3;
-        chunk = rest % a.chunks; env = (rest / a.chunks) * 8u + lane8;
-    } else {
-        env = blockIdx.x / a.chunks; chunk = blockIdx.x % a.chunks;
+    const FlatHead h = flat_head(a);
+    switch (a.rows_per_wg) {                                              // rows_per_wg = pieces per workgroup here (1 .. 4)
+        case 1: obs_flat_pieces<NT, 1>(a, h, t_flat); break;
+        case 2: obs_flat_pieces<NT, 2>(a, h, t_flat); break;
+        case 3: obs_flat_pieces<NT, 3>(a, h, t_flat); break;
+        default: obs_flat_pieces<NT, 4>(a, h, t_flat); break;
     }
-    const unsigned row_floats = 6u * N, q_per_row = a.q_per_row, total = N * q_per_row;
-    {
-        const f32x2* src = reinterpret_cast<const f32x2*>(a.table + (size_t)env * row_floats);
-        f32x2* dst = reinterpret_cast<f32x2*>(t_flat);
-        for (unsigned k = tid; k < row_floats / 2; k += T) dst[k] = src[k];
-    }
-    __syncthreads();
-    if (a.stagger > 0) {                                                  // D2D_TUNE_OBS_STAGGER (A/B)
-        const int n = (int)(tid >> 6) * a.stagger;
-        for (int k = 0; k < n; ++k) __builtin_amdgcn_s_sleep(1);
-    }
-    const f32x2* t2 = reinterpret_cast<const f32x2*>(t_flat);
-    f32x4* out = reinterpret_cast<f32x4*>(a.obs + (size_t)env * N * row_floats);
-    const unsigned base = chunk * (unsigned)a.rows_per_wg * T;            // rows_per_wg = passes per workgroup here
-    f32x4 v[4];
-    unsigned idx[4];
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        idx[p] = base + (unsigned)p * T + tid;
-        if (p < a.rows_per_wg && idx[p] < total) {
-            const unsigned i = (unsigned)(((unsigned long long)idx[p] * a.q_magic) >> 40), q = idx[p] - i * q_per_row;
-            const unsigned f = q * 4u;
-            const f32x2 lo = t2[src_col(f, i) >> 1], hi = t2[src_col(f + 2u, i) >> 1];
-            v[p] = f32x4{lo.x, lo.y, hi.x, hi.y};
-        }
-    }
-#pragma unroll
-    for (int p = 0; p < 4; ++p)
-        if (p < a.rows_per_wg && idx[p] < total) store16<NT>(out + idx[p], v[p]);
 }
 
 // The same expansion written as float64 (d2d_set_obs_dtype: the reference's observation dtype, obs_fn.py:47,51 builds float64
@@ -206,44 +281,59 @@ __global__ __launch_bounds__(1024) void obs_expand_f64_kernel(const ObsArgs a) {
 // writes `passes` x 1024 consecutive pieces (16 KB per pass) whatever the row length, every lane's (row, column) found once per
 // piece by multiply-shift, all LDS reads issued ahead of the stores.  (The row-aligned kernel above walked a row with a strided
 // loop and a three-way source select per element: 6.6 TB/s where this shape's float32 twin does 7.1 - 7.2, profiles/r4_obs_float64.jsonl.)
-template <int NT>
-__global__ __launch_bounds__(1024) void obs_expand_flat_f64_kernel(const ObsArgs a) {
-    extern __shared__ __align__(16) float t_flat[];          // [6N]
+template <int NT, int PASSES>        // the float64 twin of obs_flat_pieces: one ds_read_b64 per piece, store16 on the bit pattern of the double2
+__device__ __forceinline__ void obs_flat_f64_pieces(const ObsArgs& a, const FlatHead& h, float* t_flat) {
     typedef double f64x2 __attribute__((ext_vector_type(2)));
-    const unsigned N = a.N, tid = threadIdx.x, T = blockDim.x;
-    unsigned env, chunk;
-    if (a.xcd_remap) {
-        const unsigned bid = blockIdx.x, lane8 = bid & 7u, rest = bid >> 3;
-        chunk = rest % a.chunks; env = (rest / a.chunks) * 8u + lane8;
-    } else {
-        env = blockIdx.x / a.chunks; chunk = blockIdx.x % a.chunks;
+    const unsigned N = a.N, tid = threadIdx.x, T = h.T, env = h.env, chunk = h.chunk;
+    const unsigned row_floats = 6u * N, q_per_row = h.q_per_row, total = N * q_per_row;      // q_per_row = 3N double2 per row
+    const float* table_env = h.table + (size_t)env * row_floats;
+    const bool wide = (row_floats & 3u) == 0u;                            // even N: T[env] is 16-byte aligned, whole float4
+    const unsigned n4 = row_floats / 4u;
+    StagedPieces st;
+    if (wide) stage_load16(st, table_env, n4, 0u, tid, T);
+    const unsigned base = chunk * (unsigned)PASSES * T;
+    unsigned idx[PASSES], b0[PASSES];
+#pragma unroll
+    for (int p = 0; p < PASSES; ++p) {
+        idx[p] = base + (unsigned)p * T + tid;
+        const unsigned at = min(idx[p], total - 1u);
+        const unsigned i = (unsigned)(((unsigned long long)at * h.q_magic) >> 40), c = at - i * q_per_row;
+        b0[p] = src_byte(2u * c, i);
+        asm volatile("" : "+v"(b0[p]));                                   // computed here, not sunk behind the barrier
     }
-    const unsigned row_floats = 6u * N, q_per_row = a.q_per_row, total = N * q_per_row;      // q_per_row = 3N double2 per row
-    {
-        const f32x2* src = reinterpret_cast<const f32x2*>(a.table + (size_t)env * row_floats);
+    f32x4* out = reinterpret_cast<f32x4*>(reinterpret_cast<double*>(h.obs) + (size_t)env * N * row_floats);
+    if (wide) {
+        stage_write16(t_flat, st, n4, 0u, tid, T);
+        stage_rest16(t_flat, table_env, n4, tid, T);
+    } else {                                                              // odd N: 8-byte granules, as before
+        const f32x2* src = reinterpret_cast<const f32x2*>(table_env);
         f32x2* dst = reinterpret_cast<f32x2*>(t_flat);
         for (unsigned k = tid; k < row_floats / 2; k += T) dst[k] = src[k];
     }
+    __builtin_amdgcn_sched_barrier(0);
     __syncthreads();
-    const f32x2* t2 = reinterpret_cast<const f32x2*>(t_flat);
-    f64x2* out = reinterpret_cast<f64x2*>(reinterpret_cast<double*>(a.obs) + (size_t)env * N * row_floats);
-    const unsigned base = chunk * (unsigned)a.rows_per_wg * T;            // rows_per_wg = passes per workgroup here
-    f32x2 v[4];
-    unsigned idx[4];
+    const char* lds = reinterpret_cast<const char*>(t_flat);
+    f32x2 v[PASSES];
 #pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        idx[p] = base + (unsigned)p * T + tid;
-        if (p < a.rows_per_wg && idx[p] < total) {
-            const unsigned i = (unsigned)(((unsigned long long)idx[p] * a.q_magic) >> 40), c = idx[p] - i * q_per_row;
-            v[p] = t2[src_col(2u * c, i) >> 1];
-        }
-    }
+    for (int p = 0; p < PASSES; ++p) v[p] = *reinterpret_cast<const f32x2*>(lds + b0[p]);
 #pragma unroll
-    for (int p = 0; p < 4; ++p)
-        if (p < a.rows_per_wg && idx[p] < total) {
+    for (int p = 0; p < PASSES; ++p)
+        if (idx[p] < total) {
             const f64x2 d = {(double)v[p].x, (double)v[p].y};
-            if (NT) __builtin_nontemporal_store(d, out + idx[p]); else out[idx[p]] = d;
+            store16<NT>(out + idx[p], __builtin_bit_cast(f32x4, d));
         }
+}
+
+template <int NT>
+__global__ __launch_bounds__(1024) void obs_expand_flat_f64_kernel(const ObsArgs a) {
+    extern __shared__ __align__(16) float t_flat[];          // [6N]
+    const FlatHead h = flat_head(a);
+    switch (a.rows_per_wg) {
+        case 1: obs_flat_f64_pieces<NT, 1>(a, h, t_flat); break;
+        case 2: obs_flat_f64_pieces<NT, 2>(a, h, t_flat); break;
+        case 3: obs_flat_f64_pieces<NT, 3>(a, h, t_flat); break;
+        default: obs_flat_f64_pieces<NT, 4>(a, h, t_flat); break;
+    }
 }
 
 // Variant without LDS staging or barrier (float4 rows only): every thread fetches its two source float2 straight
@@ -285,8 +375,14 @@ hipError_t launch_obs_expand(const ObsArgs& a, hipStream_t stream) {
     dim3 grid((unsigned)a.B * (unsigned)a.chunks), block(a.block > 0 ? a.block : 256);
     if (a.out_f64) {
         if (a.variant == 2 && a.rows_per_wg <= 4) {            // flat slabs (the default)
-            if (a.nontemporal) hipLaunchKernelGGL((obs_expand_flat_f64_kernel<1>), grid, block, lds, stream, a);
-            else hipLaunchKernelGGL((obs_expand_flat_f64_kernel<0>), grid, block, lds, stream, a);
+            switch (a.nontemporal) {
+                case 0: hipLaunchKernelGGL((obs_expand_flat_f64_kernel<0>), grid, block, lds, stream, a); break;
+                case 2: hipLaunchKernelGGL((obs_expand_flat_f64_kernel<2>), grid, block, lds, stream, a); break;
+                case 3: hipLaunchKernelGGL((obs_expand_flat_f64_kernel<3>), grid, block, lds, stream, a); break;
+                case 4: hipLaunchKernelGGL((obs_expand_flat_f64_kernel<4>), grid, block, lds, stream, a); break;
+                case 5: hipLaunchKernelGGL((obs_expand_flat_f64_kernel<5>), grid, block, lds, stream, a); break;
+                default: hipLaunchKernelGGL((obs_expand_flat_f64_kernel<1>), grid, block, lds, stream, a); break;
+            }
         } else if (a.nontemporal) hipLaunchKernelGGL(obs_expand_f64_kernel<true>, grid, block, lds, stream, a);
         else hipLaunchKernelGGL(obs_expand_f64_kernel<false>, grid, block, lds, stream, a);
         return hipGetLastError();

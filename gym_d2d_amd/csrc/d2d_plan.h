@@ -24,7 +24,7 @@ struct StepTuning {
 
 // the D2D_TUNE_OBS_* keys: the LinearObs expansion kernel's shape
 struct ObsTuning {
-    int rows = 0, nt = 1, xcd = 1, block = 0, variant = 0, stagger = 0;
+    int rows = 0, nt = -1, xcd = 1, block = 0, variant = 0, stagger = 0;       // nt: the store policy of store16, -1 = plan_obs chooses
 };
 
 // everything the choice of the step kernel reads, as plain values

@@ -211,6 +211,31 @@ int plan_step(const StepInputs& in, StepPlan* out, const char** error) {
     return D2D_OK;
 }
 
+namespace {
+
+// The store policy of the obs stream where nobody set one (ObsTuning::nt < 0).  `one_trip`: a flat kernel that stages T[env] with
+// 16-byte loads in one round trip (6N % 4 == 0).  Under the write-through policy (5, sc1 nt) a store is acknowledged by memory,
+// not by L2, so the kernel is bound by how long a workgroup lives and not by HBM.  With the 8-byte staging loop of rounds 1-6
+// (two dependent L2 trips for half the waves, the kernel arguments fetched in two scalar trips around a division, the index
+// arithmetic behind the barrier) waves lived 1324 quad-cycles under 5 against 1114 under 1 and the kernel lost 10 %
+// (profiles/r7_pmc_obs_wave_lifetime.json).  With everything ahead of the first store shortened, 5 is the faster one at two
+// pieces per workgroup (profiles/r7_obs_staging_sweep.jsonl, one box: float32 1024 x 2 3756 -> 3581 us, float64 7417 -> 7131)
+// and mixed at three and four, where more bytes in flight per CU hide a longer life (ahead at 1024 x 3 and x 4 in float32, behind
+// at 512 x 3, 512 x 4 and float64 1024 x 3): those shapes are set by hand and keep 1 unless the policy is set too.  (Rounds
+// 4-6 gave "its table rows are re-read through the same L2" as the reason for the loss; the probe's staged fill re-reads a row of
+// the same size through the same L2 and GAINS from 5.)  The row-aligned kernels and the 8-byte staging of odd N keep 1.
+int obs_store_policy(int nt, bool one_trip, int pieces) { return nt >= 0 ? nt : (one_trip && pieces <= 2 ? 5 : 1); }
+
+// ObsArgs::chunk_magic of a flat launch: block / chunks (block / 8 / chunks with the XCD grouping) as a multiply-shift by
+// M = ceil(2^40 / chunks), exact while n x chunks < 2^40 (the error n (M chunks - 2^40) / (chunks 2^40) stays below 1 / chunks) and
+// n < 2^24 keeps n M inside 64 bits; a grid beyond that divides (0).
+unsigned long long obs_chunk_magic(const ObsArgs& o) {
+    const unsigned long long grid = (unsigned long long)o.B * (unsigned)o.chunks, n = o.xcd_remap ? grid / 8 : grid, d = (unsigned)o.chunks;
+    return n < (1ull << 24) && n * d < (1ull << 40) ? ((1ull << 40) + d - 1) / d : 0;
+}
+
+}  // namespace
+
 // LinearObs expansion launch geometry for a [B, N, 6] table (shared by the step path and d2d_expand_table).
 ObsArgs plan_obs(const ObsTuning& t, int B, int N, int out_f64) {
     ObsArgs o;
@@ -222,6 +247,8 @@ ObsArgs plan_obs(const ObsTuning& t, int B, int N, int out_f64) {
         o.vec = 2;
         o.q_per_row = (unsigned)(3 * N);
         o.q_magic = ((1ull << 40) + o.q_per_row - 1) / o.q_per_row;
+        // (1024 x 2 as in float32: with the single-trip staging still ahead of 512 x 2, 7131 against 7181 us, r7_obs_staging_sweep.jsonl)
+        const bool one_trip = (6 * N) % 4 == 0;
         o.block = t.block > 0 ? t.block : 1024;
         int passes = t.rows > 0 ? t.rows : 2;
         if (passes > 4) passes = 4;
@@ -229,8 +256,9 @@ ObsArgs plan_obs(const ObsTuning& t, int B, int N, int out_f64) {
         const unsigned total = (unsigned)N * o.q_per_row, slab = (unsigned)passes * (unsigned)o.block;
         o.chunks = (int)((total + slab - 1) / slab);
         o.xcd_remap = (t.xcd > 0 && B % 8 == 0) ? 1 : 0;
-        o.nontemporal = t.nt;
+        o.nontemporal = obs_store_policy(t.nt, one_trip, passes);
         o.variant = 2;
+        o.chunk_magic = obs_chunk_magic(o);
         return o;
     }
     o.vec = (6 * N) % 4 == 0 ? 4 : 2;
@@ -239,8 +267,8 @@ ObsArgs plan_obs(const ObsTuning& t, int B, int N, int out_f64) {
     // Launch geometry.  Round 4 (tools/probes/obs_policy_geometry.py, MI355X, N = 512): FLAT slabs - the env's [N][6N] block as one
     // flat array of float4, a 1024-thread workgroup writing two consecutive 16 KB pieces of it whatever the row length - the
     // shape of the fastest fill of the probe family: 7.21 TB/s against 7.01 for the row-aligned shape of rounds 1-3 (768 threads
-    // = one row's float4 count, two 12 KB rows per workgroup) in interleaved rounds on one box; 3 or 4 pieces, 768- or 512-thread
-    // slabs and every scope-bit store policy are slower.  Rounds 1-3 (tools/tune_obs.py): among row-aligned shapes the fastest
+    // = one row's float4 count, two 12 KB rows per workgroup) in interleaved rounds on one box; 3 or 4 pieces and 768- or 512-thread
+    // slabs are slower (round 7, with T staged in one trip: still so, and the store policy is obs_store_policy's).  Rounds 1-3 (tools/tune_obs.py): among row-aligned shapes the fastest
     // is the one where every thread issues exactly TWO 16-B stores (6.96 TB/s vs 5.9 for 96-KiB slabs and 5.6 for 786-KiB slabs):
     // small slabs dispatched in order keep the chip-wide write front nearly sequential in address, and a workgroup never
     // outlives its neighbours.  D2D_TUNE_OBS_VARIANT = 3 keeps the row-aligned kernel (A/B, and 8-byte rows when 6N % 4 != 0).
@@ -266,12 +294,13 @@ ObsArgs plan_obs(const ObsTuning& t, int B, int N, int out_f64) {
         o.chunks = (int)((total + slab - 1) / slab);
     }
     o.xcd_remap = (t.xcd > 0 && B % (8 * t.xcd) == 0) ? t.xcd : 0;   // envs interleaved per XCD
-    o.nontemporal = t.nt;
+    o.nontemporal = obs_store_policy(t.nt, flat, o.rows_per_wg);
     o.block = block;
     // tune_variant 2 names the flat kernel, whose grid is sized in flat chunks: when the flat shape does not apply (8-byte rows, a
     // float64 block's float32 consumers) the row-aligned default runs on the row-aligned geometry computed above
     o.variant = flat ? 2 : (t.variant == 2 ? 0 : t.variant);
     o.stagger = t.stagger;
+    if (flat) o.chunk_magic = obs_chunk_magic(o);
     return o;
 }
 

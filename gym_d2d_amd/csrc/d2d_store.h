@@ -11,7 +11,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // One 16-byte store under a chosen cache policy (gfx942+ scope / streaming bits of the global_store encoding): 0 plain, 1 nt
 // (what __builtin_nontemporal_store emits), 2 sc1 (agent scope), 3 sc0 sc1 (system scope: written through), 4 sc0 sc1 nt, 5 sc1 nt.
 // The obs stream is written once and never read by the GPU again; which policy drains it fastest is measured, not assumed
-// (d2d_probe_write_staged, D2D_TUNE_OBS_NONTEMPORAL).
+// (d2d_probe_write_staged, D2D_TUNE_OBS_NONTEMPORAL; plan_obs chooses 1 or 5 per shape, the rest are diagnostic).
 template <int POLICY>
 __device__ __forceinline__ void store16(f32x4* p, f32x4 v) {
     if (POLICY == 0) *p = v;

@@ -233,7 +233,9 @@ int d2d_set_export_actions(d2d_handle* h, int32_t enabled);
  * switch live in d2d_hip_diag.h and exist in diagnostic builds only; a release build answers them D2D_ERR_UNSUPPORTED.    */
 typedef enum d2d_tuning {
     D2D_TUNE_OBS_ROWS_PER_WG = 0,  /* consecutive 16-KiB pieces of an env's obs block written per workgroup (1 .. 4); 0 = auto (2) */
-    D2D_TUNE_OBS_NONTEMPORAL = 1,  /* store policy of the obs stream: 1 (default) nontemporal, 0 plain                */
+    D2D_TUNE_OBS_NONTEMPORAL = 1,  /* store policy of the obs stream: -1 (default) the planner's choice per shape - 5 for the
+                                      flat kernels (even N) at up to two pieces per workgroup, 1 for the rest -, 1 nontemporal,
+                                      0 plain, 5 nontemporal and written through (sc1 nt)                              */
     D2D_TUNE_OBS_XCD_REMAP = 2,    /* 1 (default): chunks of one env share an XCD                    */
     D2D_TUNE_OBS_BLOCK = 3,        /* threads per obs workgroup; 0 = auto                            */
     D2D_TUNE_STEP_THREADS = 5,     /* threads per ENV in the step kernel; 0 = auto (one per link).  Below half the link
