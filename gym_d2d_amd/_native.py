@@ -1,4 +1,4 @@
-"""ctypes binding of libd2d_hip.so (include/d2d_hip.h) and of the side libraries `SIDE` and `SOLVERS` list (libd2d_<name>.so,
+"""ctypes binding of libd2d_hip.so (include/d2d_hip.h) and of the side libraries `SIDE`, `SOLVERS` and `ADDONS` list (libd2d_<name>.so,
 include/d2d_<name>.h).
 There is no CPU fallback: if a library or a gfx950 GPU is missing, the calls below raise."""
 from __future__ import annotations
@@ -75,6 +75,13 @@ ASSIGN_LAW_INV_SQUARE, ASSIGN_LAW_POWER, ASSIGN_LAW_POW_K = 0, 1, 2
 ASSIGN_OBJECTIVE_TOTAL, ASSIGN_OBJECTIVE_OWN = 0, 1
 ASSIGN_MAX_RBS = 8192
 ASSIGN_MAX_LDS_BYTES = 163840
+# d2d_assign_power_weights's law / limits (include/d2d_assignpwr.h): d2d_assign_weights's, and the power alphabet of a movable link
+ASSIGNPWR_LAW_INV_SQUARE, ASSIGNPWR_LAW_POWER, ASSIGNPWR_LAW_POW_K = 0, 1, 2
+ASSIGNPWR_MAX_RBS = 8192
+ASSIGNPWR_MAX_LDS_BYTES = 163840
+ASSIGNPWR_MAX_LEVELS = 64
+ASSIGNPWR_CHUNK = 8
+ASSIGNPWR_NO_POWER = -32768
 
 BUFFER_DTYPES = {BUF_ACTIONS: np.int32, BUF_RB: np.int32, BUF_PWR: np.int32, BUF_ENV_FLAGS: np.int32, BUF_RESET_PENDING: np.int32,
                  BUF_EPISODE: np.uint32}
@@ -241,12 +248,21 @@ ASSIGN_SIGNATURES = {
     'd2d_assign_last_error': (C.c_char_p, []),
 }
 
+# every symbol include/d2d_assignpwr.h declares
+ASSIGNPWR_SIGNATURES = {
+    'd2d_assign_power_weights': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, C.c_int64, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P,
+                                           _P]),
+    'd2d_assignpwr_last_error': (C.c_char_p, []),
+}
+
 # the side libraries: name -> every symbol include/d2d_<name>.h declares; libd2d_<name>.so, its error text in d2d_<name>_last_error
 SIDE = {'plugin': PLUGIN_SIGNATURES, 'episode': EPISODE_SIGNATURES, 'sense': SENSE_SIGNATURES, 'graph': GRAPH_SIGNATURES,
         'marginal': MARGINAL_SIGNATURES, 'mobility': MOBILITY_SIGNATURES, 'channel': CHANNEL_SIGNATURES, 'queue': QUEUE_SIGNATURES,
         'bestrb': BESTRB_SIGNATURES, 'powerctl': POWERCTL_SIGNATURES, 'brdyn': BRDYN_SIGNATURES, 'evaluate': EVALUATE_SIGNATURES}
 # build.SOLVERS' libraries: opened, typed and reported by the same loader
 SOLVERS = {'assign': ASSIGN_SIGNATURES}
+# build.ADDONS' libraries, likewise: the table later add-on kernel families join
+ADDONS = {'assignpwr': ASSIGNPWR_SIGNATURES}
 
 _lib: Optional[C.CDLL] = None
 _side: dict = {}                    # name -> the opened, typed side library
@@ -260,6 +276,7 @@ brdyn_launches = 0                  # d2d_best_response_dynamics launches made t
 evaluate_launches = 0               # d2d_evaluate launches made through evaluate()
 assign_weights_launches = 0         # d2d_assign_weights launches made through assign_weights()
 assign_solve_launches = 0           # d2d_assign_solve launches made through assign_solve()
+assign_power_weights_launches = 0   # d2d_assign_power_weights launches made through assign_power_weights()
 mobility_launches = 0               # d2d_mobility_move calls made through mobility_move()
 channel_launches = 0                # d2d_channel_fill calls made through channel_fill()
 queue_launches = 0                  # d2d_queue_step calls made through queue_step()
@@ -289,14 +306,14 @@ def side_path(name: str) -> Path:
 
 
 def side_library(name: str) -> C.CDLL:
-    """dlopen libd2d_<name>.so once and type the entry points SIDE[name] (or SOLVERS[name]) lists.  Raises if it has not been built."""
+    """dlopen libd2d_<name>.so once and type the entry points SIDE[name] (or SOLVERS[name], ADDONS[name]) lists.  Raises if it has not been built."""
     lib = _side.get(name)
     if lib is None:
         path = side_path(name)
         if not path.exists():
             raise ImportError(f'{path} is missing - build it with `python -m gym_d2d_amd.build`')
         lib = C.CDLL(str(path))
-        for symbol, (res, args) in (SIDE.get(name) or SOLVERS[name]).items():
+        for symbol, (res, args) in (SIDE.get(name) or SOLVERS.get(name) or ADDONS[name]).items():
             fn = getattr(lib, symbol)
             fn.restype = res
             fn.argtypes = args
@@ -324,6 +341,7 @@ def load_powerctl_library() -> C.CDLL: return side_library('powerctl')
 def load_brdyn_library() -> C.CDLL: return side_library('brdyn')
 def load_evaluate_library() -> C.CDLL: return side_library('evaluate')
 def load_assign_library() -> C.CDLL: return side_library('assign')
+def load_assignpwr_library() -> C.CDLL: return side_library('assignpwr')
 
 
 # Pointer arguments are passed as the ints they are: every argtype is c_void_p, which takes 0 as the null pointer and any int up to
@@ -483,6 +501,22 @@ def assign_solve(weights_ptr: int, n_envs: int, n_rows: int, n_cols: int, col_pt
         weights_ptr, n_envs, n_rows, n_cols, col_ptr, value_ptr, feasible_ptr, stream_ptr))
     if n_envs:
         assign_solve_launches += 1
+
+
+def assign_power_weights(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, link_tx_ptr: int, link_rx_ptr: int, cols_ptr: int,
+                         cap_cols_ptr: int, law: int, pow_k: int, n_envs: int, n_dev: int, n_links: int, n_rbs: int,
+                         movable_links_ptr: int, n_movable: int, allowed_ptr: int, p_min_ptr: int, p_max_ptr: int, floor_ptr: int,
+                         weights_ptr: int, power_ptr: int, stream_ptr: int = 0) -> None:
+    """d2d_assign_power_weights: every movable link's best admissible power on every RB and its weight there - weights float32 and
+    power_dbm int32 [n_envs, n_movable, n_rbs], two planes (device pointers; movable_links_ptr, allowed_ptr as assign_weights()
+    takes them; p_min_ptr / p_max_ptr int32 [n_links] on the device; floor_ptr 0: no floors, else float32 [n_links], -inf: none for
+    that link)."""
+    global assign_power_weights_launches
+    _check_side('assignpwr', load_assignpwr_library().d2d_assign_power_weights(
+        pos_x_ptr, pos_y_ptr, rb_ptr, pwr_ptr, link_tx_ptr, link_rx_ptr, cols_ptr, cap_cols_ptr, law, pow_k, n_envs, n_dev, n_links,
+        n_rbs, movable_links_ptr, n_movable, allowed_ptr, p_min_ptr, p_max_ptr, floor_ptr, weights_ptr, power_ptr, stream_ptr))
+    if n_envs:
+        assign_power_weights_launches += 1
 
 
 def mobility_move(pos_x_ptr: int, pos_y_ptr: int, vel_x_ptr: int, vel_y_ptr: int, fixed_mask_ptr: int, n_envs: int, n_cues: int,

@@ -63,8 +63,8 @@ class Assignment(PairKernel):
     """The matching kernels bound to one env object: constants uploaded once, one launch per plane block, one per matching."""
     words = words                                # best_response.words, as a method: self.words(allowed)
 
-    def __init__(self, sim, num_links: int, agent, due, torch, device) -> None:
-        super().__init__(sim, num_links, torch, device, api='assign_rbs', max_rbs=_native.ASSIGN_MAX_RBS, capacity=True)
+    def __init__(self, sim, num_links: int, agent, due, torch, device, api: str = 'assign_rbs') -> None:
+        super().__init__(sim, num_links, torch, device, api=api, max_rbs=_native.ASSIGN_MAX_RBS, capacity=True)
         self.agent = np.asarray(agent, dtype=bool)                   # links that have an action column: the only ones ever moved
         self.due = np.asarray(due, dtype=bool)                       # the DUE-pair links: movable=None
         if self.agent.shape != (self.n,) or self.due.shape != (self.n,):

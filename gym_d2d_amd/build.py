@@ -1,10 +1,11 @@
-"""Build every shared library of `LIBRARIES` and `SOLVERS` for gfx950 with hipcc - in-tree, so the .so files travel with the repo snapshot.
+"""Build every shared library of `LIBRARIES`, `SOLVERS` and `ADDONS` for gfx950 with hipcc - in-tree, so the .so files travel with the repo snapshot.
 
     stem      libd2d_<stem>.so                                        public header
     hip       the product: the C ABI                                  include/d2d_hip.h
     probe     measurement equipment: the write-ceiling probe          include/d2d_hip_diag.h
     the rest  one stateless add-on kernel family each   include/d2d_<stem>.h
     assign    the RB matching, listed in SOLVERS        include/d2d_assign.h
+    assignpwr the joint RB and power weights (4.17), listed in ADDONS   include/d2d_assignpwr.h
 
     python -m gym_d2d_amd.build [--force] [--verbose]
     D2D_BUILD_DIAG=1 python -m gym_d2d_amd.build      # diagnostic build of libd2d_hip.so: the A/B tuning keys and the ablation
@@ -33,9 +34,13 @@ LIBRARIES = {'hip': SOURCES, 'probe': ['d2d_probe.hip'],
 # libraries that are no add-on kernel family of the table above (which _native.SIDE mirrors entry for entry): built and stamped
 # with the rest, and a missing one is rebuilt (solvers_built()).  assign: the matching solver takes ANY weights, not only an env's
 SOLVERS = {'assign': ['d2d_assign.hip']}
-BUILT = {**LIBRARIES, **SOLVERS}                 # what build() compiles and links, in order
+BUILT = {**LIBRARIES, **SOLVERS}
+# further stateless kernel families (which _native.ADDONS mirrors): built and stamped with the rest, and a missing one is rebuilt
+# (addons_built()).  This table is the one that grows.  assignpwr: the joint RB and power weights
+ADDONS = {'assignpwr': ['d2d_assignpwr.hip']}
+EVERYTHING = {**BUILT, **ADDONS}                 # what build() compiles and links, in order
 HEADERS = [CSRC / 'd2d_internal.h', CSRC / 'd2d_plan.h', CSRC / 'd2d_step_device.h', CSRC / 'd2d_store.h', CSRC / 'd2d_same_rb.h', CSRC / 'd2d_addon.h', INCLUDE / 'd2d_hip.h', INCLUDE / 'd2d_hip_diag.h',
-           *(INCLUDE / f'd2d_{stem}.h' for stem in BUILT if stem not in ('hip', 'probe'))]
+           *(INCLUDE / f'd2d_{stem}.h' for stem in EVERYTHING if stem not in ('hip', 'probe'))]
 
 
 def lib_path(stem: str, lib_dir: Path = LIB_DIR) -> Path:
@@ -63,7 +68,7 @@ def _hipcc() -> str:
 
 def digest_files() -> list:
     """The files source_digest() hashes, in order: every library's sources, then the headers."""
-    return [p for p in [CSRC / s for sources in BUILT.values() for s in sources] + HEADERS if p.exists()]
+    return [p for p in [CSRC / s for sources in EVERYTHING.values() for s in sources] + HEADERS if p.exists()]
 
 
 def source_digest() -> str:
@@ -87,16 +92,21 @@ def solvers_built(lib_dir: Path = LIB_DIR) -> bool:
     return all(lib_path(stem, lib_dir).exists() for stem in SOLVERS)
 
 
+def addons_built(lib_dir: Path = LIB_DIR) -> bool:
+    """Every library of ADDONS is there; they share the stamp up_to_date() tests."""
+    return all(lib_path(stem, lib_dir).exists() for stem in ADDONS)
+
+
 def build(force: bool = False, verbose: bool = False) -> Path:
     LIB_DIR.mkdir(exist_ok=True)
     digest = source_digest()
-    if not force and up_to_date(digest) and solvers_built():
+    if not force and up_to_date(digest) and solvers_built() and addons_built():
         return LIB_PATH
     hipcc = _hipcc()
     obj_dir = LIB_DIR / 'obj'
     obj_dir.mkdir(exist_ok=True)
     procs = []
-    for s in [s for sources in BUILT.values() for s in sources]:
+    for s in [s for sources in EVERYTHING.values() for s in sources]:
         src = CSRC / s
         obj = obj_dir / (src.stem + '.o')
         cmd = [hipcc, *FLAGS, '-I', str(INCLUDE), '-c', str(src), '-o', str(obj)]
@@ -109,7 +119,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
             raise RuntimeError(f'hipcc failed on {s}:\n{out}')
         if verbose and out.strip():
             print(out)
-    for stem, sources in BUILT.items():
+    for stem, sources in EVERYTHING.items():
         objs = [str(obj_dir / (Path(s).stem + '.o')) for s in sources]
         cmd = [hipcc, '-shared', '-fPIC', f'--offload-arch={ARCH}', '-o', str(lib_path(stem)), *objs]
         if verbose:

@@ -22,7 +22,7 @@ from typing import Optional
 
 import numpy as np
 
-from .. import _native, assignment, best_response, best_response_dynamics, graph, marginal, power_control, sensing
+from .. import _native, assignment, best_response, best_response_dynamics, graph, joint_assignment, marginal, power_control, sensing
 from .. import evaluate as evaluate_mod
 from .. import mobility as mobility_mod
 from .. import queues as queues_mod
@@ -280,6 +280,8 @@ class VecD2DEnv:
         self._evaluate = None
         # optimal one-to-one RB matching (assign_rbs()): likewise nothing unless it is called
         self._assign = None
+        # joint RB and power matching with SINR floors (assign_rbs_power()): likewise
+        self._joint = None
 
     def _setup_autoreset(self) -> None:
         """Refuse what a device-side per-env reset cannot serve, then allocate the per-env bookkeeping: pending / episode are bound
@@ -836,9 +838,22 @@ class VecD2DEnv:
         return SimpleNamespace(**vars(view), best_rb=best, best_sinr_db=sinr, gain_db=gain)
 
     # ------------------------------------------------------------------ target-SINR power control
+    def _class_bounds(self):
+        """(p_min, p_max) int32 [N] of every link's class, in the dBm the step transmits (power_control.class_bounds)."""
+        return power_control.class_bounds(self.num_pwr_actions, self._cue_kind, self.num_cues, self.num_due_pairs)
+
+    def _agent_power_levels(self):
+        """(first agent link, lowest power [num_agents], power levels [num_agents]) for power_control.encode_actions: the two
+        device tensors are made once."""
+        first = self.num_links - self.num_agents
+        if self._power_levels is None:
+            p_min, p_max = self._class_bounds()
+            self._power_levels = tuple(torch.as_tensor(a[first:], device=self.device) for a in (p_min, p_max - p_min + 1))
+        return (first, *self._power_levels)
+
     def _power_control_kernel(self):
-        return self._kernel('_powerctl', power_control, power_control.PowerControl, lambda: (*power_control.class_bounds(
-            self.num_pwr_actions, self._cue_kind, self.num_cues, self.num_due_pairs), self._agent_links()))
+        return self._kernel('_powerctl', power_control, power_control.PowerControl,
+                            lambda: (*self._class_bounds(), self._agent_links()))
 
     def power_control(self, target_sinr_db, adjustable=None, max_iters: int = 64, out=None, env_mask=None):
         """The least powers that meet a target SINR, with positions and RBs as the last step left them: (power_dbm int32 [B, N],
@@ -874,11 +889,8 @@ class VecD2DEnv:
         repeats its last action.  Links on fixed actions (cue_actions='traffic') have no column.  Composes with
         best_response_actions(): one call picks RBs, the other picks powers."""
         power = self.power_control(target_sinr_db, adjustable, max_iters)[0]
-        first = self.num_links - self.num_agents
-        if self._power_levels is None:
-            p_min, p_max = power_control.class_bounds(self.num_pwr_actions, self._cue_kind, self.num_cues, self.num_due_pairs)
-            self._power_levels = tuple(torch.as_tensor(a[first:], device=self.device) for a in (p_min, p_max - p_min + 1))
-        return power_control.encode_actions(self._t['rb'], power, *self._power_levels, first)
+        first, p_min, levels = self._agent_power_levels()
+        return power_control.encode_actions(self._t['rb'], power, p_min, levels, first)
 
     # ------------------------------------------------------------------ sequential best-response dynamics
     def _best_response_dynamics_kernel(self):
@@ -1039,6 +1051,63 @@ class VecD2DEnv:
             self._action_levels = torch.as_tensor(np.asarray(levels, dtype=np.int32), device=self.device)
         return best_response_dynamics.encode_actions(rb, self._t['pwr'], self._action_levels, self.num_links - self.num_agents)
 
+    # ------------------------------------------------------------------ joint RB and power matching with SINR floors
+    def _joint_assignment_kernel(self):
+        return self._kernel('_joint', joint_assignment, joint_assignment.JointAssignment,
+                            lambda: (self._agent_links(), np.arange(self.num_links) >= self.num_links - self.num_due_pairs,
+                                     *self._class_bounds()))
+
+    def joint_assignment_weights(self, movable=None, allowed=None, min_sinr_db=None, out=None):
+        """What every movable link is worth on every RB at its BEST admissible power, with the background as the last step left
+        it: (weights float32 [B, M, R], power_dbm int32 [B, M, R], links int32 [M]).
+
+        movable, allowed, the background and the rows as assignment_weights() has them, except that a movable link's current power
+        plays no part either: every level p of its class (power_control()'s bounds, the ones step() decodes) is tried.
+        w(a, r, p) = own - harm as assignment_weights(objective='total') defines them at power p - bit for bit that call's weight
+        with the link's power set to p.  min_sinr_db: a number, {'cue': x, 'due': y} or [N] values (array or tensor), dB, -inf: no
+        floor for that link; None: no floors.  (a, r, p) is admissible iff link a's SINR there is >= its floor and no background
+        member of r that meets its floor without link a falls below it with link a present; a member the background alone already
+        holds under its floor constrains nothing.  weights[b, a, r] is the largest w over the admissible p - equal values to the
+        lowest power - and power_dbm[b, a, r] that p; -inf and -32768 where allowed forbids or no p is admissible.
+
+        Under a one-to-one placement a background link sees at most one movable link, so the capacity it loses and whether it keeps
+        its floor depend on that link's RB and power alone: total = evaluate(background) + the sum of w(a, r_a, p_a) for every
+        one-to-one placement and every choice of powers, and the floors hold iff every (a, r_a, p_a) is admissible.
+
+        One kernel launch (csrc/d2d_assignpwr.hip): sorts, background sums and pair gains are shared across the levels.  The env is
+        left untouched.  Valid after reset() and after every step(), autoreset and mobility included.  Torch path only: enqueued on
+        torch's current stream, nothing is synchronised; the two tensors the env owns (4 B M R bytes each, rewritten by every call),
+        or `out` = (weights, power_dbm).  Refusals as assignment_weights(), under the name assign_rbs_power()."""
+        k = self._joint_assignment_kernel()
+        floors = k.floors(min_sinr_db, self.num_cues)
+        self._follow_torch_stream()
+        return k.power_weights(self._t, movable, allowed, floors, out, self._stream_ptr)
+
+    def assign_rbs_power(self, movable=None, allowed=None, min_sinr_db=None, out=None):
+        """The one-to-one placement of the movable links AND the power of each that maximise the total capacity of the env subject
+        to the SINR floors, the background staying where it is: (rb int32 [B, N], power_dbm int32 [B, N], value_mbps float32 [B],
+        feasible uint8 [B]), a tuple with those names.
+
+        rb / power_dbm are the current planes with every movable link on its matched RB, all distinct, at the best admissible power
+        of that entry.  evaluate(rb, power_dbm)['total_mbps'] = evaluate(background) + value_mbps, every constrained link keeps
+        min_sinr_db, and no other (one-to-one placement, powers) that keeps the floors gives more (joint_assignment_weights()): the
+        Hungarian optimum of max over p of w[a, r, p] is the joint optimum.  An env in which the floors or `allowed` leave some
+        movable link no RB of its own is infeasible: it keeps its rb and power rows, with value 0.0 and feasible 0.  The joint
+        launch, then solve_assignment(), then the gather of the matched powers and the two scatters.  More movable links than RBs
+        is a ValueError.  `out` = (rb, power_dbm, value_mbps, feasible)."""
+        k = self._joint_assignment_kernel()
+        floors = k.floors(min_sinr_db, self.num_cues)
+        self._follow_torch_stream()
+        return k.assign_power(self._t, movable, allowed, floors, out, self._stream_ptr)
+
+    def assign_rbs_power_actions(self, movable=None, allowed=None, min_sinr_db=None):
+        """assign_rbs_power() as an action tensor, int32 [B, num_agents], ready for step(): every agent link on its RB at its power
+        of assign_rbs_power(), encoded rb * power levels + level (power_control.encode_actions).  Links on fixed actions
+        (cue_actions='traffic') have no column."""
+        res = self.assign_rbs_power(movable, allowed, min_sinr_db)
+        first, p_min, levels = self._agent_power_levels()
+        return power_control.encode_actions(res.rb, res.power_dbm, p_min, levels, first)
+
     def _observe(self, view):
         extra = {}
         if self._senses:
@@ -1114,4 +1183,7 @@ class VecD2DEnv:
         if self._assign is not None:
             self._assign.close()
             self._assign = None
+        if self._joint is not None:
+            self._joint.close()
+            self._joint = None
         self.simulator.handle.close()

@@ -65,6 +65,31 @@ def encode_actions(rb, power_dbm, p_min, levels, first_agent: int = 0):
     return act.to(torch.int32)
 
 
+def link_values(kernel, values, num_cues: int, name: str):
+    """float32 [N] on the kernel object's device from a scalar, {'cue': x, 'due': y} or [N] values (array or tensor), none of them
+    NaN; `name` is what a refusal calls the argument.  The last host value is kept in kernel._target: a repeat is not uploaded again."""
+    torch = kernel.torch
+    if torch.is_tensor(values):
+        t = values.to(device=kernel.device, dtype=torch.float32).contiguous()
+        if tuple(t.shape) != (kernel.n,):
+            raise ValueError(f'{name} must be a number, {{"cue": x, "due": y}} or [{kernel.n}] values')
+        return t
+    if isinstance(values, dict):
+        if set(values) != {'cue', 'due'}:
+            raise ValueError(f"{name} as a dict takes exactly the keys 'cue' and 'due'")
+        host = np.asarray([values['cue']] * num_cues + [values['due']] * (kernel.n - num_cues), dtype=np.float32)
+    else:
+        host = np.asarray(values, dtype=np.float32)
+        if host.ndim == 0:
+            host = np.full(kernel.n, host, dtype=np.float32)
+    if host.shape != (kernel.n,) or np.isnan(host).any():
+        raise ValueError(f'{name} must be a number, {{"cue": x, "due": y}} or [{kernel.n}] values, none of them NaN')
+    key = host.tobytes()
+    if kernel._target is None or kernel._target[0] != key:
+        kernel._target = (key, torch.as_tensor(host, device=kernel.device))
+    return kernel._target[1]
+
+
 class PowerControl(PairKernel):
     """The power-control kernel bound to one env object: constants uploaded once, one launch per call."""
 
@@ -80,26 +105,7 @@ class PowerControl(PairKernel):
 
     def target(self, target_sinr_db, num_cues: int):
         """float32 [N] on the device from a scalar, {'cue': x, 'due': y} or [N] values (array or tensor)."""
-        torch = self.torch
-        if torch.is_tensor(target_sinr_db):
-            t = target_sinr_db.to(device=self.device, dtype=torch.float32).contiguous()
-            if tuple(t.shape) != (self.n,):
-                raise ValueError(f'target_sinr_db must be a number, {{"cue": x, "due": y}} or [{self.n}] values')
-            return t
-        if isinstance(target_sinr_db, dict):
-            if set(target_sinr_db) != {'cue', 'due'}:
-                raise ValueError("target_sinr_db as a dict takes exactly the keys 'cue' and 'due'")
-            host = np.asarray([target_sinr_db['cue']] * num_cues + [target_sinr_db['due']] * (self.n - num_cues), dtype=np.float32)
-        else:
-            host = np.asarray(target_sinr_db, dtype=np.float32)
-            if host.ndim == 0:
-                host = np.full(self.n, host, dtype=np.float32)
-        if host.shape != (self.n,) or np.isnan(host).any():
-            raise ValueError(f'target_sinr_db must be a number, {{"cue": x, "due": y}} or [{self.n}] values, none of them NaN')
-        key = host.tobytes()
-        if self._target is None or self._target[0] != key:
-            self._target = (key, torch.as_tensor(host, device=self.device))
-        return self._target[1]
+        return link_values(self, target_sinr_db, num_cues, 'target_sinr_db')
 
     def adjustable(self, adjustable):
         """uint8 [N] on the device: the agent links (None), or those of them `adjustable` (bool [N], array or tensor) marks."""
