@@ -82,6 +82,10 @@ ASSIGNPWR_MAX_LDS_BYTES = 163840
 ASSIGNPWR_MAX_LEVELS = 64
 ASSIGNPWR_CHUNK = 8
 ASSIGNPWR_NO_POWER = -32768
+# d2d_color_graph's limits (include/d2d_color.h): the links and RBs an env may have, and the LDS of one workgroup
+COLOR_MAX_LINKS = 2048
+COLOR_MAX_RBS = 8192
+COLOR_MAX_LDS_BYTES = 163840
 
 BUFFER_DTYPES = {BUF_ACTIONS: np.int32, BUF_RB: np.int32, BUF_PWR: np.int32, BUF_ENV_FLAGS: np.int32, BUF_RESET_PENDING: np.int32,
                  BUF_EPISODE: np.uint32}
@@ -255,6 +259,12 @@ ASSIGNPWR_SIGNATURES = {
     'd2d_assignpwr_last_error': (C.c_char_p, []),
 }
 
+# every symbol include/d2d_color.h declares
+COLOR_SIGNATURES = {
+    'd2d_color_graph': (C.c_int, [_P, _P, _P, _P, C.c_int64, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
+    'd2d_color_last_error': (C.c_char_p, []),
+}
+
 # the side libraries: name -> every symbol include/d2d_<name>.h declares; libd2d_<name>.so, its error text in d2d_<name>_last_error
 SIDE = {'plugin': PLUGIN_SIGNATURES, 'episode': EPISODE_SIGNATURES, 'sense': SENSE_SIGNATURES, 'graph': GRAPH_SIGNATURES,
         'marginal': MARGINAL_SIGNATURES, 'mobility': MOBILITY_SIGNATURES, 'channel': CHANNEL_SIGNATURES, 'queue': QUEUE_SIGNATURES,
@@ -262,7 +272,7 @@ SIDE = {'plugin': PLUGIN_SIGNATURES, 'episode': EPISODE_SIGNATURES, 'sense': SEN
 # build.SOLVERS' libraries: opened, typed and reported by the same loader
 SOLVERS = {'assign': ASSIGN_SIGNATURES}
 # build.ADDONS' libraries, likewise: the table later add-on kernel families join
-ADDONS = {'assignpwr': ASSIGNPWR_SIGNATURES}
+ADDONS = {'assignpwr': ASSIGNPWR_SIGNATURES, 'color': COLOR_SIGNATURES}
 
 _lib: Optional[C.CDLL] = None
 _side: dict = {}                    # name -> the opened, typed side library
@@ -277,6 +287,7 @@ evaluate_launches = 0               # d2d_evaluate launches made through evaluat
 assign_weights_launches = 0         # d2d_assign_weights launches made through assign_weights()
 assign_solve_launches = 0           # d2d_assign_solve launches made through assign_solve()
 assign_power_weights_launches = 0   # d2d_assign_power_weights launches made through assign_power_weights()
+color_launches = 0                  # d2d_color_graph launches made through color_graph()
 mobility_launches = 0               # d2d_mobility_move calls made through mobility_move()
 channel_launches = 0                # d2d_channel_fill calls made through channel_fill()
 queue_launches = 0                  # d2d_queue_step calls made through queue_step()
@@ -342,6 +353,7 @@ def load_brdyn_library() -> C.CDLL: return side_library('brdyn')
 def load_evaluate_library() -> C.CDLL: return side_library('evaluate')
 def load_assign_library() -> C.CDLL: return side_library('assign')
 def load_assignpwr_library() -> C.CDLL: return side_library('assignpwr')
+def load_color_library() -> C.CDLL: return side_library('color')
 
 
 # Pointer arguments are passed as the ints they are: every argtype is c_void_p, which takes 0 as the null pointer and any int up to
@@ -517,6 +529,21 @@ def assign_power_weights(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: i
         n_rbs, movable_links_ptr, n_movable, allowed_ptr, p_min_ptr, p_max_ptr, floor_ptr, weights_ptr, power_ptr, stream_ptr))
     if n_envs:
         assign_power_weights_launches += 1
+
+
+def color_graph(score_ptr: int, tx_bias_ptr: int, rx_thr_ptr: int, rb_ptr: int, n_envs: int, n_links: int, n_rbs: int, allowed_ptr: int,
+                movable_ptr: int, pack: bool, rb_out_ptr: int, conflicts_ptr: int, rbs_used_ptr: int, proper_ptr: int,
+                stream_ptr: int = 0) -> None:
+    """d2d_color_graph: the DSATUR colouring of every env's conflict graph in one launch - rb int32 [n_envs, n_links], conflicts /
+    rbs_used int32 and proper uint8 [n_envs] (device pointers; score float32 [n_envs, n_links, n_links], receiver-major; tx_bias_ptr
+    0: no bias, else float32 [n_envs, n_links]; rx_thr float32 [n_envs, n_links]; allowed_ptr 0: every RB, else uint32 [n_links,
+    ceil(n_rbs / 32)]; movable_ptr 0: every link, else uint8 [n_links])."""
+    global color_launches
+    _check_side('color', load_color_library().d2d_color_graph(
+        score_ptr, tx_bias_ptr, rx_thr_ptr, rb_ptr, n_envs, n_links, n_rbs, allowed_ptr, movable_ptr, 1 if pack else 0, rb_out_ptr,
+        conflicts_ptr, rbs_used_ptr, proper_ptr, stream_ptr))
+    if n_envs:
+        color_launches += 1
 
 
 def mobility_move(pos_x_ptr: int, pos_y_ptr: int, vel_x_ptr: int, vel_y_ptr: int, fixed_mask_ptr: int, n_envs: int, n_cues: int,

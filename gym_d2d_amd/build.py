@@ -6,6 +6,7 @@
     the rest  one stateless add-on kernel family each   include/d2d_<stem>.h
     assign    the RB matching, listed in SOLVERS        include/d2d_assign.h
     assignpwr the joint RB and power weights (4.17), listed in ADDONS   include/d2d_assignpwr.h
+    color     the conflict-graph RB colouring (4.18), listed in ADDONS   include/d2d_color.h
 
     python -m gym_d2d_amd.build [--force] [--verbose]
     D2D_BUILD_DIAG=1 python -m gym_d2d_amd.build      # diagnostic build of libd2d_hip.so: the A/B tuning keys and the ablation
@@ -36,8 +37,9 @@ LIBRARIES = {'hip': SOURCES, 'probe': ['d2d_probe.hip'],
 SOLVERS = {'assign': ['d2d_assign.hip']}
 BUILT = {**LIBRARIES, **SOLVERS}
 # further stateless kernel families (which _native.ADDONS mirrors): built and stamped with the rest, and a missing one is rebuilt
-# (addons_built()).  This table is the one that grows.  assignpwr: the joint RB and power weights
-ADDONS = {'assignpwr': ['d2d_assignpwr.hip']}
+# (addons_built() for the row the table opened with, addons_missing() for every row).  This table is the one that grows.
+# assignpwr: the joint RB and power weights; color: the conflict-graph RB colouring (4.18)
+ADDONS = {'assignpwr': ['d2d_assignpwr.hip'], 'color': ['d2d_color.hip']}
 EVERYTHING = {**BUILT, **ADDONS}                 # what build() compiles and links, in order
 HEADERS = [CSRC / 'd2d_internal.h', CSRC / 'd2d_plan.h', CSRC / 'd2d_step_device.h', CSRC / 'd2d_store.h', CSRC / 'd2d_same_rb.h', CSRC / 'd2d_addon.h', INCLUDE / 'd2d_hip.h', INCLUDE / 'd2d_hip_diag.h',
            *(INCLUDE / f'd2d_{stem}.h' for stem in EVERYTHING if stem not in ('hip', 'probe'))]
@@ -93,14 +95,21 @@ def solvers_built(lib_dir: Path = LIB_DIR) -> bool:
 
 
 def addons_built(lib_dir: Path = LIB_DIR) -> bool:
-    """Every library of ADDONS is there; they share the stamp up_to_date() tests."""
-    return all(lib_path(stem, lib_dir).exists() for stem in ADDONS)
+    """The library of the row ADDONS opened with, assignpwr, is there - what this predicate has answered since that library was the
+    whole table, and what a directory that holds that library alone still answers.  The rows that joined since are answered by
+    addons_missing(); build() asks both.  They share the stamp up_to_date() tests."""
+    return lib_path(next(iter(ADDONS)), lib_dir).exists()
+
+
+def addons_missing(lib_dir: Path = LIB_DIR) -> list:
+    """The stems of ADDONS whose library is not there, in the table's order: a missing one is rebuilt."""
+    return [stem for stem in ADDONS if not lib_path(stem, lib_dir).exists()]
 
 
 def build(force: bool = False, verbose: bool = False) -> Path:
     LIB_DIR.mkdir(exist_ok=True)
     digest = source_digest()
-    if not force and up_to_date(digest) and solvers_built() and addons_built():
+    if not force and up_to_date(digest) and solvers_built() and addons_built() and not addons_missing():
         return LIB_PATH
     hipcc = _hipcc()
     obj_dir = LIB_DIR / 'obj'

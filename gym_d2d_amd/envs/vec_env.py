@@ -22,7 +22,7 @@ from typing import Optional
 
 import numpy as np
 
-from .. import _native, assignment, best_response, best_response_dynamics, graph, joint_assignment, marginal, power_control, sensing
+from .. import _native, assignment, best_response, best_response_dynamics, coloring, graph, joint_assignment, marginal, power_control, sensing
 from .. import evaluate as evaluate_mod
 from .. import mobility as mobility_mod
 from .. import queues as queues_mod
@@ -282,6 +282,8 @@ class VecD2DEnv:
         self._assign = None
         # joint RB and power matching with SINR floors (assign_rbs_power()): likewise
         self._joint = None
+        # conflict-graph RB colouring (color_graph(), color_rbs()): likewise
+        self._color = None
 
     def _setup_autoreset(self) -> None:
         """Refuse what a device-side per-env reset cannot serve, then allocate the per-env bookkeeping: pending / episode are bound
@@ -1108,6 +1110,77 @@ class VecD2DEnv:
         first, p_min, levels = self._agent_power_levels()
         return power_control.encode_actions(res.rb, res.power_dbm, p_min, levels, first)
 
+    # ------------------------------------------------------------------ conflict-graph RB colouring
+    def _color_kernel(self):
+        return self._kernel('_color', coloring, coloring.Coloring, lambda: (self._agent_links(),))
+
+    def color_graph(self, score, rx_thr, tx_bias=None, movable=None, allowed=None, pack: bool = False, out=None):
+        """DSATUR colouring of a conflict graph with the RBs, several compatible links per RB: (rb int32 [B, N], conflicts int32 [B],
+        rbs_used int32 [B], proper uint8 [B]), a tuple with those names.
+
+        score: ANY contiguous float32 [B, N, N] tensor on the env's device, receiver-major as coupling() is (i receives, j
+        transmits); rx_thr float32 [B, N]; tx_bias float32 [B, N] or None (0).  Link j conflicts with link i iff i != j and
+        score[b, i, j] + tx_bias[b, j] >= rx_thr[b, i] - one float32 addition, a NaN on either side compares false, rx_thr +inf: never
+        a victim - and {i, j} is an edge iff either direction conflicts.  A link takes a turn iff it is movable and has an allowed RB;
+        every other link is background: it keeps its RB (as the decoded plane holds it) and is coloured from the start.  Turn after
+        turn the uncoloured link with the most distinct RBs among its coloured neighbours (then the most neighbours, then the lowest
+        index) takes the allowed RB with the fewest coloured neighbours on it, then - pack=False - the fewest links on it, then the
+        lowest; pack=True leaves the load out: the lowest free RB, the classic minimum-colour greedy.  With no free RB the rule
+        degrades to the least-conflicting one.  conflicts counts the same-RB edges with an end that took a turn, rbs_used the distinct
+        RBs those links hold, proper is conflicts == 0.  A heuristic: nothing is claimed beyond those counts.
+
+        movable: bool [N], the links that take turns; None: every agent link (links on cue_actions='traffic' never move).  allowed:
+        bool [N, R] as best_rb() takes it; None: every RB.  All turns of an env run in one workgroup of one kernel launch
+        (csrc/d2d_color.hip) out of LDS, in integers: two calls give the same words.  The env is left untouched.
+
+        Torch path only: enqueued on torch's current stream, nothing is synchronised; the four tensors the env owns, rewritten by
+        every call (clone them to keep them), or `out` = (rb, conflicts, rbs_used, proper), contiguous int32 [B, N], int32 / int32 /
+        uint8 [B] on the env's device.  Refused as color_rbs() is."""
+        k = self._color_kernel()
+        mov = k.movable(movable)
+        self._follow_torch_stream()
+        return k.color(self._t['rb'], score, rx_thr, tx_bias, mov, allowed, pack, out, self._stream_ptr)
+
+    def color_rbs(self, margin_db, movable=None, allowed=None, power_dbm=None, pack: bool = False, out=None):
+        """The interference-graph colouring baseline: color_graph() on the SIR conflict graph of the current positions and powers.
+
+        Link j conflicts with link i iff j alone, at its power, would hold i's signal-to-interference ratio under margin_db[i]:
+        coupling()[b, i, j] + p[b, j] >= (coupling()[b, i, i] + p[b, i]) - margin_db[i], every operation in float32 in that
+        association (the receiver gains are on both sides, which is why coupling() fits although it carries none).  p is the
+        decoded power plane, or power_dbm (int32 [B, N] on the env's device) - power_control()'s powers, say.  margin_db: a number,
+        {'cue': x, 'due': y} or [N] values (array or tensor), dB; -inf: that link is never a victim; NaN is a ValueError.
+
+        When proper is 1 every same-RB pair with an end that took a turn keeps those PAIRWISE margins.  Nothing is said about the
+        aggregate SINR of several co-channel links, and there is no optimality certificate as assign_rbs() has one; several links
+        may share an RB, so more movable links than RBs is no error here.  movable, allowed, pack, out and the result as
+        color_graph() has them.  Two kernel launches, coupling() - whose env-owned tensor is rewritten - and the colouring, and three
+        elementwise torch operations.  Valid after reset() and after every step(), autoreset and mobility included, as coupling()
+        is.  Torch path only; ValueError for what coupling() refuses: export_actions=False, ShadowingPathLoss, every table route,
+        pinned device_config coordinates float32 cannot hold."""
+        k = self._color_kernel()
+        margin, mov = k.margin(margin_db, self.num_cues), k.movable(movable)
+        if power_dbm is None:
+            power_dbm = self._t['pwr']
+        elif not torch.is_tensor(power_dbm) or tuple(power_dbm.shape) != (self.num_envs, self.num_links) or power_dbm.dtype != torch.int32 \
+                or power_dbm.device != self.device:
+            raise ValueError(f'power_dbm must be an int32 tensor [{self.num_envs}, {self.num_links}] on {self.device} or None')
+        c = self.coupling()
+        p = power_dbm.to(torch.float32).contiguous()
+        thr = coloring.sir_threshold(c, p, margin).contiguous()
+        return k.color(self._t['rb'], c, thr, p, mov, allowed, pack, out, self._stream_ptr)
+
+    def color_rbs_actions(self, margin_db, movable=None, allowed=None, power_dbm=None, pack: bool = False):
+        """color_rbs() as an action tensor, int32 [B, num_agents], ready for step(): every agent link on its RB of color_rbs() at its
+        current power level (as the decoded planes hold it), encoded rb * power levels + level.  Links on fixed actions
+        (cue_actions='traffic') have no column.  Composes with power_control_actions() the way best_response_dynamics_actions()
+        does: one call picks RBs, the other picks powers."""
+        rb = self.color_rbs(margin_db, movable, allowed, power_dbm, pack)[0]
+        if self._action_levels is None:
+            p = self.num_pwr_actions
+            levels = ([p[self._cue_kind]] * self.num_cues if self.cue_actions == 'agent' else []) + [p['due']] * self.num_due_pairs
+            self._action_levels = torch.as_tensor(np.asarray(levels, dtype=np.int32), device=self.device)
+        return best_response_dynamics.encode_actions(rb, self._t['pwr'], self._action_levels, self.num_links - self.num_agents)
+
     def _observe(self, view):
         extra = {}
         if self._senses:
@@ -1186,4 +1259,7 @@ class VecD2DEnv:
         if self._joint is not None:
             self._joint.close()
             self._joint = None
+        if self._color is not None:
+            self._color.close()
+            self._color = None
         self.simulator.handle.close()
