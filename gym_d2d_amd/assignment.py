@@ -4,7 +4,8 @@
 columns sensing.fold_capacity_columns folds, both unchanged) and launches the two kernels on torch's device pointers: the weight
 planes of every movable link on every RB, and the maximum-weight matching of any such planes.  The allowed mask goes through
 best_response.words / pack_allowed; the matched RBs become step()'s action tensor through best_response_dynamics.encode_actions.
-Torch path only.
+Torch path only.  The refusal texts are the 'assign_rbs' row of
+sensing.REFUSALS; the out= predicate (all_fit), the launch prefix (launch_args) and r16 are PairKernel's.
 """
 from __future__ import annotations
 
@@ -14,7 +15,7 @@ import numpy as np
 
 from . import _native
 from .best_response import words
-from .sensing import PairKernel, unserved
+from .sensing import PairKernel, r16, refusal_text
 
 OBJECTIVES = {'total': _native.ASSIGN_OBJECTIVE_TOTAL, 'own': _native.ASSIGN_OBJECTIVE_OWN}
 
@@ -28,34 +29,17 @@ class AssignmentResult(NamedTuple):
 
 def refusal(sim, export_actions: bool, use_torch: bool = True) -> Optional[str]:
     """Why this env has no assign_rbs() (None: it has): the predicate of sensing.unserved under evaluate()'s texts and this name."""
-    if not use_torch:
-        return 'assign_rbs() needs the torch path (use_torch): its planes are device tensors'
-    why = unserved(sim, export_actions)
-    if why is None:
-        return None
-    kind, route = why
-    return {
-        'export_actions': 'assign_rbs() works in the units of the decoded (rb, tx power) planes and reads them for the background '
-                          'links, and export_actions=False does not write them: build the env with export_actions=True',
-        'route': f"assign_rbs() does not serve the '{route}' path-loss route (a table, not a law its kernel can evaluate for the pairs "
-                 'no step reads); it serves the native power-law models',
-        'shadowing': 'assign_rbs() does not serve ShadowingPathLoss: a fresh draw per evaluation has no counterfactual (what another '
-                     'assignment would have given is another draw)',
-        'pinned': 'assign_rbs() does not serve pinned device_config coordinates that float32 cannot hold: their low parts live inside '
-                  'the handle (float64 positions)',
-    }[kind]
+    return refusal_text('assign_rbs', sim, export_actions, use_torch)
 
 
 def lds_bytes(num_links: int, num_rbs: int, power_law: bool) -> int:
     """The LDS one workgroup of the weights kernel needs (the header's formula): at most _native.ASSIGN_MAX_LDS_BYTES is served."""
-    r16 = lambda x: (x + 15) & ~15
     n, n4 = num_links, (num_links + 3) & ~3
     return 48 * n + (r16(8 * n) if power_law else 0) + r16(8 * n4) + 3 * r16(4 * n) + r16(4 * (num_rbs + 1))
 
 
 def solve_lds_bytes(num_rows: int, num_cols: int) -> int:
     """The LDS one workgroup of the matching kernel needs (the header's formula): at most _native.ASSIGN_MAX_LDS_BYTES is served."""
-    r16 = lambda x: (x + 15) & ~15
     return r16(8 * num_rows) + 2 * r16(8 * num_cols) + 2 * r16(4 * num_cols) + r16(4 * num_rows) + 96
 
 
@@ -101,11 +85,7 @@ class Assignment(PairKernel):
         return self.own[key]
 
     def _check_out(self, out, names, shapes, dtypes):
-        torch = self.torch
-        ok = isinstance(out, (tuple, list)) and len(out) == len(names) and all(
-            torch.is_tensor(o) and tuple(o.shape) == tuple(s) and o.dtype == dt and o.is_contiguous() and o.device == self.device
-            for o, s, dt in zip(out, shapes, dtypes))
-        if not ok or len({o.data_ptr() for o in out}) != len(names):
+        if not self.all_fit(out, shapes, dtypes):
             raise ValueError('out must be (' + ', '.join(names) + '): contiguous tensors ' +
                              ', '.join(f'{str(dt).replace("torch.", "")} {list(s)}' for s, dt in zip(shapes, dtypes)) +
                              f' on {self.device} that do not share memory')
@@ -129,10 +109,8 @@ class Assignment(PairKernel):
         else:
             planes = self._check_out((out,) if torch.is_tensor(out) else out, names, (shape,) * len(names), (torch.float32,) * len(names))
         mask = self.words(allowed)                   # lives until the launch is enqueued; the stream orders its release behind it
-        _native.assign_weights(t['pos_x'].data_ptr(), t['pos_y'].data_ptr(), t['rb'].data_ptr(), t['pwr'].data_ptr(), *self.ptrs,
-                               self.law, self.pow_k, self.b, self.d, self.n, self.r, links.data_ptr(), m,
-                               0 if mask is None else mask.data_ptr(), OBJECTIVES[objective], planes[0].data_ptr(),
-                               planes[1].data_ptr() if harm else 0, stream)
+        _native.assign_weights(*self.launch_args(t), links.data_ptr(), m, 0 if mask is None else mask.data_ptr(), OBJECTIVES[objective],
+                               planes[0].data_ptr(), planes[1].data_ptr() if harm else 0, stream)
         return (planes[0], links, planes[1]) if harm else (planes[0], links)
 
     def solve(self, weights, out, stream: int):

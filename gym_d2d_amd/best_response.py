@@ -2,7 +2,8 @@
 
 `BestRb` owns the device-side constants of one env object (link lists, the columns sensing.fold_columns folds, unchanged) and launches
 the kernel on torch's device pointers.  `pack_allowed` lowers a bool [N, R] mask to the kernel's words, `encode_actions` turns the
-kernel's planes into the action tensor VecD2DEnv.step() takes.  Torch path only.
+kernel's planes into the action tensor VecD2DEnv.step() takes.  Torch path only.  The refusal texts are the 'best_rb' row of
+sensing.REFUSALS; the out= check and the owned planes (declare_outputs, outputs) and the launch prefix (launch_args) are PairKernel's.
 """
 from __future__ import annotations
 
@@ -11,27 +12,12 @@ from typing import Optional
 import numpy as np
 
 from . import _native
-from .sensing import PairKernel, unserved
+from .sensing import PairKernel, refusal_text
 
 
 def refusal(sim, export_actions: bool, use_torch: bool = True) -> Optional[str]:
     """Why this env has no best_rb() (None: it has): the predicate of sensing.unserved under texts of its own."""
-    if not use_torch:
-        return 'best_rb() needs the torch path (use_torch): its planes are device tensors'
-    why = unserved(sim, export_actions)
-    if why is None:
-        return None
-    kind, route = why
-    return {
-        'export_actions': 'best_rb() reads the decoded (rb, tx power) planes, which export_actions=False does not write: build the '
-                          'env with export_actions=True',
-        'route': f"best_rb() does not serve the '{route}' path-loss route (a table, not a law its kernel can evaluate for the pairs "
-                 'no step reads); it serves the native power-law models',
-        'shadowing': 'best_rb() does not serve ShadowingPathLoss: a fresh draw per evaluation has no counterfactual (what another RB '
-                     'would have given is another draw)',
-        'pinned': 'best_rb() does not serve pinned device_config coordinates that float32 cannot hold: their low parts live inside '
-                  'the handle (float64 positions)',
-    }[kind]
+    return refusal_text('best_rb', sim, export_actions, use_torch)
 
 
 def pack_allowed(mask, xp=np):
@@ -83,28 +69,14 @@ class BestRb(PairKernel):
 
     def __init__(self, sim, num_links: int, torch, device) -> None:
         super().__init__(sim, num_links, torch, device, api='best_rb', max_rbs=_native.BESTRB_MAX_RBS)
-        self.own = None                              # the three planes this object owns, allocated by the first call without out=
+        shape = (self.b, self.n)
+        self.declare_outputs(('best_rb', 'best_sinr_db', 'gain_db'), (shape,) * 3, (torch.int32, torch.float32, torch.float32),
+                             f'out must be (best_rb, best_sinr_db, gain_db): contiguous int32, float32, float32 tensors {list(shape)} '
+                             f'on {device} that do not share memory')
 
     def planes(self, t: dict, allowed, out, stream: int, env_mask=None):
-        torch = self.torch
-        shape = (self.b, self.n)
-        if out is None:
-            if self.own is None:
-                self.own = (torch.empty(shape, dtype=torch.int32, device=self.device),
-                            torch.empty(shape, dtype=torch.float32, device=self.device),
-                            torch.empty(shape, dtype=torch.float32, device=self.device))
-            out = self.own
-        else:
-            ok = isinstance(out, (tuple, list)) and len(out) == 3 and all(
-                torch.is_tensor(o) and tuple(o.shape) == shape and o.dtype == dt and o.is_contiguous() and o.device == self.device
-                for o, dt in zip(out, (torch.int32, torch.float32, torch.float32)))
-            if not ok or len({o.data_ptr() for o in out}) != 3:
-                raise ValueError(f'out must be (best_rb, best_sinr_db, gain_db): contiguous int32, float32, float32 tensors {list(shape)} '
-                                 f'on {self.device} that do not share memory')
-            out = tuple(out)
+        best, sinr, gain = self.outputs(out)
         words = self.words(allowed)                  # lives until the launch is enqueued; the stream orders its release behind it
-        best, sinr, gain = out
-        _native.best_rb(t['pos_x'].data_ptr(), t['pos_y'].data_ptr(), t['rb'].data_ptr(), t['pwr'].data_ptr(), *self.ptrs, self.law,
-                        self.pow_k, self.b, self.d, self.n, self.r, 0 if words is None else words.data_ptr(),
-                        0 if env_mask is None else env_mask.data_ptr(), best.data_ptr(), sinr.data_ptr(), gain.data_ptr(), stream)
+        _native.best_rb(*self.launch_args(t), 0 if words is None else words.data_ptr(), 0 if env_mask is None else env_mask.data_ptr(),
+                        best.data_ptr(), sinr.data_ptr(), gain.data_ptr(), stream)
         return best, sinr, gain

@@ -2,7 +2,8 @@
 
 `BestResponseDynamics` owns the device-side constants of one env object (link lists, the columns sensing.fold_columns folds,
 unchanged) and launches the kernel on torch's device pointers; the allowed mask goes through best_response.words / pack_allowed.
-`encode_actions` turns the solved RBs into the action tensor VecD2DEnv.step() takes.  Torch path only.
+`encode_actions` turns the solved RBs into the action tensor VecD2DEnv.step() takes.  Torch path only.  The refusal texts are the 'best_response_dynamics' row of
+sensing.REFUSALS; the out= check and the owned outputs (declare_outputs, outputs), the launch prefix (launch_args) and r16 are PairKernel's.
 """
 from __future__ import annotations
 
@@ -13,7 +14,7 @@ import numpy as np
 
 from . import _native
 from .best_response import words
-from .sensing import PairKernel, unserved
+from .sensing import PairKernel, r16, refusal_text
 
 
 class BestResponseDynamicsResult(NamedTuple):
@@ -27,27 +28,11 @@ class BestResponseDynamicsResult(NamedTuple):
 
 def refusal(sim, export_actions: bool, use_torch: bool = True) -> Optional[str]:
     """Why this env has no best_response_dynamics() (None: it has): the predicate of sensing.unserved under texts of its own."""
-    if not use_torch:
-        return 'best_response_dynamics() needs the torch path (use_torch): its planes are device tensors'
-    why = unserved(sim, export_actions)
-    if why is None:
-        return None
-    kind, route = why
-    return {
-        'export_actions': 'best_response_dynamics() reads the decoded (rb, tx power) planes, which export_actions=False does not '
-                          'write: build the env with export_actions=True',
-        'route': f"best_response_dynamics() does not serve the '{route}' path-loss route (a table, not a law its kernel can "
-                 'evaluate for the RBs no step has applied); it serves the native power-law models',
-        'shadowing': 'best_response_dynamics() does not serve ShadowingPathLoss: a fresh draw per evaluation has no best response '
-                     '(the SINR a move was made for is another draw than the one the next link sees)',
-        'pinned': 'best_response_dynamics() does not serve pinned device_config coordinates that float32 cannot hold: their low '
-                  'parts live inside the handle (float64 positions)',
-    }[kind]
+    return refusal_text('best_response_dynamics', sim, export_actions, use_torch)
 
 
 def lds_bytes(num_links: int, num_rbs: int, power_law: bool, allowed: bool) -> int:
     """The LDS one workgroup of the kernel needs (the header's formula): at most _native.BRDYN_MAX_LDS_BYTES is served."""
-    r16 = lambda x: (x + 15) & ~15
     n, n4 = num_links, (num_links + 3) & ~3
     return (32 * n + (r16(8 * n) if power_law else 0) + 12 * n4 + (r16(4 * n * ((num_rbs + 31) // 32)) if allowed else 0)
             + r16(4 * ((n + 31) // 32) * num_rbs) + 80)
@@ -75,28 +60,12 @@ class BestResponseDynamics(PairKernel):
         self.agent = np.asarray(agent, dtype=bool)                   # links that have an action column: the only ones ever moved
         if self.agent.shape != (self.n,):
             raise ValueError('the agent mask does not match the env')
-        self.own = None                              # the five outputs this object owns, allocated by the first call without out=
+        self.declare_outputs(BestResponseDynamicsResult._fields, ((self.b, self.n), (self.b, self.n), (self.b,), (self.b,), (self.b,)),
+                             (torch.int32, torch.float32, torch.int32, torch.int32, torch.uint8))
 
     def movable(self, movable):
         """uint8 [N] on the device: the agent links (None), or those of them `movable` (bool [N], array or tensor) marks."""
         return self.agent_subset(movable, 'movable')
-
-    def outputs(self, out):
-        torch = self.torch
-        shapes = ((self.b, self.n), (self.b, self.n), (self.b,), (self.b,), (self.b,))
-        dtypes = (torch.int32, torch.float32, torch.int32, torch.int32, torch.uint8)
-        if out is None:
-            if self.own is None:
-                self.own = tuple(torch.empty(s, dtype=dt, device=self.device) for s, dt in zip(shapes, dtypes))
-            return self.own
-        ok = isinstance(out, (tuple, list)) and len(out) == 5 and all(
-            torch.is_tensor(o) and tuple(o.shape) == s and o.dtype == dt and o.is_contiguous() and o.device == self.device
-            for o, s, dt in zip(out, shapes, dtypes))
-        if not ok or len({o.data_ptr() for o in out}) != 5:
-            raise ValueError(f'out must be (rb, sinr_db, rounds, moves, converged): contiguous int32 {list(shapes[0])}, float32 '
-                             f'{list(shapes[1])}, int32 [{self.b}], int32 [{self.b}] and uint8 [{self.b}] tensors on {self.device} '
-                             'that do not share memory')
-        return tuple(out)
 
     def solve(self, t: dict, allowed, movable, min_gain_db: float, max_rounds: int, out, stream: int,
               env_mask=None) -> BestResponseDynamicsResult:
@@ -113,8 +82,7 @@ class BestResponseDynamics(PairKernel):
         rb, sinr, rounds, moves, conv = self.outputs(out)
         words = self.words(allowed)                  # lives until the launch is enqueued; the stream orders its release behind it
         mask = self.env_mask(env_mask)
-        _native.best_response_dynamics(t['pos_x'].data_ptr(), t['pos_y'].data_ptr(), t['rb'].data_ptr(), t['pwr'].data_ptr(), *self.ptrs,
-                                       self.law, self.pow_k, self.b, self.d, self.n, self.r, 0 if words is None else words.data_ptr(),
-                                       movable.data_ptr(), float(min_gain_db), int(max_rounds), 0 if mask is None else mask.data_ptr(),
-                                       rb.data_ptr(), sinr.data_ptr(), rounds.data_ptr(), moves.data_ptr(), conv.data_ptr(), stream)
+        _native.best_response_dynamics(*self.launch_args(t), 0 if words is None else words.data_ptr(), movable.data_ptr(),
+                                       float(min_gain_db), int(max_rounds), 0 if mask is None else mask.data_ptr(), rb.data_ptr(),
+                                       sinr.data_ptr(), rounds.data_ptr(), moves.data_ptr(), conv.data_ptr(), stream)
         return BestResponseDynamicsResult(rb, sinr, rounds, moves, conv)

@@ -4,7 +4,8 @@
 bias and threshold tensors are the caller's (color_graph) or the SIR graph of the literature built from coupling() and the power
 plane (`sir_threshold`, color_rbs); the movable links go through PairKernel.agent_subset, the allowed mask through
 best_response.words, the margins through power_control.link_values.  The solved RBs become step()'s action tensor through
-best_response_dynamics.encode_actions.  Torch path only.
+best_response_dynamics.encode_actions.  Torch path only.  The refusal texts are the 'color_rbs' row of
+sensing.REFUSALS; the out= check and the owned outputs (declare_outputs, outputs), the single-tensor predicate (fits) and r16 are PairKernel's.
 """
 from __future__ import annotations
 
@@ -15,7 +16,7 @@ import numpy as np
 from . import _native
 from .best_response import words
 from .power_control import link_values
-from .sensing import PairKernel, unserved
+from .sensing import PairKernel, r16, refusal_text
 
 
 class ColoringResult(NamedTuple):
@@ -28,27 +29,11 @@ class ColoringResult(NamedTuple):
 
 def refusal(sim, export_actions: bool, use_torch: bool = True) -> Optional[str]:
     """Why this env has no color_rbs() (None: it has): the predicate of sensing.unserved under texts of its own."""
-    if not use_torch:
-        return 'color_rbs() needs the torch path (use_torch): its graph and planes are device tensors'
-    why = unserved(sim, export_actions)
-    if why is None:
-        return None
-    kind, route = why
-    return {
-        'export_actions': 'color_rbs() reads the decoded (rb, tx power) planes, which export_actions=False does not write: build the '
-                          'env with export_actions=True',
-        'route': f"color_rbs() does not serve the '{route}' path-loss route (a table, not a law coupling() can evaluate for the "
-                 'pairs no step reads); it serves the native power-law models',
-        'shadowing': 'color_rbs() does not serve ShadowingPathLoss: a fresh draw per evaluation has no conflict graph (the pair a '
-                     'colour was chosen for is another draw than the one the next step sees)',
-        'pinned': 'color_rbs() does not serve pinned device_config coordinates that float32 cannot hold: their low parts live inside '
-                  'the handle (float64 positions)',
-    }[kind]
+    return refusal_text('color_rbs', sim, export_actions, use_torch)
 
 
 def lds_bytes(num_links: int, num_rbs: int, allowed: bool) -> int:
     """The LDS one workgroup of the kernel needs (the header's formula): at most _native.COLOR_MAX_LDS_BYTES is served."""
-    r16 = lambda x: (x + 15) & ~15
     n, w, words = num_links, (num_links + 31) // 32, (num_rbs + 31) // 32
     return r16(4 * n * w) + (2 if allowed else 1) * r16(4 * n * words) + 3 * r16(4 * n) + 2 * r16(4 * num_rbs) + r16(4 * words) + 64
 
@@ -70,7 +55,8 @@ class Coloring(PairKernel):
         self.agent = np.asarray(agent, dtype=bool)                   # links that have an action column: the only ones ever coloured
         if self.agent.shape != (self.n,):
             raise ValueError('the agent mask does not match the env')
-        self.own = None                              # the four outputs this object owns, allocated by the first call without out=
+        self.declare_outputs(ColoringResult._fields, ((self.b, self.n), (self.b,), (self.b,), (self.b,)),
+                             (torch.int32, torch.int32, torch.int32, torch.uint8))
         self._target = None                          # (key, tensor) of the last margins: a repeat is not uploaded again
 
     def movable(self, movable):
@@ -87,29 +73,11 @@ class Coloring(PairKernel):
     def plane(self, value, name: str, shape, optional: bool = False):
         """`value` if it is a contiguous float32 tensor of `shape` on the env's device (None passes with optional), else ValueError
         under `name`."""
-        torch = self.torch
         if value is None and optional:
             return None
-        if not torch.is_tensor(value) or tuple(value.shape) != tuple(shape) or value.dtype != torch.float32 \
-                or not value.is_contiguous() or value.device != self.device:
+        if not self.fits(value, shape, self.torch.float32):
             raise ValueError(f'{name} must be a contiguous float32 tensor {list(shape)} on {self.device}' + (' or None' if optional else ''))
         return value
-
-    def outputs(self, out):
-        torch = self.torch
-        shapes = ((self.b, self.n), (self.b,), (self.b,), (self.b,))
-        dtypes = (torch.int32, torch.int32, torch.int32, torch.uint8)
-        if out is None:
-            if self.own is None:
-                self.own = tuple(torch.empty(s, dtype=dt, device=self.device) for s, dt in zip(shapes, dtypes))
-            return self.own
-        ok = isinstance(out, (tuple, list)) and len(out) == 4 and all(
-            torch.is_tensor(o) and tuple(o.shape) == s and o.dtype == dt and o.is_contiguous() and o.device == self.device
-            for o, s, dt in zip(out, shapes, dtypes))
-        if not ok or len({o.data_ptr() for o in out}) != 4:
-            raise ValueError(f'out must be (rb, conflicts, rbs_used, proper): contiguous int32 {list(shapes[0])}, int32 [{self.b}], '
-                             f'int32 [{self.b}] and uint8 [{self.b}] tensors on {self.device} that do not share memory')
-        return tuple(out)
 
     def color(self, rb, score, rx_thr, tx_bias, movable, allowed, pack, out, stream: int) -> ColoringResult:
         """rb: the env's decoded RB plane; movable: the tensor movable() returns; allowed: what the caller passed."""

@@ -680,6 +680,19 @@ class VecD2DEnv:
         """bool [N]: the links that have an action column (links on fixed actions come first and have none)."""
         return np.arange(self.num_links) >= self.num_links - self.num_agents
 
+    def _due_links(self):
+        """bool [N]: the DUE-pair links (the last ones of the link list)."""
+        return np.arange(self.num_links) >= self.num_links - self.num_due_pairs
+
+    def _agent_levels(self):
+        """int32 [num_agents] on the device: the power levels of every agent link's class, what the encode_actions / decode_actions
+        functions take.  self._action_levels, made by the first *_actions call that needs it."""
+        if self._action_levels is None:
+            p = self.num_pwr_actions
+            levels = ([p[self._cue_kind]] * self.num_cues if self.cue_actions == 'agent' else []) + [p['due']] * self.num_due_pairs
+            self._action_levels = torch.as_tensor(np.asarray(levels, dtype=np.int32), device=self.device)
+        return self._action_levels
+
     # ------------------------------------------------------------------ per-RB sensing
     def _rb_sensor(self):
         return self._kernel('_sensor', sensing, sensing.RbSensor, torch_only=False)
@@ -826,11 +839,7 @@ class VecD2DEnv:
         if not np.isfinite(min_gain_db) or min_gain_db < 0.0:
             raise ValueError(f'min_gain_db must be a finite number >= 0, got {min_gain_db!r}')
         best, _, gain = self.best_rb(allowed)
-        if self._action_levels is None:
-            p = self.num_pwr_actions
-            levels = ([p[self._cue_kind]] * self.num_cues if self.cue_actions == 'agent' else []) + [p['due']] * self.num_due_pairs
-            self._action_levels = torch.as_tensor(np.asarray(levels, dtype=np.int32), device=self.device)
-        return best_response.encode_actions(self._t['rb'], self._t['pwr'], best, gain, self._action_levels, float(min_gain_db),
+        return best_response.encode_actions(self._t['rb'], self._t['pwr'], best, gain, self._agent_levels(), float(min_gain_db),
                                             self.num_links - self.num_agents)
 
     def _with_best_rb(self, view):
@@ -935,11 +944,7 @@ class VecD2DEnv:
         (cue_actions='traffic') have no column.  Composes with power_control_actions() the way best_response_actions() does: one
         call picks RBs, the other picks powers."""
         rb = self.best_response_dynamics(allowed, movable, min_gain_db, max_rounds)[0]
-        if self._action_levels is None:
-            p = self.num_pwr_actions
-            levels = ([p[self._cue_kind]] * self.num_cues if self.cue_actions == 'agent' else []) + [p['due']] * self.num_due_pairs
-            self._action_levels = torch.as_tensor(np.asarray(levels, dtype=np.int32), device=self.device)
-        return best_response_dynamics.encode_actions(rb, self._t['pwr'], self._action_levels, self.num_links - self.num_agents)
+        return best_response_dynamics.encode_actions(rb, self._t['pwr'], self._agent_levels(), self.num_links - self.num_agents)
 
     # ------------------------------------------------------------------ what-if evaluation of candidate joint actions
     def _evaluate_kernel(self):
@@ -978,20 +983,17 @@ class VecD2DEnv:
                 or actions.device != self.device:
             raise ValueError(f'actions must be an integer tensor [{self.num_envs}, K, {self.num_agents}] (env, candidate, agent) on '
                              f'{self.device}')
-        if self._action_levels is None:
-            p = self.num_pwr_actions
-            levels = ([p[self._cue_kind]] * self.num_cues if self.cue_actions == 'agent' else []) + [p['due']] * self.num_due_pairs
-            self._action_levels = torch.as_tensor(np.asarray(levels, dtype=np.int32), device=self.device)
+        levels = self._agent_levels()
         first = self.num_links - self.num_agents
         self._follow_torch_stream()
         fixed = (self._t['rb'][:, :first], self._t['pwr'][:, :first]) if first else (None, None)
-        rb, pwr = evaluate_mod.decode_actions(actions, self._action_levels, *fixed)
+        rb, pwr = evaluate_mod.decode_actions(actions, levels, *fixed)
         return k.planes(self._t, rb, pwr, planes, None, self._stream_ptr)
 
     # ------------------------------------------------------------------ optimal one-to-one RB matching
     def _assignment_kernel(self):
         return self._kernel('_assign', assignment, assignment.Assignment,
-                            lambda: (self._agent_links(), np.arange(self.num_links) >= self.num_links - self.num_due_pairs))
+                            lambda: (self._agent_links(), self._due_links()))
 
     def assignment_weights(self, movable=None, allowed=None, objective: str = 'total', harm: bool = False, out=None):
         """What every movable link is worth on every RB, with the background as the last step left it: (weights float32 [B, M, R],
@@ -1047,17 +1049,12 @@ class VecD2DEnv:
         its current power level, encoded rb * power levels + level.  Links on fixed actions (cue_actions='traffic') have no
         column.  Composes with power_control_actions() the way best_response_dynamics_actions() does."""
         rb = self.assign_rbs(movable, allowed, objective)[0]
-        if self._action_levels is None:
-            p = self.num_pwr_actions
-            levels = ([p[self._cue_kind]] * self.num_cues if self.cue_actions == 'agent' else []) + [p['due']] * self.num_due_pairs
-            self._action_levels = torch.as_tensor(np.asarray(levels, dtype=np.int32), device=self.device)
-        return best_response_dynamics.encode_actions(rb, self._t['pwr'], self._action_levels, self.num_links - self.num_agents)
+        return best_response_dynamics.encode_actions(rb, self._t['pwr'], self._agent_levels(), self.num_links - self.num_agents)
 
     # ------------------------------------------------------------------ joint RB and power matching with SINR floors
     def _joint_assignment_kernel(self):
         return self._kernel('_joint', joint_assignment, joint_assignment.JointAssignment,
-                            lambda: (self._agent_links(), np.arange(self.num_links) >= self.num_links - self.num_due_pairs,
-                                     *self._class_bounds()))
+                            lambda: (self._agent_links(), self._due_links(), *self._class_bounds()))
 
     def joint_assignment_weights(self, movable=None, allowed=None, min_sinr_db=None, out=None):
         """What every movable link is worth on every RB at its BEST admissible power, with the background as the last step left
@@ -1175,11 +1172,7 @@ class VecD2DEnv:
         (cue_actions='traffic') have no column.  Composes with power_control_actions() the way best_response_dynamics_actions()
         does: one call picks RBs, the other picks powers."""
         rb = self.color_rbs(margin_db, movable, allowed, power_dbm, pack)[0]
-        if self._action_levels is None:
-            p = self.num_pwr_actions
-            levels = ([p[self._cue_kind]] * self.num_cues if self.cue_actions == 'agent' else []) + [p['due']] * self.num_due_pairs
-            self._action_levels = torch.as_tensor(np.asarray(levels, dtype=np.int32), device=self.device)
-        return best_response_dynamics.encode_actions(rb, self._t['pwr'], self._action_levels, self.num_links - self.num_agents)
+        return best_response_dynamics.encode_actions(rb, self._t['pwr'], self._agent_levels(), self.num_links - self.num_agents)
 
     def _observe(self, view):
         extra = {}

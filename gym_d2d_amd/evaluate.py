@@ -3,7 +3,8 @@
 `Evaluate` owns the device-side constants of one env object (link lists, the columns sensing.fold_columns folds and the capacity
 columns sensing.fold_capacity_columns folds, both unchanged) and launches the kernel on torch's device pointers.  `decode_actions`
 turns action tensors [B, K, num_agents] in step()'s layout into the (rb, tx power) planes [B, K, N] the kernel reads - the inverse of
-best_response.encode_actions / power_control.encode_actions.  Torch path only.
+best_response.encode_actions / power_control.encode_actions.  Torch path only.  The refusal texts are the 'evaluate' row of
+sensing.REFUSALS; the out= predicate its dict goes through (all_fit) is PairKernel's.
 """
 from __future__ import annotations
 
@@ -12,29 +13,14 @@ from typing import Optional
 import numpy as np
 
 from . import _native
-from .sensing import PairKernel, unserved
+from .sensing import PairKernel, refusal_text
 
 PLANES = ('sinr_db', 'capacity_mbps')
 
 
 def refusal(sim, export_actions: bool, use_torch: bool = True) -> Optional[str]:
     """Why this env has no evaluate() (None: it has): the predicate of sensing.unserved under texts of its own."""
-    if not use_torch:
-        return 'evaluate() needs the torch path (use_torch): its planes are device tensors'
-    why = unserved(sim, export_actions)
-    if why is None:
-        return None
-    kind, route = why
-    return {
-        'export_actions': 'evaluate() works in the units of the decoded (rb, tx power) planes and reads them for the links on fixed '
-                          'actions, and export_actions=False does not write them: build the env with export_actions=True',
-        'route': f"evaluate() does not serve the '{route}' path-loss route (a table, not a law its kernel can evaluate for the pairs "
-                 'no step reads); it serves the native power-law models',
-        'shadowing': 'evaluate() does not serve ShadowingPathLoss: a fresh draw per evaluation has no counterfactual (what another '
-                     'assignment would have given is another draw)',
-        'pinned': 'evaluate() does not serve pinned device_config coordinates that float32 cannot hold: their low parts live inside '
-                  'the handle (float64 positions)',
-    }[kind]
+    return refusal_text('evaluate', sim, export_actions, use_torch)
 
 
 def decode_actions(actions, levels, fixed_rb=None, fixed_pwr=None):
@@ -108,10 +94,8 @@ class Evaluate(PairKernel):
                     self.own[name] = torch.empty(shape, dtype=torch.float32, device=self.device)
             res = {name: self.own[name] for name in shapes}
         else:
-            ok = isinstance(out, dict) and set(out) == set(shapes) and all(
-                torch.is_tensor(o) and tuple(o.shape) == shapes[name] and o.dtype == torch.float32 and o.is_contiguous()
-                and o.device == self.device for name, o in out.items())
-            if not ok or len({o.data_ptr() for o in out.values()}) != len(out):
+            if not (isinstance(out, dict) and set(out) == set(shapes)
+                    and self.all_fit([out[name] for name in shapes], list(shapes.values()), (torch.float32,) * len(shapes))):
                 raise ValueError('out must be a dict of contiguous float32 tensors on ' + str(self.device) + ' that do not share '
                                  'memory: ' + ', '.join(f'{name} {list(shape)}' for name, shape in shapes.items()))
             res = {name: out[name] for name in shapes}

@@ -6,6 +6,7 @@ INDEX ORDER: [b, i, j] is receiver-major - i is the receiving link (the agent), 
 The path-loss tables elsewhere in the project are [b, j, i].  `NeighborGraph` owns the device-side constants of one env object (link
 lists, the columns `sensing.fold_columns` folds, so a pair has the bits the step and sense() give it) and the env's own result
 blocks, and launches the three kernels on device pointers: torch tensors on the torch path, plain HIP allocations on the NumPy path.
+The refusal texts are the 'graph' row of sensing.REFUSALS; the torch path's out= predicate (fits) is PairKernel's.
 """
 from __future__ import annotations
 
@@ -14,25 +15,12 @@ from typing import Optional
 import numpy as np
 
 from . import _native
-from .sensing import PairKernel, unserved
+from .sensing import PairKernel, refusal_text
 
 
 def refusal(sim, export_actions: bool) -> Optional[str]:
     """Why this env has no neighbour graph (None: it has one): the predicate of sensing.unserved under the graph's own texts."""
-    why = unserved(sim, export_actions)
-    if why is None:
-        return None
-    kind, route = why
-    return {
-        'export_actions': 'the neighbour graph feeds an observation that gathers the decoded (rb, tx power) planes, which '
-                          'export_actions=False does not write: build the env with export_actions=True',
-        'route': f"the neighbour graph does not serve the '{route}' path-loss route (a table, not a law its kernels can evaluate); "
-                 'it serves the native power-law models',
-        'shadowing': 'the neighbour graph does not serve ShadowingPathLoss: a fresh draw per evaluation has no strongest '
-                     'interferer that holds between resets',
-        'pinned': 'the neighbour graph does not serve pinned device_config coordinates that float32 cannot hold: their low parts '
-                  'live inside the handle (float64 positions)',
-    }[kind]
+    return refusal_text('graph', sim, export_actions)
 
 
 def check_k(k, num_links: int) -> int:
@@ -58,8 +46,7 @@ class NeighborGraph(PairKernel):
             if name not in self.own:
                 self.own[name] = torch.empty(shape, dtype=dtype, device=self.device)
             return self.own[name]
-        if not torch.is_tensor(out) or tuple(out.shape) != tuple(shape) or out.dtype != dtype or not out.is_contiguous() \
-                or out.device != self.device:
+        if not self.fits(out, shape, dtype):
             kind = 'int32' if dtype == torch.int32 else 'float32'
             raise ValueError(f'out must be a contiguous {kind} tensor {list(shape)} on {self.device}')
         return out

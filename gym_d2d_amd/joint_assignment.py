@@ -4,7 +4,8 @@ csrc/d2d_assignpwr.hip).
 `JointAssignment` is assignment.Assignment - the same movable links, allowed words, owned tensors and matching launch - with the
 power alphabet of every link's class (power_control.class_bounds) and the launch that scans it: every movable link's best admissible
 power on every RB and the weight it has there.  The floors take the three forms power_control() takes its targets in.  The matched
-RBs and powers become step()'s action tensor through power_control.encode_actions.  Torch path only.
+RBs and powers become step()'s action tensor through power_control.encode_actions.  Torch path only.  The refusal texts are the
+'assign_rbs_power' row of sensing.REFUSALS, assign_rbs()'s under this name; `lds_bytes` is assignment's.
 """
 from __future__ import annotations
 
@@ -14,6 +15,7 @@ import numpy as np
 
 from . import _native, assignment
 from .power_control import link_values
+from .sensing import refusal_text
 
 
 class JointAssignmentResult(NamedTuple):
@@ -26,16 +28,12 @@ class JointAssignmentResult(NamedTuple):
 
 def refusal(sim, export_actions: bool, use_torch: bool = True) -> Optional[str]:
     """Why this env has no assign_rbs_power() (None: it has): assign_rbs()'s reasons, word for word, under this name."""
-    why = assignment.refusal(sim, export_actions, use_torch)
-    return None if why is None else why.replace('assign_rbs()', 'assign_rbs_power()')
+    return refusal_text('assign_rbs_power', sim, export_actions, use_torch)
 
 
-def lds_bytes(num_links: int, num_rbs: int, power_law: bool) -> int:
-    """The LDS one workgroup of the kernel needs (the header's formula, d2d_assign_weights's: the floors ride in words that kernel
-    has too): at most _native.ASSIGNPWR_MAX_LDS_BYTES is served."""
-    r16 = lambda x: (x + 15) & ~15
-    n, n4 = num_links, (num_links + 3) & ~3
-    return 48 * n + (r16(8 * n) if power_law else 0) + r16(8 * n4) + 3 * r16(4 * n) + r16(4 * (num_rbs + 1))
+# the LDS one workgroup of the kernel needs is d2d_assign_weights's formula (the floors ride in words that kernel has too): at most
+# _native.ASSIGNPWR_MAX_LDS_BYTES is served
+lds_bytes = assignment.lds_bytes
 
 
 def check_alphabet(p_min, p_max, links=None) -> None:
@@ -95,10 +93,9 @@ class JointAssignment(assignment.Assignment):
         else:
             w, pw = self._check_out(out, names, (shape, shape), dtypes)
         mask = self.words(allowed)                   # lives until the launch is enqueued; the stream orders its release behind it
-        _native.assign_power_weights(t['pos_x'].data_ptr(), t['pos_y'].data_ptr(), t['rb'].data_ptr(), t['pwr'].data_ptr(), *self.ptrs,
-                                     self.law, self.pow_k, self.b, self.d, self.n, self.r, links.data_ptr(), m,
-                                     0 if mask is None else mask.data_ptr(), self.p_min.data_ptr(), self.p_max.data_ptr(),
-                                     0 if floors is None else floors.data_ptr(), w.data_ptr(), pw.data_ptr(), stream)
+        _native.assign_power_weights(*self.launch_args(t), links.data_ptr(), m, 0 if mask is None else mask.data_ptr(),
+                                     self.p_min.data_ptr(), self.p_max.data_ptr(), 0 if floors is None else floors.data_ptr(),
+                                     w.data_ptr(), pw.data_ptr(), stream)
         return w, pw, links
 
     def assign_power(self, t: dict, movable, allowed, floors, out, stream: int) -> JointAssignmentResult:

@@ -2,7 +2,8 @@
 
 `PowerControl` owns the device-side constants of one env object (link lists, the columns sensing.fold_columns folds, unchanged, the
 power bounds of every link's class) and launches the kernel on torch's device pointers.  `class_bounds` gives the bounds,
-`encode_actions` turns the solved powers into the action tensor VecD2DEnv.step() takes.  Torch path only.
+`encode_actions` turns the solved powers into the action tensor VecD2DEnv.step() takes.  Torch path only.  The refusal texts are the 'power_control' row of
+sensing.REFUSALS; the out= check and the owned outputs (declare_outputs, outputs) and the launch prefix (launch_args) are PairKernel's.
 """
 from __future__ import annotations
 
@@ -11,7 +12,7 @@ from typing import NamedTuple, Optional
 import numpy as np
 
 from . import _native
-from .sensing import PairKernel, unserved
+from .sensing import PairKernel, refusal_text
 
 
 class PowerControlResult(NamedTuple):
@@ -24,22 +25,7 @@ class PowerControlResult(NamedTuple):
 
 def refusal(sim, export_actions: bool, use_torch: bool = True) -> Optional[str]:
     """Why this env has no power_control() (None: it has): the predicate of sensing.unserved under texts of its own."""
-    if not use_torch:
-        return 'power_control() needs the torch path (use_torch): its planes are device tensors'
-    why = unserved(sim, export_actions)
-    if why is None:
-        return None
-    kind, route = why
-    return {
-        'export_actions': 'power_control() reads the decoded (rb, tx power) planes, which export_actions=False does not write: build '
-                          'the env with export_actions=True',
-        'route': f"power_control() does not serve the '{route}' path-loss route (a table, not a law its kernel can evaluate for the "
-                 'powers no step has applied); it serves the native power-law models',
-        'shadowing': 'power_control() does not serve ShadowingPathLoss: a fresh draw per evaluation has no fixed point (the SINR a '
-                     'power was solved for is another draw than the one the next step sees)',
-        'pinned': 'power_control() does not serve pinned device_config coordinates that float32 cannot hold: their low parts live '
-                  'inside the handle (float64 positions)',
-    }[kind]
+    return refusal_text('power_control', sim, export_actions, use_torch)
 
 
 def class_bounds(num_pwr_actions: dict, cue_kind: str, num_cues: int, num_due_pairs: int):
@@ -99,7 +85,8 @@ class PowerControl(PairKernel):
         self.agent = np.asarray(agent, dtype=bool)                   # links that have an action column: the only ones ever adjusted
         if not (p_min.shape == p_max.shape == self.agent.shape == (self.n,)) or (p_min > p_max).any() or np.abs(p_max).max() >= 4096:
             raise ValueError('the power bounds do not match the env')
-        self.own = None                              # the four outputs this object owns, allocated by the first call without out=
+        self.declare_outputs(PowerControlResult._fields, ((self.b, self.n), (self.b, self.n), (self.b,), (self.b,)),
+                             (torch.int32, torch.float32, torch.int32, torch.uint8))
         self.p_min, self.p_max = (torch.as_tensor(a, device=device) for a in (p_min, p_max))
         self._target = None                          # (key, tensor) of the last call: a repeated target is not uploaded again
 
@@ -111,31 +98,13 @@ class PowerControl(PairKernel):
         """uint8 [N] on the device: the agent links (None), or those of them `adjustable` (bool [N], array or tensor) marks."""
         return self.agent_subset(adjustable, 'adjustable')
 
-    def outputs(self, out):
-        torch = self.torch
-        shapes = ((self.b, self.n), (self.b, self.n), (self.b,), (self.b,))
-        dtypes = (torch.int32, torch.float32, torch.int32, torch.uint8)
-        if out is None:
-            if self.own is None:
-                self.own = tuple(torch.empty(s, dtype=dt, device=self.device) for s, dt in zip(shapes, dtypes))
-            return self.own
-        ok = isinstance(out, (tuple, list)) and len(out) == 4 and all(
-            torch.is_tensor(o) and tuple(o.shape) == s and o.dtype == dt and o.is_contiguous() and o.device == self.device
-            for o, s, dt in zip(out, shapes, dtypes))
-        if not ok or len({o.data_ptr() for o in out}) != 4:
-            raise ValueError(f'out must be (power_dbm, sinr_db, iters, converged): contiguous int32 {list(shapes[0])}, float32 '
-                             f'{list(shapes[1])}, int32 [{self.b}] and uint8 [{self.b}] tensors on {self.device} that do not share '
-                             'memory')
-        return tuple(out)
-
     def solve(self, t: dict, target, adjustable, max_iters: int, out, stream: int, env_mask=None) -> PowerControlResult:
         """target, adjustable: the tensors target() and adjustable() return."""
         if isinstance(max_iters, bool) or not isinstance(max_iters, (int, np.integer)) or max_iters < 1:
             raise ValueError(f'max_iters must be an int >= 1, got {max_iters!r}')
         power, sinr, iters, conv = self.outputs(out)
         mask = self.env_mask(env_mask)               # lives until the launch is enqueued; the stream orders its release behind it
-        _native.power_control(t['pos_x'].data_ptr(), t['pos_y'].data_ptr(), t['rb'].data_ptr(), t['pwr'].data_ptr(), *self.ptrs,
-                              self.law, self.pow_k, self.b, self.d, self.n, self.r, target.data_ptr(), self.p_min.data_ptr(),
-                              self.p_max.data_ptr(), adjustable.data_ptr(), int(max_iters), 0 if mask is None else mask.data_ptr(),
-                              power.data_ptr(), sinr.data_ptr(), iters.data_ptr(), conv.data_ptr(), stream)
+        _native.power_control(*self.launch_args(t), target.data_ptr(), self.p_min.data_ptr(), self.p_max.data_ptr(), adjustable.data_ptr(),
+                              int(max_iters), 0 if mask is None else mask.data_ptr(), power.data_ptr(), sinr.data_ptr(),
+                              iters.data_ptr(), conv.data_ptr(), stream)
         return PowerControlResult(power, sinr, iters, conv)

@@ -1,10 +1,13 @@
-"""Per-RB interference sensing: the host side of libd2d_sense.so (include/d2d_sense.h, csrc/d2d_sense.hip).
+"""Per-RB interference sensing: the host side of libd2d_sense.so (include/d2d_sense.h, csrc/d2d_sense.hip), and what the host
+modules of all the stateless pair kernels share.
 
 `fold_columns` lowers the per-device link-budget and power-law columns to the float32 block the kernel reads, in double precision
 and by the rules the step's own records follow (csrc/d2d_capi.hip, refresh_tables), so that the sensed column of a link's own RB is
-the step's sinr_db.  `PairKernel` is the opening every stateless pair kernel's class shares: it owns the device-side constants of one
-env object (link lists, columns) - torch tensors on the torch path, plain HIP allocations on the NumPy path.  `RbSensor` derives
-from it and launches the sensing kernel on device pointers.
+the step's sinr_db.  `unserved` is the one predicate of what these kernels cannot serve and `refusal_text` the one place that words
+it: every module's `refusal` is a row of `REFUSALS`.  `PairKernel` is the opening every kernel's class shares: it owns the
+device-side constants of one env object (link lists, columns) - torch tensors on the torch path, plain HIP allocations on the NumPy
+path - and states once the out= predicate (`fits`, `all_fit`), the owned result tuple (`declare_outputs`, `outputs`) and the leading
+launch arguments (`launch_args`).  `RbSensor` derives from it and launches the sensing kernel on device pointers.
 """
 from __future__ import annotations
 
@@ -74,22 +77,65 @@ def unserved(sim, export_actions: bool) -> Optional[Tuple[str, str]]:
     return None
 
 
-def refusal(sim, export_actions: bool) -> Optional[str]:
-    """Why this env cannot be sensed (None: it can).  Each text names the route or the switch."""
+# What differs between the APIs' refusal texts, by API: (subject, what it does with the decoded planes that export_actions=False
+# does not write, what cannot evaluate a table route, what a fresh shadowing draw per evaluation does not have, which of its
+# results are device tensors - None where the API has a NumPy path).  A new family adds its row here.
+_READS = 'reads the decoded (rb, tx power) planes, which export_actions=False does not write'
+_UNITS = 'works in the units of the decoded (rb, tx power) planes and reads them for the {}, and export_actions=False does not write them'
+_PAIRS = 'its kernel can evaluate for the pairs no step reads'
+_OTHER_RB = 'counterfactual (what another RB would have given is another draw)'
+_OTHER_ASSIGNMENT = 'counterfactual (what another assignment would have given is another draw)'
+REFUSALS = {
+    'sense': ('sense()', _READS, 'the sensing kernel can evaluate for the pairs no step reads', _OTHER_RB, None),
+    'graph': ('the neighbour graph',
+              'feeds an observation that gathers the decoded (rb, tx power) planes, which export_actions=False does not write',
+              'its kernels can evaluate', 'strongest interferer that holds between resets', None),
+    'marginal_capacity': ('marginal_capacity()', _READS, "its kernel can evaluate from the transmitter's side",
+                          'counterfactual (the step without one link would be another draw)', None),
+    'best_rb': ('best_rb()', _READS, _PAIRS, _OTHER_RB, 'planes'),
+    'power_control': ('power_control()', _READS, 'its kernel can evaluate for the powers no step has applied',
+                      'fixed point (the SINR a power was solved for is another draw than the one the next step sees)', 'planes'),
+    'best_response_dynamics': ('best_response_dynamics()', _READS, 'its kernel can evaluate for the RBs no step has applied',
+                               'best response (the SINR a move was made for is another draw than the one the next link sees)',
+                               'planes'),
+    'evaluate': ('evaluate()', _UNITS.format('links on fixed actions'), _PAIRS, _OTHER_ASSIGNMENT, 'planes'),
+    'assign_rbs': ('assign_rbs()', _UNITS.format('background links'), _PAIRS, _OTHER_ASSIGNMENT, 'planes'),
+    'color_rbs': ('color_rbs()', _READS, 'coupling() can evaluate for the pairs no step reads',
+                  'conflict graph (the pair a colour was chosen for is another draw than the one the next step sees)',
+                  'graph and planes'),
+}
+REFUSALS['assign_rbs_power'] = ('assign_rbs_power()', *REFUSALS['assign_rbs'][1:])      # assign_rbs()'s reasons under its own name
+
+
+def refusal_text(api: str, sim, export_actions: bool, use_torch: Optional[bool] = None) -> Optional[str]:
+    """Why this env cannot have `api`, a key of REFUSALS (None: it can).  Each text names the route or the switch; use_torch is
+    passed by the APIs that have the torch path only."""
+    subject, planes, law, draw, tensors = REFUSALS[api]
+    if use_torch is not None and not use_torch:
+        return f'{subject} needs the torch path (use_torch): its {tensors} are device tensors'
     why = unserved(sim, export_actions)
     if why is None:
         return None
     kind, route = why
-    return {
-        'export_actions': 'sense() reads the decoded (rb, tx power) planes, which export_actions=False does not write: build the env '
-                          'with export_actions=True',
-        'route': f"sense() does not serve the '{route}' path-loss route (a table, not a law the sensing kernel can evaluate for the "
-                 'pairs no step reads); it serves the native power-law models',
-        'shadowing': 'sense() does not serve ShadowingPathLoss: a fresh draw per evaluation has no counterfactual (what another RB '
-                     'would have given is another draw)',
-        'pinned': 'sense() does not serve pinned device_config coordinates that float32 cannot hold: their low parts live inside '
-                  'the handle (float64 positions)',
-    }[kind]
+    if kind == 'export_actions':
+        return f'{subject} {planes}: build the env with export_actions=True'
+    if kind == 'route':
+        return f"{subject} does not serve the '{route}' path-loss route (a table, not a law {law}); it serves the native power-law models"
+    if kind == 'shadowing':
+        return f'{subject} does not serve ShadowingPathLoss: a fresh draw per evaluation has no {draw}'
+    return (f'{subject} does not serve pinned device_config coordinates that float32 cannot hold: their low parts live inside the '
+            'handle (float64 positions)')
+
+
+def refusal(sim, export_actions: bool) -> Optional[str]:
+    """Why this env cannot be sensed (None: it can)."""
+    return refusal_text('sense', sim, export_actions)
+
+
+def r16(x: int) -> int:
+    """x rounded up to a multiple of 16, as the kernels lay out their LDS (round16 of csrc/d2d_same_rb.h): for the lds_bytes
+    functions."""
+    return (x + 15) & ~15
 
 
 class _HipMemory:
@@ -185,6 +231,45 @@ class PairKernel:
             self._subset = (key, torch.as_tensor(host.astype(np.uint8), device=self.device))
         return self._subset[1]
 
+    # ------------------------------------------------------------------ out=, the owned results and the launch prefix, stated once
+    def fits(self, o, shape, dtype) -> bool:
+        """Is `o` a contiguous tensor of this shape and dtype on the env's device?  The single-tensor form of the out= predicate."""
+        return self.torch.is_tensor(o) and tuple(o.shape) == tuple(shape) and o.dtype == dtype and o.is_contiguous() \
+            and o.device == self.device
+
+    def all_fit(self, out, shapes, dtypes) -> bool:
+        """The out= predicate: is `out` a tuple or list of len(shapes) tensors, each of which fits() its slot and no two of which
+        share memory?  What is no sequence is refused before anything is asked of its entries."""
+        return isinstance(out, (tuple, list)) and len(out) == len(shapes) \
+            and all(self.fits(o, s, dt) for o, s, dt in zip(out, shapes, dtypes)) and len({o.data_ptr() for o in out}) == len(shapes)
+
+    def declare_outputs(self, names, shapes, dtypes, message: Optional[str] = None) -> None:
+        """What a class with a fixed result tuple states once, in __init__: the slots of outputs() and what its refusal says -
+        `message`, or the shared format made from the declaration."""
+        self.out_shapes, self.out_dtypes = tuple(shapes), tuple(dtypes)
+        kinds = [f'{str(dt).replace("torch.", "")} {list(s)}' for s, dt in zip(shapes, dtypes)]
+        self.out_message = message or (f'out must be ({", ".join(names)}): contiguous {", ".join(kinds[:-1])} and {kinds[-1]} tensors '
+                                       f'on {self.device} that do not share memory')
+        self.own = None                              # the result tuple this object owns, allocated by the first call without out=
+
+    def outputs(self, out) -> tuple:
+        """The declared result tuple: the one this object owns (None), or `out` if it passes all_fit(), else ValueError."""
+        if out is None:
+            if self.own is None:
+                self.own = tuple(self.torch.empty(s, dtype=dt, device=self.device) for s, dt in zip(self.out_shapes, self.out_dtypes))
+            return self.own
+        if not self.all_fit(out, self.out_shapes, self.out_dtypes):
+            raise ValueError(self.out_message)
+        return tuple(out)
+
+    def raw_launch_args(self, pos_x: int, pos_y: int, rb: int, pwr: int) -> tuple:
+        """The arguments every kernel that reads the four planes begins with, from their device pointers."""
+        return (pos_x, pos_y, rb, pwr, *self.ptrs, self.law, self.pow_k, self.b, self.d, self.n, self.r)
+
+    def launch_args(self, t: dict) -> tuple:
+        """raw_launch_args of the planes dict `t` of the torch path."""
+        return self.raw_launch_args(t['pos_x'].data_ptr(), t['pos_y'].data_ptr(), t['rb'].data_ptr(), t['pwr'].data_ptr())
+
     def close(self) -> None:
         if self.torch is None:
             self.mem.close()
@@ -197,9 +282,6 @@ class RbSensor(PairKernel):
         super().__init__(sim, num_links, torch, device, api='sense', max_rbs=_native.SENSE_MAX_RBS)
         self.own = None                              # the result block this object owns, allocated by the first call without out=
 
-    def launch(self, pos_x: int, pos_y: int, rb: int, pwr: int, what: int, out: int, stream: int = 0) -> None:
-        _native.sense_rb(pos_x, pos_y, rb, pwr, *self.ptrs, self.law, self.pow_k, self.b, self.d, self.n, self.r, what, out, stream)
-
     def sense_torch(self, t: dict, what: int, out, stream: int):
         torch = self.torch
         shape = (self.b, self.n, self.r)
@@ -207,10 +289,9 @@ class RbSensor(PairKernel):
             if self.own is None:
                 self.own = torch.empty(shape, dtype=torch.float32, device=self.device)
             out = self.own
-        elif not torch.is_tensor(out) or tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() \
-                or out.device != self.device:
+        elif not self.fits(out, shape, torch.float32):
             raise ValueError(f'out must be a contiguous float32 tensor {list(shape)} on {self.device}')
-        self.launch(t['pos_x'].data_ptr(), t['pos_y'].data_ptr(), t['rb'].data_ptr(), t['pwr'].data_ptr(), what, out.data_ptr(), stream)
+        _native.sense_rb(*self.launch_args(t), what, out.data_ptr(), stream)
         return out
 
     def sense_numpy(self, what: int, out):
@@ -220,10 +301,10 @@ class RbSensor(PairKernel):
                                 or not out.flags.c_contiguous):
             raise ValueError(f'out must be a C-contiguous float32 ndarray {list(shape)}')
         h.synchronize()                               # the planes are the last step's; the kernel runs on the null stream
-        ptr = {w: h.get_buffer(w)[0] for w in (_native.BUF_POS_X, _native.BUF_POS_Y, _native.BUF_RB, _native.BUF_PWR)}
+        planes = [h.get_buffer(w)[0] for w in (_native.BUF_POS_X, _native.BUF_POS_Y, _native.BUF_RB, _native.BUF_PWR)]
         if self.own is None:
             self.own = self.mem.alloc(self.b * self.n * self.r * 4)
-        self.launch(ptr[_native.BUF_POS_X], ptr[_native.BUF_POS_Y], ptr[_native.BUF_RB], ptr[_native.BUF_PWR], what, self.own)
+        _native.sense_rb(*self.raw_launch_args(*planes), what, self.own, 0)
         res = out if out is not None else np.empty(shape, dtype=np.float32)
         self.mem.download(self.own, res)              # synchronous on the null stream: behind the kernel
         return res
