@@ -1,5 +1,5 @@
-"""ctypes binding of libd2d_hip.so (include/d2d_hip.h) and of the side libraries `SIDE`, `SOLVERS` and `ADDONS` list (libd2d_<name>.so,
-include/d2d_<name>.h).
+"""ctypes binding of libd2d_hip.so (include/d2d_hip.h) and of the side libraries `SIDE`, `SOLVERS`, `ADDONS` and `FAMILIES` list
+(libd2d_<name>.so, include/d2d_<name>.h).
 There is no CPU fallback: if a library or a gfx950 GPU is missing, the calls below raise."""
 from __future__ import annotations
 
@@ -86,6 +86,12 @@ ASSIGNPWR_NO_POWER = -32768
 COLOR_MAX_LINKS = 2048
 COLOR_MAX_RBS = 8192
 COLOR_MAX_LDS_BYTES = 163840
+# d2d_balance_sinr's law / limits (include/d2d_balance.h): d2d_power_control's, the levels of the grid and the LDS of one workgroup
+BALANCE_LAW_INV_SQUARE, BALANCE_LAW_POWER, BALANCE_LAW_POW_K = 0, 1, 2
+BALANCE_MAX_LINKS = 2048
+BALANCE_MAX_RBS = 8192
+BALANCE_MAX_MARGINS = 4096
+BALANCE_MAX_LDS_BYTES = 163840
 
 BUFFER_DTYPES = {BUF_ACTIONS: np.int32, BUF_RB: np.int32, BUF_PWR: np.int32, BUF_ENV_FLAGS: np.int32, BUF_RESET_PENDING: np.int32,
                  BUF_EPISODE: np.uint32}
@@ -265,6 +271,13 @@ COLOR_SIGNATURES = {
     'd2d_color_last_error': (C.c_char_p, []),
 }
 
+# every symbol include/d2d_balance.h declares
+BALANCE_SIGNATURES = {
+    'd2d_balance_sinr': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _I, _I, C.c_int64, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P,
+                                   _P, _P, _P]),
+    'd2d_balance_last_error': (C.c_char_p, []),
+}
+
 # the side libraries: name -> every symbol include/d2d_<name>.h declares; libd2d_<name>.so, its error text in d2d_<name>_last_error
 SIDE = {'plugin': PLUGIN_SIGNATURES, 'episode': EPISODE_SIGNATURES, 'sense': SENSE_SIGNATURES, 'graph': GRAPH_SIGNATURES,
         'marginal': MARGINAL_SIGNATURES, 'mobility': MOBILITY_SIGNATURES, 'channel': CHANNEL_SIGNATURES, 'queue': QUEUE_SIGNATURES,
@@ -273,6 +286,8 @@ SIDE = {'plugin': PLUGIN_SIGNATURES, 'episode': EPISODE_SIGNATURES, 'sense': SEN
 SOLVERS = {'assign': ASSIGN_SIGNATURES}
 # build.ADDONS' libraries, likewise: the table later add-on kernel families join
 ADDONS = {'assignpwr': ASSIGNPWR_SIGNATURES, 'color': COLOR_SIGNATURES}
+# build.FAMILIES' libraries, likewise: the table the kernel families since then join
+FAMILIES = {'balance': BALANCE_SIGNATURES}
 
 _lib: Optional[C.CDLL] = None
 _side: dict = {}                    # name -> the opened, typed side library
@@ -288,6 +303,7 @@ assign_weights_launches = 0         # d2d_assign_weights launches made through a
 assign_solve_launches = 0           # d2d_assign_solve launches made through assign_solve()
 assign_power_weights_launches = 0   # d2d_assign_power_weights launches made through assign_power_weights()
 color_launches = 0                  # d2d_color_graph launches made through color_graph()
+balance_launches = 0                # d2d_balance_sinr launches made through balance_sinr()
 mobility_launches = 0               # d2d_mobility_move calls made through mobility_move()
 channel_launches = 0                # d2d_channel_fill calls made through channel_fill()
 queue_launches = 0                  # d2d_queue_step calls made through queue_step()
@@ -317,14 +333,14 @@ def side_path(name: str) -> Path:
 
 
 def side_library(name: str) -> C.CDLL:
-    """dlopen libd2d_<name>.so once and type the entry points SIDE[name] (or SOLVERS[name], ADDONS[name]) lists.  Raises if it has not been built."""
+    """dlopen libd2d_<name>.so once and type the entry points SIDE[name] (or SOLVERS[name], ADDONS[name], FAMILIES[name]) lists.  Raises if it has not been built."""
     lib = _side.get(name)
     if lib is None:
         path = side_path(name)
         if not path.exists():
             raise ImportError(f'{path} is missing - build it with `python -m gym_d2d_amd.build`')
         lib = C.CDLL(str(path))
-        for symbol, (res, args) in (SIDE.get(name) or SOLVERS.get(name) or ADDONS[name]).items():
+        for symbol, (res, args) in (SIDE.get(name) or SOLVERS.get(name) or ADDONS.get(name) or FAMILIES[name]).items():
             fn = getattr(lib, symbol)
             fn.restype = res
             fn.argtypes = args
@@ -354,6 +370,7 @@ def load_evaluate_library() -> C.CDLL: return side_library('evaluate')
 def load_assign_library() -> C.CDLL: return side_library('assign')
 def load_assignpwr_library() -> C.CDLL: return side_library('assignpwr')
 def load_color_library() -> C.CDLL: return side_library('color')
+def load_balance_library() -> C.CDLL: return side_library('balance')
 
 
 # Pointer arguments are passed as the ints they are: every argtype is c_void_p, which takes 0 as the null pointer and any int up to
@@ -544,6 +561,24 @@ def color_graph(score_ptr: int, tx_bias_ptr: int, rx_thr_ptr: int, rb_ptr: int, 
         conflicts_ptr, rbs_used_ptr, proper_ptr, stream_ptr))
     if n_envs:
         color_launches += 1
+
+
+def balance_sinr(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, link_tx_ptr: int, link_rx_ptr: int, cols_ptr: int, law: int,
+                 pow_k: int, n_envs: int, n_dev: int, n_links: int, n_rbs: int, base_ptr: int, floor_ptr: int, margins_ptr: int,
+                 n_margins: int, p_min_ptr: int, p_max_ptr: int, adjustable_ptr: int, max_iters: int, env_mask_ptr: int, power_ptr: int,
+                 sinr_ptr: int, margin_ptr: int, level_ptr: int, probes_ptr: int, stream_ptr: int = 0) -> None:
+    """d2d_balance_sinr: the max-min SINR search of every env in one launch - power_dbm int32 and sinr_db float32 [n_envs, n_links],
+    margin_db float32, level and probes int32 [n_envs] (device pointers; base float32 [n_links]; floor_ptr 0: no floors, else float32
+    [n_links], -inf: none for that link; margins float32 [n_margins], ascending; p_min / p_max int32 [n_links]; adjustable_ptr 0:
+    every link, else uint8 [n_links]; env_mask_ptr 0: every env, else uint8 [n_envs] and the envs whose byte is 0 keep their
+    rows)."""
+    global balance_launches
+    _check_side('balance', load_balance_library().d2d_balance_sinr(
+        pos_x_ptr, pos_y_ptr, rb_ptr, pwr_ptr, link_tx_ptr, link_rx_ptr, cols_ptr, law, pow_k, n_envs, n_dev, n_links, n_rbs,
+        base_ptr, floor_ptr, margins_ptr, n_margins, p_min_ptr, p_max_ptr, adjustable_ptr, max_iters, env_mask_ptr, power_ptr,
+        sinr_ptr, margin_ptr, level_ptr, probes_ptr, stream_ptr))
+    if n_envs:
+        balance_launches += 1
 
 
 def mobility_move(pos_x_ptr: int, pos_y_ptr: int, vel_x_ptr: int, vel_y_ptr: int, fixed_mask_ptr: int, n_envs: int, n_cues: int,

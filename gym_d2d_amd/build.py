@@ -1,4 +1,4 @@
-"""Build every shared library of `LIBRARIES`, `SOLVERS` and `ADDONS` for gfx950 with hipcc - in-tree, so the .so files travel with the repo snapshot.
+"""Build every shared library of `LIBRARIES`, `SOLVERS`, `ADDONS` and `FAMILIES` for gfx950 with hipcc - in-tree, so the .so files travel with the repo snapshot.
 
     stem      libd2d_<stem>.so                                        public header
     hip       the product: the C ABI                                  include/d2d_hip.h
@@ -7,6 +7,7 @@
     assign    the RB matching, listed in SOLVERS        include/d2d_assign.h
     assignpwr the joint RB and power weights (4.17), listed in ADDONS   include/d2d_assignpwr.h
     color     the conflict-graph RB colouring (4.18), listed in ADDONS   include/d2d_color.h
+    balance   the max-min SINR balancing (4.19), listed in FAMILIES      include/d2d_balance.h
 
     python -m gym_d2d_amd.build [--force] [--verbose]
     D2D_BUILD_DIAG=1 python -m gym_d2d_amd.build      # diagnostic build of libd2d_hip.so: the A/B tuning keys and the ablation
@@ -37,12 +38,19 @@ LIBRARIES = {'hip': SOURCES, 'probe': ['d2d_probe.hip'],
 SOLVERS = {'assign': ['d2d_assign.hip']}
 BUILT = {**LIBRARIES, **SOLVERS}
 # further stateless kernel families (which _native.ADDONS mirrors): built and stamped with the rest, and a missing one is rebuilt
-# (addons_built() for the row the table opened with, addons_missing() for every row).  This table is the one that grows.
+# (addons_built() for the row the table opened with, addons_missing() for every row).  Its two rows are fixed, as the tables above
+# are: what joins the build now joins FAMILIES below.
 # assignpwr: the joint RB and power weights; color: the conflict-graph RB colouring (4.18)
 ADDONS = {'assignpwr': ['d2d_assignpwr.hip'], 'color': ['d2d_color.hip']}
-EVERYTHING = {**BUILT, **ADDONS}                 # what build() compiles and links, in order
-HEADERS = [CSRC / 'd2d_internal.h', CSRC / 'd2d_plan.h', CSRC / 'd2d_step_device.h', CSRC / 'd2d_store.h', CSRC / 'd2d_same_rb.h', CSRC / 'd2d_addon.h', INCLUDE / 'd2d_hip.h', INCLUDE / 'd2d_hip_diag.h',
-           *(INCLUDE / f'd2d_{stem}.h' for stem in EVERYTHING if stem not in ('hip', 'probe'))]
+EVERYTHING = {**BUILT, **ADDONS}                 # what build() compiles and links first, in order
+# the stateless kernel families that joined since (which _native.FAMILIES mirrors): compiled and linked behind EVERYTHING, stamped with
+# the rest, and a missing one is rebuilt (families_missing()).  This table is the one that grows.
+# balance: the max-min SINR balancing
+FAMILIES = {'balance': ['d2d_balance.hip']}
+TARGETS = {**EVERYTHING, **FAMILIES}             # every library of the build: what the digest, the compile and the link iterate
+HEADERS = [CSRC / 'd2d_internal.h', CSRC / 'd2d_plan.h', CSRC / 'd2d_step_device.h', CSRC / 'd2d_store.h', CSRC / 'd2d_same_rb.h', CSRC / 'd2d_addon.h',
+           CSRC / 'd2d_powerctl_device.h', INCLUDE / 'd2d_hip.h', INCLUDE / 'd2d_hip_diag.h',
+           *(INCLUDE / f'd2d_{stem}.h' for stem in TARGETS if stem not in ('hip', 'probe'))]
 
 
 def lib_path(stem: str, lib_dir: Path = LIB_DIR) -> Path:
@@ -70,7 +78,7 @@ def _hipcc() -> str:
 
 def digest_files() -> list:
     """The files source_digest() hashes, in order: every library's sources, then the headers."""
-    return [p for p in [CSRC / s for sources in EVERYTHING.values() for s in sources] + HEADERS if p.exists()]
+    return [p for p in [CSRC / s for sources in TARGETS.values() for s in sources] + HEADERS if p.exists()]
 
 
 def source_digest() -> str:
@@ -106,16 +114,21 @@ def addons_missing(lib_dir: Path = LIB_DIR) -> list:
     return [stem for stem in ADDONS if not lib_path(stem, lib_dir).exists()]
 
 
+def families_missing(lib_dir: Path = LIB_DIR) -> list:
+    """The stems of FAMILIES whose library is not there, in the table's order: a missing one is rebuilt."""
+    return [stem for stem in FAMILIES if not lib_path(stem, lib_dir).exists()]
+
+
 def build(force: bool = False, verbose: bool = False) -> Path:
     LIB_DIR.mkdir(exist_ok=True)
     digest = source_digest()
-    if not force and up_to_date(digest) and solvers_built() and addons_built() and not addons_missing():
+    if not force and up_to_date(digest) and solvers_built() and addons_built() and not addons_missing() and not families_missing():
         return LIB_PATH
     hipcc = _hipcc()
     obj_dir = LIB_DIR / 'obj'
     obj_dir.mkdir(exist_ok=True)
     procs = []
-    for s in [s for sources in EVERYTHING.values() for s in sources]:
+    for s in [s for sources in TARGETS.values() for s in sources]:
         src = CSRC / s
         obj = obj_dir / (src.stem + '.o')
         cmd = [hipcc, *FLAGS, '-I', str(INCLUDE), '-c', str(src), '-o', str(obj)]
@@ -128,7 +141,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
             raise RuntimeError(f'hipcc failed on {s}:\n{out}')
         if verbose and out.strip():
             print(out)
-    for stem, sources in EVERYTHING.items():
+    for stem, sources in TARGETS.items():
         objs = [str(obj_dir / (Path(s).stem + '.o')) for s in sources]
         cmd = [hipcc, '-shared', '-fPIC', f'--offload-arch={ARCH}', '-o', str(lib_path(stem)), *objs]
         if verbose:

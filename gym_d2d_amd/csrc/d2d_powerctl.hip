@@ -25,8 +25,8 @@
 
 #include "d2d_addon.h"
 #include "d2d_powerctl.h"
+#include "d2d_powerctl_device.h"
 #include "d2d_same_rb.h"
-#include "d2d_step_device.h"
 
 namespace {
 
@@ -34,7 +34,7 @@ using namespace d2d;
 
 constexpr int PC_THREADS = 256;
 constexpr int PC_WAVES = PC_THREADS / 64;
-constexpr unsigned NO_RB = 0x80000000u;                          // range word of a link on no RB
+constexpr unsigned NO_RB = PC_NO_RB;                             // range word of a link on no RB (d2d_powerctl_device.h)
 static_assert(D2D_POWERCTL_MAX_LINKS == SAME_RB_MAX_LINKS && D2D_POWERCTL_MAX_RBS == SAME_RB_MAX_RBS, "the limits of the shared sort (d2d_same_rb.h)");
 static_assert(D2D_POWERCTL_LAW_INV_SQUARE == LAW_INV_SQUARE && D2D_POWERCTL_LAW_POWER == LAW_POWER && D2D_POWERCTL_LAW_POW_K == LAW_POW_K, "the laws check_law() knows (d2d_addon.h)");
 static_assert(D2D_POWERCTL_MAX_LINKS < (1 << 15), "a range word packs two slot indices into 16 bits each under the NO_RB bit");
@@ -86,27 +86,6 @@ __device__ __forceinline__ Lds carve_lds(unsigned char* smem, const PowerArgs& a
     s.start = reinterpret_cast<int*>(smem + a.off_start);
     s.flag = reinterpret_cast<int*>(smem + a.off_flag);
     return s;
-}
-
-// sinr_db of the link in slot k under the linear powers z, as the step forms it; the caller has checked that the link is on an RB
-template <int MODE>
-__device__ __forceinline__ float slot_sinr_db(const Lds& s, const float* z, int k, unsigned range, int pow_k) {
-    constexpr bool POWLAW = MODE != PL_INV_SQUARE;
-    const float4 rx = s.rxa[k];                                          // rx x, rx y, rx_pl, noise
-    const float2 own = s.rxb[k];                                         // own-pair gain, rx_lin
-    const float sig = z[k] * own.x * rx.z * own.y;                       // simulator.py:93
-    const int q_end = (int)(range >> 16);
-    double acc = 0.0;
-    for (int q = (int)(range & 0xFFFFu); q < q_end; ++q) {
-        const float4 o = s.tx[q];
-        const float dx = o.x - rx.x, dy = o.y - rx.y;
-        const float d2 = fmaf(dx, dx, dy * dy);
-        const float g = pair_gain<MODE>(d2, POWLAW ? s.hh[q] : make_float2(-1.0f, 0.0f), pow_k);
-        const float term = z[q] * g;                                     // simulator.py:97-101, linear mW
-        acc += q != k ? (double)term : 0.0;                              // j != i: slots and links correspond one to one
-    }
-    const float accf = (float)acc;
-    return 3.01029995663981195f * __builtin_amdgcn_logf(precise_div(sig, fmaf(accf, rx.z, rx.w)));
 }
 
 template <int MODE>

@@ -1,5 +1,5 @@
 // The same-RB staging of the kernels that sort an env's links by (rb, link index) in LDS: d2d_sense.hip, d2d_bestrb.hip,
-// d2d_marginal.hip, d2d_powerctl.hip and d2d_evaluate.hip.  Three steps, each a workgroup-wide loop between the barriers the calling
+// d2d_marginal.hip, d2d_powerctl.hip, d2d_evaluate.hip and d2d_balance.hip.  Three steps, each a workgroup-wide loop between the barriers the calling
 // kernel places (it knows which bytes its keys share with what): the packed keys rb * 2048 + j, the rank of one key among all of
 // them (four keys per ds_read_b128 at a wave-uniform address: stable, free of atomics, the same order on every call), and
 // start[r] = the first sorted entry of RB r.  What a kernel puts into a link's slot is its own and stays in the kernel.

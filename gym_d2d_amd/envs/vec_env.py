@@ -22,7 +22,7 @@ from typing import Optional
 
 import numpy as np
 
-from .. import _native, assignment, best_response, best_response_dynamics, coloring, graph, joint_assignment, marginal, power_control, sensing
+from .. import _native, assignment, balance, best_response, best_response_dynamics, coloring, graph, joint_assignment, marginal, power_control, sensing
 from .. import evaluate as evaluate_mod
 from .. import mobility as mobility_mod
 from .. import queues as queues_mod
@@ -284,6 +284,8 @@ class VecD2DEnv:
         self._joint = None
         # conflict-graph RB colouring (color_graph(), color_rbs()): likewise
         self._color = None
+        # max-min SINR balancing (balance_sinr()): likewise
+        self._balance = None
 
     def _setup_autoreset(self) -> None:
         """Refuse what a device-side per-env reset cannot serve, then allocate the per-env bookkeeping: pending / episode are bound
@@ -903,6 +905,51 @@ class VecD2DEnv:
         first, p_min, levels = self._agent_power_levels()
         return power_control.encode_actions(self._t['rb'], power, p_min, levels, first)
 
+    # ------------------------------------------------------------------ max-min SINR balancing
+    def _balance_kernel(self):
+        return self._kernel('_balance', balance, balance.SinrBalance, lambda: (*self._class_bounds(), self._agent_links()))
+
+    def balance_sinr(self, base_sinr_db=0.0, margins_db=None, floor_sinr_db=None, adjustable=None, max_iters: int = 64, out=None,
+                     env_mask=None):
+        """The largest SINR level every adjustable link can be given at once with the protected links kept above their floors, and the
+        least powers that give it, with positions and RBs as the last step left them: (power_dbm int32 [B, N], sinr_db float32
+        [B, N], margin_db float32 [B], level int32 [B], probes int32 [B]), a tuple with those names.
+
+        Level k of the grid margins_db asks every adjustable link i for base_sinr_db[i] + margins_db[k].  Probe k is power_control()
+        for that target - cold from the lowest powers, at most max_iters sweeps - and its powers, SINRs and converged flag are what
+        power_control() returns for it, bit for bit.  It passes iff it converged, no adjustable link on an RB sits at its class
+        maximum with sinr_db below its target, and no link on an RB has sinr_db below floor_sinr_db (float32 comparisons; NaN
+        compares false).  The search is fixed: probe 0 first - if it fails the env is infeasible (level -1, margin_db -inf, the
+        planes of probe 0, probes 1) - then lo = 0, hi = K and, while hi - lo > 1, probe (lo + hi) // 2: a pass raises lo, a fail
+        lowers hi.  level = lo: it passes, and level + 1 is K or fails.  At most 13 probes.  The whole search of an env runs in one
+        workgroup of ONE kernel launch (csrc/d2d_balance.hip) out of LDS.  Valid after reset() and after every step(), as
+        power_control() is.
+
+        base_sinr_db, floor_sinr_db: a number, {'cue': x, 'due': y}, or [N] values (array or tensor), dB; floor None or -inf: no
+        floor.  margins_db: 1 to 4096 finite, strictly ascending values, checked on the host when given as an array; a float32
+        tensor [K] on the env's device is taken as it is (its order is the caller's promise); None: -20, -19, ..., 40.
+        adjustable, max_iters, env_mask: as power_control() takes them - None adjusts every agent link, links on fixed actions
+        (cue_actions='traffic') never move, a link that is not adjusted keeps its power, interferes and is still held to its floor.
+
+        Torch path only: enqueued on torch's current stream, nothing is synchronised; the five tensors the env owns, rewritten by
+        every call (clone them to keep them), or `out` = (power_dbm, sinr_db, margin_db, level, probes), contiguous int32 / float32
+        [B, N], float32 / int32 / int32 [B] on the env's device.  Serves what power_control() serves; ValueError for
+        export_actions=False, ShadowingPathLoss, every table route, pinned device_config coordinates float32 cannot hold."""
+        k = self._balance_kernel()
+        base, floor = k.base(base_sinr_db, self.num_cues), k.floor(floor_sinr_db, self.num_cues)
+        margins, adj = k.margins(margins_db), k.adjustable(adjustable)
+        self._follow_torch_stream()
+        return k.solve(self._t, base, margins, floor, adj, max_iters, out, self._stream_ptr, env_mask)
+
+    def balance_sinr_actions(self, base_sinr_db=0.0, margins_db=None, floor_sinr_db=None, adjustable=None, max_iters: int = 64):
+        """balance_sinr() as an action tensor, int32 [B, num_agents], ready for step(): every agent link stays on its RB (as the
+        decoded planes hold it) at the balanced power, encoded rb * power levels + level (power_control.encode_actions); an agent
+        link that is not adjustable repeats its last action.  Links on fixed actions (cue_actions='traffic') have no column.
+        Composes with color_rbs_actions() or best_response_dynamics_actions(): one call picks RBs, the other picks powers."""
+        power = self.balance_sinr(base_sinr_db, margins_db, floor_sinr_db, adjustable, max_iters)[0]
+        first, p_min, levels = self._agent_power_levels()
+        return power_control.encode_actions(self._t['rb'], power, p_min, levels, first)
+
     # ------------------------------------------------------------------ sequential best-response dynamics
     def _best_response_dynamics_kernel(self):
         return self._kernel('_brdyn', best_response_dynamics, best_response_dynamics.BestResponseDynamics,
@@ -1255,4 +1302,7 @@ class VecD2DEnv:
         if self._color is not None:
             self._color.close()
             self._color = None
+        if self._balance is not None:
+            self._balance.close()
+            self._balance = None
         self.simulator.handle.close()

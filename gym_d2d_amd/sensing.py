@@ -105,6 +105,8 @@ REFUSALS = {
                   'graph and planes'),
 }
 REFUSALS['assign_rbs_power'] = ('assign_rbs_power()', *REFUSALS['assign_rbs'][1:])      # assign_rbs()'s reasons under its own name
+REFUSALS['balance_sinr'] = ('balance_sinr()', _READS, 'its kernel can evaluate for the powers no step has applied',
+                            'balanced level (the SINR a probe was solved for is another draw than the one the next step sees)', 'planes')
 
 
 def refusal_text(api: str, sim, export_actions: bool, use_torch: Optional[bool] = None) -> Optional[str]:
