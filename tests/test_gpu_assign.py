@@ -47,13 +47,16 @@ def _device_inputs(c):
 
 def _launch_weights(c, links, allowed=None, objective=0, harm=True, shift=0):
     """One d2d_assign_weights launch with both planes inside guard words; shift: words (4 bytes each) by which the output pointers
-    are moved off their 256-byte alignment.  Returns (weights, harm) [B, M, R] as host arrays, harm None if not asked for."""
+    are moved off their 256-byte alignment; allowed: bool [N, R], or the packed uint32 words [N, ceil(R / 32)] themselves.  Returns
+    (weights, harm) [B, M, R] as host arrays, harm None if not asked for."""
     from gym_d2d_amd import _native
     from gym_d2d_amd.best_response import pack_allowed
     px, py, rb, pwr, tx, rx, cols, cap_cols = _device_inputs(c)
     b, n, r, m = c['b'], c['n'], c['r'], len(links)
     links_t = torch.as_tensor(np.ascontiguousarray(links, dtype=np.int32), device=_dev())
-    words_t = None if allowed is None else torch.as_tensor(pack_allowed(allowed).view(np.int32), device=_dev())
+    packed = None if allowed is None else allowed if allowed.dtype == np.uint32 else pack_allowed(allowed)
+    assert packed is None or packed.shape == (n, (r + 31) // 32)
+    words_t = None if packed is None else torch.as_tensor(np.ascontiguousarray(packed).view(np.int32), device=_dev())
     words = b * m * r
     o_w, o_h = PAD + shift, 2 * PAD + words + shift
     arena = torch.full((2 * words + 3 * PAD + shift,), GUARD, dtype=torch.int32, device=_dev())
@@ -165,12 +168,12 @@ def test_scattered_movable_links_and_allowed():
     assert np.array_equal(_bits(w2[:, :3]), _bits(w3)) and np.array_equal(_bits(h2[:, :3]), _bits(h3)) and (w2[:, 3:] == -np.inf).all() and (_bits(h2[:, 3:]) == 0).all()
 
 
-@pytest.mark.parametrize('cues,dues,r,law', asu.TIE_CASES)
-def test_own_weights_are_evaluates_capacity_bit_for_bit(cues, dues, r, law):
-    """Candidate (a, r): link a on r, the background where it is, every other movable link on rb -1."""
+def _own_weights_are_evaluates_capacity(cues, dues, r, law, links=None):
+    """Candidate (a, r): link a on r, the background where it is, every other movable link on rb -1.  links: the movable links,
+    ascending (None: the DUE links)."""
     from gym_d2d_amd import _native
     c = asu.case(cues, dues, r, law)
-    links = asu.due_links(c, cues)
+    links = asu.due_links(c, cues) if links is None else np.asarray(links, dtype=np.int32)
     m, b, n = len(links), c['b'], c['n']
     own, _ = _launch_weights(c, links, objective=1, harm=False)
     rb = np.repeat(asu.background_candidate(c, links)[:, None, :], m * r, axis=1)            # [B, M R, N]
@@ -190,6 +193,12 @@ def test_own_weights_are_evaluates_capacity_bit_for_bit(cues, dues, r, law):
     print(f'{cues} + {dues} links, {r} RBs, {law}: {m * r} candidates per env, {same.mean():.2%} of the own weights equal '
           f"evaluate()'s capacity bit for bit; {(want > 0).mean():.1%} above the sensitivity")
     assert same.all()
+    return own
+
+
+@pytest.mark.parametrize('cues,dues,r,law', asu.TIE_CASES)
+def test_own_weights_are_evaluates_capacity_bit_for_bit(cues, dues, r, law):
+    _own_weights_are_evaluates_capacity(cues, dues, r, law)
 
 
 # ------------------------------------------------------------------------------------------------ the matching kernel
@@ -241,7 +250,9 @@ def test_matching_with_ties_a_chain_and_what_cannot_be_matched():
 
 
 # ------------------------------------------------------------------------------------------------ through the env
-ENVS = {'small': ({'num_rbs': 8, 'num_cues': 4, 'num_due_pairs': 6}, 5), 'config2': ({'num_rbs': 25, 'num_cues': 25, 'num_due_pairs': 25}, 3)}
+ENVS = {'small': ({'num_rbs': 8, 'num_cues': 4, 'num_due_pairs': 6}, 5), 'config2': ({'num_rbs': 25, 'num_cues': 25, 'num_due_pairs': 25}, 3),
+        # 280 movable links on 300 RBs: a matching thread owns two columns, and the host packs a 10-word `allowed` with a 12-bit tail
+        'wide': ({'num_rbs': 300, 'num_cues': 150, 'num_due_pairs': 280}, 2)}
 
 
 def _env(name, **kw):

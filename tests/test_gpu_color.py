@@ -212,7 +212,7 @@ def _margins_hold(env, res, margin, turn, power=None):
     return int(proper.sum())
 
 
-@pytest.mark.parametrize('r', [6, 40])
+@pytest.mark.parametrize('r', [6, 40, 300])                     # 300: ten `allowed` words with a 12-bit tail, a second trip of the r loops
 def test_color_rbs_equals_the_restatement_and_keeps_the_margins_where_proper(r):
     env = _env(r)
     try:
