@@ -1,4 +1,4 @@
-"""ctypes binding of libd2d_hip.so (include/d2d_hip.h) and of the side libraries `SIDE`, `SOLVERS`, `ADDONS` and `FAMILIES` list
+"""ctypes binding of libd2d_hip.so (include/d2d_hip.h) and of the side libraries `SIDE`, `SOLVERS`, `ADDONS`, `FAMILIES` and `EXTRAS` list
 (libd2d_<name>.so, include/d2d_<name>.h).
 There is no CPU fallback: if a library or a gfx950 GPU is missing, the calls below raise."""
 from __future__ import annotations
@@ -92,6 +92,10 @@ BALANCE_MAX_LINKS = 2048
 BALANCE_MAX_RBS = 8192
 BALANCE_MAX_MARGINS = 4096
 BALANCE_MAX_LDS_BYTES = 163840
+# d2d_stable_match's limits (include/d2d_stable.h): the rows and columns an env may have, and the LDS of one workgroup
+STABLE_MAX_LINKS = 2048
+STABLE_MAX_RBS = 8192
+STABLE_MAX_LDS_BYTES = 163840
 
 BUFFER_DTYPES = {BUF_ACTIONS: np.int32, BUF_RB: np.int32, BUF_PWR: np.int32, BUF_ENV_FLAGS: np.int32, BUF_RESET_PENDING: np.int32,
                  BUF_EPISODE: np.uint32}
@@ -278,6 +282,12 @@ BALANCE_SIGNATURES = {
     'd2d_balance_last_error': (C.c_char_p, []),
 }
 
+# every symbol include/d2d_stable.h declares
+STABLE_SIGNATURES = {
+    'd2d_stable_match': (C.c_int, [_P, _P, _P, C.c_int64, _I, _I, _P, _P, _P, _P, _P]),
+    'd2d_stable_last_error': (C.c_char_p, []),
+}
+
 # the side libraries: name -> every symbol include/d2d_<name>.h declares; libd2d_<name>.so, its error text in d2d_<name>_last_error
 SIDE = {'plugin': PLUGIN_SIGNATURES, 'episode': EPISODE_SIGNATURES, 'sense': SENSE_SIGNATURES, 'graph': GRAPH_SIGNATURES,
         'marginal': MARGINAL_SIGNATURES, 'mobility': MOBILITY_SIGNATURES, 'channel': CHANNEL_SIGNATURES, 'queue': QUEUE_SIGNATURES,
@@ -288,6 +298,8 @@ SOLVERS = {'assign': ASSIGN_SIGNATURES}
 ADDONS = {'assignpwr': ASSIGNPWR_SIGNATURES, 'color': COLOR_SIGNATURES}
 # build.FAMILIES' libraries, likewise: the table the kernel families since then join
 FAMILIES = {'balance': BALANCE_SIGNATURES}
+# build.EXTRAS' libraries, likewise: what joined behind the families
+EXTRAS = {'stable': STABLE_SIGNATURES}
 
 _lib: Optional[C.CDLL] = None
 _side: dict = {}                    # name -> the opened, typed side library
@@ -304,6 +316,7 @@ assign_solve_launches = 0           # d2d_assign_solve launches made through ass
 assign_power_weights_launches = 0   # d2d_assign_power_weights launches made through assign_power_weights()
 color_launches = 0                  # d2d_color_graph launches made through color_graph()
 balance_launches = 0                # d2d_balance_sinr launches made through balance_sinr()
+stable_launches = 0                 # d2d_stable_match launches made through stable_match()
 mobility_launches = 0               # d2d_mobility_move calls made through mobility_move()
 channel_launches = 0                # d2d_channel_fill calls made through channel_fill()
 queue_launches = 0                  # d2d_queue_step calls made through queue_step()
@@ -333,14 +346,14 @@ def side_path(name: str) -> Path:
 
 
 def side_library(name: str) -> C.CDLL:
-    """dlopen libd2d_<name>.so once and type the entry points SIDE[name] (or SOLVERS[name], ADDONS[name], FAMILIES[name]) lists.  Raises if it has not been built."""
+    """dlopen libd2d_<name>.so once and type the entry points SIDE[name] (or SOLVERS[name], ADDONS[name], FAMILIES[name], EXTRAS[name]) lists.  Raises if it has not been built."""
     lib = _side.get(name)
     if lib is None:
         path = side_path(name)
         if not path.exists():
             raise ImportError(f'{path} is missing - build it with `python -m gym_d2d_amd.build`')
         lib = C.CDLL(str(path))
-        for symbol, (res, args) in (SIDE.get(name) or SOLVERS.get(name) or ADDONS.get(name) or FAMILIES[name]).items():
+        for symbol, (res, args) in (SIDE.get(name) or SOLVERS.get(name) or ADDONS.get(name) or FAMILIES.get(name) or EXTRAS[name]).items():
             fn = getattr(lib, symbol)
             fn.restype = res
             fn.argtypes = args
@@ -371,6 +384,7 @@ def load_assign_library() -> C.CDLL: return side_library('assign')
 def load_assignpwr_library() -> C.CDLL: return side_library('assignpwr')
 def load_color_library() -> C.CDLL: return side_library('color')
 def load_balance_library() -> C.CDLL: return side_library('balance')
+def load_stable_library() -> C.CDLL: return side_library('stable')
 
 
 # Pointer arguments are passed as the ints they are: every argtype is c_void_p, which takes 0 as the null pointer and any int up to
@@ -579,6 +593,18 @@ def balance_sinr(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, link
         sinr_ptr, margin_ptr, level_ptr, probes_ptr, stream_ptr))
     if n_envs:
         balance_launches += 1
+
+
+def stable_match(link_pref_ptr: int, rb_pref_ptr: int, quota_ptr: int, n_envs: int, n_links: int, n_rbs: int, col_ptr: int, load_ptr: int,
+                 proposals_ptr: int, unmatched_ptr: int, stream_ptr: int = 0) -> None:
+    """d2d_stable_match: the link-optimal stable matching of every env in one launch - col int32 [n_envs, n_links] (-1: unmatched),
+    load int32 [n_envs, n_rbs], proposals and unmatched int32 [n_envs] (device pointers; link_pref and rb_pref float32 [n_envs,
+    n_links, n_rbs], higher is better, a pair with an entry that is not finite is unacceptable; quota int32 [n_rbs])."""
+    global stable_launches
+    _check_side('stable', load_stable_library().d2d_stable_match(
+        link_pref_ptr, rb_pref_ptr, quota_ptr, n_envs, n_links, n_rbs, col_ptr, load_ptr, proposals_ptr, unmatched_ptr, stream_ptr))
+    if n_envs:
+        stable_launches += 1
 
 
 def mobility_move(pos_x_ptr: int, pos_y_ptr: int, vel_x_ptr: int, vel_y_ptr: int, fixed_mask_ptr: int, n_envs: int, n_cues: int,

@@ -1,4 +1,4 @@
-"""Build every shared library of `LIBRARIES`, `SOLVERS`, `ADDONS` and `FAMILIES` for gfx950 with hipcc - in-tree, so the .so files travel with the repo snapshot.
+"""Build every shared library of `LIBRARIES`, `SOLVERS`, `ADDONS`, `FAMILIES` and `EXTRAS` for gfx950 with hipcc - in-tree, so the .so files travel with the repo snapshot.
 
     stem      libd2d_<stem>.so                                        public header
     hip       the product: the C ABI                                  include/d2d_hip.h
@@ -8,6 +8,7 @@
     assignpwr the joint RB and power weights (4.17), listed in ADDONS   include/d2d_assignpwr.h
     color     the conflict-graph RB colouring (4.18), listed in ADDONS   include/d2d_color.h
     balance   the max-min SINR balancing (4.19), listed in FAMILIES      include/d2d_balance.h
+    stable    the stable RB matching with quotas (4.20), listed in EXTRAS include/d2d_stable.h
 
     python -m gym_d2d_amd.build [--force] [--verbose]
     D2D_BUILD_DIAG=1 python -m gym_d2d_amd.build      # diagnostic build of libd2d_hip.so: the A/B tuning keys and the ablation
@@ -47,10 +48,16 @@ EVERYTHING = {**BUILT, **ADDONS}                 # what build() compiles and lin
 # the rest, and a missing one is rebuilt (families_missing()).  This table is the one that grows.
 # balance: the max-min SINR balancing
 FAMILIES = {'balance': ['d2d_balance.hip']}
-TARGETS = {**EVERYTHING, **FAMILIES}             # every library of the build: what the digest, the compile and the link iterate
+TARGETS = {**EVERYTHING, **FAMILIES}             # EVERYTHING and the families: fixed with them, as the tables above are
+# the libraries that joined behind the families (which _native.EXTRAS mirrors): compiled and linked last, stamped with the rest, and a
+# missing one is rebuilt (extras_missing()).
+# stable: the stable RB matching with quotas
+EXTRAS = {'stable': ['d2d_stable.hip']}
+ALL = {**TARGETS, **EXTRAS}                      # every library of the build: what the digest, the compile and the link iterate
 HEADERS = [CSRC / 'd2d_internal.h', CSRC / 'd2d_plan.h', CSRC / 'd2d_step_device.h', CSRC / 'd2d_store.h', CSRC / 'd2d_same_rb.h', CSRC / 'd2d_addon.h',
-           CSRC / 'd2d_powerctl_device.h', INCLUDE / 'd2d_hip.h', INCLUDE / 'd2d_hip_diag.h',
-           *(INCLUDE / f'd2d_{stem}.h' for stem in TARGETS if stem not in ('hip', 'probe'))]
+           CSRC / 'd2d_powerctl_device.h', CSRC / 'd2d_wave_key.h', INCLUDE / 'd2d_hip.h', INCLUDE / 'd2d_hip_diag.h',
+           *(INCLUDE / f'd2d_{stem}.h' for stem in TARGETS if stem not in ('hip', 'probe')),
+           *(INCLUDE / f'd2d_{stem}.h' for stem in EXTRAS)]
 
 
 def lib_path(stem: str, lib_dir: Path = LIB_DIR) -> Path:
@@ -78,7 +85,7 @@ def _hipcc() -> str:
 
 def digest_files() -> list:
     """The files source_digest() hashes, in order: every library's sources, then the headers."""
-    return [p for p in [CSRC / s for sources in TARGETS.values() for s in sources] + HEADERS if p.exists()]
+    return [p for p in [CSRC / s for sources in ALL.values() for s in sources] + HEADERS if p.exists()]
 
 
 def source_digest() -> str:
@@ -119,16 +126,22 @@ def families_missing(lib_dir: Path = LIB_DIR) -> list:
     return [stem for stem in FAMILIES if not lib_path(stem, lib_dir).exists()]
 
 
+def extras_missing(lib_dir: Path = LIB_DIR) -> list:
+    """The stems of EXTRAS whose library is not there, in the table's order: a missing one is rebuilt."""
+    return [stem for stem in EXTRAS if not lib_path(stem, lib_dir).exists()]
+
+
 def build(force: bool = False, verbose: bool = False) -> Path:
     LIB_DIR.mkdir(exist_ok=True)
     digest = source_digest()
-    if not force and up_to_date(digest) and solvers_built() and addons_built() and not addons_missing() and not families_missing():
+    if not force and up_to_date(digest) and solvers_built() and addons_built() and not addons_missing() and not families_missing() \
+            and not extras_missing():
         return LIB_PATH
     hipcc = _hipcc()
     obj_dir = LIB_DIR / 'obj'
     obj_dir.mkdir(exist_ok=True)
     procs = []
-    for s in [s for sources in TARGETS.values() for s in sources]:
+    for s in [s for sources in ALL.values() for s in sources]:
         src = CSRC / s
         obj = obj_dir / (src.stem + '.o')
         cmd = [hipcc, *FLAGS, '-I', str(INCLUDE), '-c', str(src), '-o', str(obj)]
@@ -141,7 +154,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
             raise RuntimeError(f'hipcc failed on {s}:\n{out}')
         if verbose and out.strip():
             print(out)
-    for stem, sources in TARGETS.items():
+    for stem, sources in ALL.items():
         objs = [str(obj_dir / (Path(s).stem + '.o')) for s in sources]
         cmd = [hipcc, '-shared', '-fPIC', f'--offload-arch={ARCH}', '-o', str(lib_path(stem)), *objs]
         if verbose:

@@ -22,7 +22,7 @@ from typing import Optional
 
 import numpy as np
 
-from .. import _native, assignment, balance, best_response, best_response_dynamics, coloring, graph, joint_assignment, marginal, power_control, sensing
+from .. import _native, assignment, balance, best_response, best_response_dynamics, coloring, graph, joint_assignment, marginal, power_control, sensing, stable_matching
 from .. import evaluate as evaluate_mod
 from .. import mobility as mobility_mod
 from .. import queues as queues_mod
@@ -286,6 +286,8 @@ class VecD2DEnv:
         self._color = None
         # max-min SINR balancing (balance_sinr()): likewise
         self._balance = None
+        # stable RB matching with quotas (solve_stable_matching(), stable_rbs()): likewise
+        self._stable = None
 
     def _setup_autoreset(self) -> None:
         """Refuse what a device-side per-env reset cannot serve, then allocate the per-env bookkeeping: pending / episode are bound
@@ -1098,6 +1100,59 @@ class VecD2DEnv:
         rb = self.assign_rbs(movable, allowed, objective)[0]
         return best_response_dynamics.encode_actions(rb, self._t['pwr'], self._agent_levels(), self.num_links - self.num_agents)
 
+    # ------------------------------------------------------------------ stable RB matching with quotas
+    def _stable_kernel(self):
+        return self._kernel('_stable', stable_matching, stable_matching.StableMatching, lambda: (self._assignment_kernel(),))
+
+    def solve_stable_matching(self, link_pref, rb_pref, quota=1, out=None):
+        """The link-optimal stable matching of ANY pair of contiguous float32 [B, M, R] tensors (env, row = link, column = RB; higher
+        is better) on the env's device, by Gale-Shapley deferred acceptance with the links proposing: (col int32 [B, M], load int32
+        [B, R], proposals int32 [B], unmatched int32 [B]), a tuple with those names.
+
+        A pair (a, r) is acceptable iff both its entries are finite.  Link a ranks its acceptable RBs by (link_pref descending, r
+        ascending), RB r the links by (rb_pref descending, a ascending), in float32 comparisons (+0.0 ties with -0.0).  quota: the
+        links an RB can hold - an int for every RB, [R] ints each in [0, M] (0: closed), or an int32 [R] tensor on the device.  col[b,
+        a] is the RB of row a, -1 for an unmatched row; load[b, r] <= quota[r] the rows on r.  No acceptable pair blocks the result
+        (a prefers r to its match, and r is under quota or prefers a to its worst holder), every link weakly prefers it to every
+        other stable matching, and it is unique: any order of proposals reaches it and makes the same proposals, whose number is
+        proposals[b].  An env without an acceptable pair has every col -1 and does not disturb the others.
+
+        One kernel launch (csrc/d2d_stable.hip), one workgroup per env, every round inside it; integers only behind the
+        comparisons: two calls give the same words.  Enqueued on torch's current stream, nothing is synchronised.  The env's own
+        tensors, rewritten by every call, or `out` = (col, load, proposals, unmatched).  Refused as stable_rbs() is."""
+        k = self._stable_kernel()
+        self._follow_torch_stream()
+        return k.solve(link_pref, rb_pref, quota, out, self._stream_ptr)
+
+    def stable_rbs(self, movable=None, allowed=None, quota=1, rb_pref: str = 'harm', out=None):
+        """The stable-matching baseline of the D2D-underlay literature: the movable links and the RBs (the base station acting for
+        the background on each RB) rank each other, and the links are placed by solve_stable_matching(): (rb int32 [B, N],
+        unmatched int32 [B], proposals int32 [B]), a tuple with those names.
+
+        The preferences are the planes of ONE assignment_weights(objective='own', harm=True) launch: link_pref = own, what a link
+        gets on an RB beside its background; rb_pref = -harm under rb_pref='harm' (the RB prefers whoever hurts its background
+        least) or own - harm under 'total' (one float32 subtraction, assignment_weights(objective='total')).  A pair `allowed`
+        forbids arrives as -inf and is unacceptable.  Then the matching launch and one scatter: a matched movable link goes to its
+        RB, an unmatched one keeps its current RB and unmatched[b] counts it, background rows are copied through.  More movable
+        links than RBs is no error: quota > 1 serves them, or they stay unmatched.
+
+        What stability means here.  With quota = 1 the movable links end on distinct RBs and do not interfere with each other, so
+        the preferences are the true capacities and stability is a statement about the env: no link and RB would both rather be
+        together.  With quota > 1 the links that share an RB interfere with each other, which the fixed preferences ignore:
+        stability then holds with respect to the stated tensors only, and evaluate() gives the truth.  Unlike assign_rbs() nothing
+        is maximised; unlike best_response_dynamics() it always ends.  movable, allowed, validity and refusals as
+        assignment_weights(), whose env-owned planes are rewritten, under the name stable_rbs().  `out` = (rb, unmatched,
+        proposals)."""
+        k = self._stable_kernel()
+        self._follow_torch_stream()
+        return k.rbs(self._t, movable, allowed, quota, rb_pref, out, self._stream_ptr)
+
+    def stable_rbs_actions(self, movable=None, allowed=None, quota=1, rb_pref: str = 'harm'):
+        """stable_rbs() as an action tensor, int32 [B, num_agents], ready for step(): every agent link on its RB of stable_rbs() at
+        its current power level, encoded rb * power levels + level, as assign_rbs_actions() does."""
+        rb = self.stable_rbs(movable, allowed, quota, rb_pref)[0]
+        return best_response_dynamics.encode_actions(rb, self._t['pwr'], self._agent_levels(), self.num_links - self.num_agents)
+
     # ------------------------------------------------------------------ joint RB and power matching with SINR floors
     def _joint_assignment_kernel(self):
         return self._kernel('_joint', joint_assignment, joint_assignment.JointAssignment,
@@ -1305,4 +1360,7 @@ class VecD2DEnv:
         if self._balance is not None:
             self._balance.close()
             self._balance = None
+        if self._stable is not None:
+            self._stable.close()
+            self._stable = None
         self.simulator.handle.close()

@@ -109,10 +109,10 @@ REFUSALS['balance_sinr'] = ('balance_sinr()', _READS, 'its kernel can evaluate f
                             'balanced level (the SINR a probe was solved for is another draw than the one the next step sees)', 'planes')
 
 
-def refusal_text(api: str, sim, export_actions: bool, use_torch: Optional[bool] = None) -> Optional[str]:
-    """Why this env cannot have `api`, a key of REFUSALS (None: it can).  Each text names the route or the switch; use_torch is
-    passed by the APIs that have the torch path only."""
-    subject, planes, law, draw, tensors = REFUSALS[api]
+def refusal_text(api, sim, export_actions: bool, use_torch: Optional[bool] = None) -> Optional[str]:
+    """Why this env cannot have `api`, a key of REFUSALS or a row of its form that a module keeps itself (None: it can).  Each text
+    names the route or the switch; use_torch is passed by the APIs that have the torch path only."""
+    subject, planes, law, draw, tensors = REFUSALS[api] if isinstance(api, str) else api
     if use_torch is not None and not use_torch:
         return f'{subject} needs the torch path (use_torch): its {tensors} are device tensors'
     why = unserved(sim, export_actions)
