@@ -298,8 +298,12 @@ int d2d_positions_changed(d2d_handle* h);
  * BS at the origin, CUEs / DUE transmitters uniform in the cell disc, DUE receivers uniform within
  * d2d_radius_m of their transmitter and re-drawn until inside the cell.  Counter-based Philox4x32-10
  * stream keyed by `seed`, counter (first_env + env, device, try, episode) - see csrc/d2d_reset.hip.
+ * A receiver is drawn at most 64 times (tries 0..63): one whose draws all fall outside the cell
+ * (d2d_radius_m far above cell_radius_m) takes its transmitter's coordinates exactly, and the next
+ * step raises D2D_FLAG_ZERO_DISTANCE for its env.  first_env + env wraps at 2^32 in the counter.
  * fixed_mask[D] / fixed_xy[D,2] (host, may be NULL): devices pinned by a device_config_file
- * (simulator.py:65-66).  Asynchronous.                                                             */
+ * (simulator.py:65-66); a pinned receiver is not drawn, the receiver of a pinned transmitter is
+ * drawn around the pin, and the bit of device 0 (the base station) is ignored.  Asynchronous.      */
 int d2d_reset_positions(d2d_handle* h, uint64_t seed, uint64_t episode, const uint8_t* fixed_mask,
                         const float* fixed_xy);
 /* episode = D2D_EPISODE_PER_ENV: reset only the envs whose D2D_BUF_RESET_PENDING entry is non-zero, env b at episode
