@@ -74,6 +74,15 @@ FLAGS = ['-O3', '-std=c++17', '-fPIC', f'--offload-arch={ARCH}', '-fno-gpu-rdc',
 FLAGS += os.environ.get('D2D_BUILD_DEFINES', '').split()       # experiment builds (tools/ab_builds.py), e.g. -DD2D_EXP_PF_POS=1
 if os.environ.get('D2D_BUILD_DIAG') == '1':          # diagnostic build: the step kernel honours D2D_TUNE_STEP_ABLATE
     FLAGS += ['-DD2D_DIAG=1', '-DD2D_STEP_ABLATE=1']
+# flags of ONE source, appended behind FLAGS (every other source compiles as before, register for register).  d2d_obs.hip: the flat
+# LinearObs kernels take scalar arguments so that the command processor preloads them into user SGPRs at wave launch (at most 14
+# dwords: 16 user SGPRs less the kernarg segment pointer); a kernel whose argument is a struct by value is not affected
+SOURCE_FLAGS = {'d2d_obs.hip': ['-mllvm', '-amdgpu-kernarg-preload-count=14']}
+
+
+def flags_for(source: str) -> list:
+    """The compile flags of `source` (a name of csrc/): FLAGS, then its row of SOURCE_FLAGS."""
+    return [*FLAGS, *SOURCE_FLAGS.get(Path(source).name, [])]
 
 
 def _hipcc() -> str:
@@ -94,6 +103,8 @@ def source_digest() -> str:
     for p in digest_files():
         h.update(p.name.encode()); h.update(p.read_bytes())
     h.update(' '.join(FLAGS).encode())
+    for name in sorted(SOURCE_FLAGS):
+        h.update(name.encode()); h.update(' '.join(SOURCE_FLAGS[name]).encode())
     return h.hexdigest()
 
 
@@ -144,7 +155,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     for s in [s for sources in ALL.values() for s in sources]:
         src = CSRC / s
         obj = obj_dir / (src.stem + '.o')
-        cmd = [hipcc, *FLAGS, '-I', str(INCLUDE), '-c', str(src), '-o', str(obj)]
+        cmd = [hipcc, *flags_for(s), '-I', str(INCLUDE), '-c', str(src), '-o', str(obj)]
         if verbose:
             print(' '.join(cmd), flush=True)
         procs.append((s, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))

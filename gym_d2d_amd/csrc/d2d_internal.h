@@ -137,7 +137,8 @@ struct ObsArgs {
     int block;               // threads per workgroup (0 -> 256)
     int variant;             // 0: T staged in LDS   1: T read straight from global (A/B)
     int out_f64;             // obs is float64 [B,N,6N] (d2d_set_obs_dtype): obs_expand_f64_kernel
-    int stagger;             // > 0: wave w of a workgroup sleeps w * stagger x 64 clocks before its stores (A/B)
+    int stagger;             // > 0: wave w of a workgroup sleeps w * stagger x 64 clocks before its stores (A/B; the row-aligned kernel
+                             // only: the flat kernels' arguments are the scalars launch_obs_expand passes, d2d_obs.hip)
     unsigned long long chunk_magic;  // flat kernels: ceil(2^40 / chunks) where the multiply-shift is exact for every block, else 0 (divide)
     const float* table;      // [B,N,6]
     float* obs;              // [B,N,6N]

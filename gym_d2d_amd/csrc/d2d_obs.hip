@@ -6,7 +6,8 @@
 // This is the HBM-dominant kernel of the path: 24*N bytes written per agent-step against 24 read.  It is a
 // pure streaming store, so the design is about the store side only:
 //   * T[b] (6N floats) is staged once per workgroup in LDS - in the flat kernels in ONE round trip: 16-byte loads, all issued before
-//     the first wait, the kernel arguments read in one scalar trip and every piece's index arithmetic done under the loads
+//     the first wait, the kernel arguments scalars that the command processor preloads into SGPRs at wave launch (round 8: no
+//     scalar-memory trip ahead of the first load) and every piece's index arithmetic done under the loads
 //     (round 7: what a workgroup does before its first store decides which store policy is the fastest, see plan_obs);
 //   * the output block of an env is contiguous ([N][6N] floats), so a workgroup walks a contiguous slab of it
 //     with one 16-byte store per lane per iteration - every wave-instruction writes 1 KiB of consecutive
@@ -155,21 +156,28 @@ __global__ __launch_bounds__(1024) void obs_expand_kernel(const ObsArgs a) {
 // probe family (1024 threads x 2 passes = 32 KB per workgroup, 16 KB contiguous per pass), where the row-aligned default writes
 // 2 x 12 KB.  A lane's (row, column) differs per pass: two multiply-shift divisions per lane and launch.
 
-// (env, chunk) of a flat workgroup and the kernel arguments its pieces need, all in SGPRs before the first table load goes out: the
-// arguments are read in ONE scalar round trip (the compiler otherwise fetches half of them behind the env computation - a second
-// dependent trip ahead of the staging loads) and the division by `chunks` is a multiply-shift wherever plan_obs found it exact.
+// The flat kernels take their arguments as SCALARS, the twelve dwords every wave needs first - so that the command processor
+// can place them in user SGPRs at wave launch (kernarg preload, -amdgpu-kernarg-preload-count in build.py's SOURCE_FLAGS; an
+// argument struct passed by value is never preloaded) and no scalar-memory round trip stands in front of the first table load.
+// `pieces` is the thirteenth.  The block size is a template constant at 1024 and 512 (TB = 0 reads blockDim: one scalar load).
+#define D2D_FLAT_PARAMS const float* table, float* obs, unsigned long long q_magic, unsigned long long chunk_magic, unsigned N, \
+                        unsigned chunks, unsigned q_per_row, unsigned xcd_remap, unsigned pieces
+#define D2D_FLAT_ARGS(a) (a).table, (a).obs, (a).q_magic, (a).chunk_magic, (unsigned)(a).N, (unsigned)(a).chunks, (a).q_per_row, \
+                         (unsigned)(a).xcd_remap, (unsigned)(a).rows_per_wg
+
+// (env, chunk) of a flat workgroup and what its pieces need, all in SGPRs before the first table load goes out; the division by
+// `chunks` is a multiply-shift wherever plan_obs found it exact.
 struct FlatHead {
-    unsigned env, chunk, T, q_per_row, stagger;
+    unsigned env, chunk, T, N, q_per_row;
     unsigned long long q_magic;
     const float* table;
     float* obs;
 };
-__device__ __forceinline__ FlatHead flat_head(const ObsArgs& a) {
+template <int TB>
+__device__ __forceinline__ FlatHead flat_head(const float* table, float* obs, unsigned long long q_magic, unsigned long long magic,
+                                              unsigned N, unsigned chunks, unsigned q_per_row, unsigned remap) {
     FlatHead h;
-    h.T = blockDim.x; h.q_per_row = a.q_per_row; h.stagger = (unsigned)a.stagger; h.q_magic = a.q_magic; h.table = a.table; h.obs = a.obs;
-    unsigned chunks = (unsigned)a.chunks, remap = (unsigned)a.xcd_remap;
-    unsigned long long magic = a.chunk_magic;
-    asm volatile("" : "+s"(h.T), "+s"(h.q_per_row), "+s"(h.stagger), "+s"(h.q_magic), "+s"(h.table), "+s"(h.obs), "+s"(chunks), "+s"(remap), "+s"(magic));
+    h.T = TB ? (unsigned)TB : blockDim.x; h.N = N; h.q_per_row = q_per_row; h.q_magic = q_magic; h.table = table; h.obs = obs;
     // blocks b, b + 8, b + 16, ... share an XCD (round-robin dispatch): with xcd_remap they are the chunks of one env
     const unsigned bid = blockIdx.x, rest = remap ? bid >> 3 : bid;
     const unsigned e = magic ? (unsigned)(((unsigned long long)rest * magic) >> 40) : rest / chunks;
@@ -179,12 +187,14 @@ __device__ __forceinline__ FlatHead flat_head(const ObsArgs& a) {
 }
 
 // What a workgroup does before its first store decides how long it lives, and under the write-through policies that, not HBM, is
-// what bounds the kernel: the staging loads go out first; every piece's (row, column) and LDS addresses - which
-// depend on the thread, the block and the arguments only - are worked out while the loads are under way; behind the barrier only
-// the LDS reads, one wait and the stores are left.  PASSES is the workgroup's piece count as a constant, so the reads need no guard.
+// what bounds the kernel: the arguments are in SGPRs when the wave starts; the staging loads go out first; every
+// piece's (row, column) and LDS addresses - which depend on the thread, the block and the arguments only - are worked out while
+// the loads are under way; behind the barrier only the LDS reads, one wait and the stores are left.  PASSES is the workgroup's
+// piece count as a constant, so the reads need no guard.  (Staging by LDS-DMA, global_load_lds_dwordx4 in place of the load and the
+// ds_write_b128, shortens a wave's life further and is SLOWER at the default shape: profiles/NEGATIVE_RESULTS.md.)
 template <int NT, int PASSES>
-__device__ __forceinline__ void obs_flat_pieces(const ObsArgs& a, const FlatHead& h, float* t_flat) {
-    const unsigned N = a.N, tid = threadIdx.x, T = h.T, env = h.env, chunk = h.chunk;
+__device__ __forceinline__ void obs_flat_pieces(const FlatHead& h, float* t_flat) {
+    const unsigned N = h.N, tid = threadIdx.x, T = h.T, env = h.env, chunk = h.chunk;
     const unsigned row_floats = 6u * N, q_per_row = h.q_per_row, total = N * q_per_row, n4 = row_floats / 4u;
     const float* table_env = h.table + (size_t)env * row_floats;
     StagedPieces st;
@@ -205,10 +215,6 @@ __device__ __forceinline__ void obs_flat_pieces(const ObsArgs& a, const FlatHead
     stage_rest16(t_flat, table_env, n4, tid, T);
     __builtin_amdgcn_sched_barrier(0);                                    // none of the above sinks behind the barrier
     __syncthreads();
-    if (h.stagger > 0) {                                                  // D2D_TUNE_OBS_STAGGER (A/B)
-        const int n = (int)((tid >> 6) * h.stagger);
-        for (int k = 0; k < n; ++k) __builtin_amdgcn_s_sleep(1);
-    }
     const char* lds = reinterpret_cast<const char*>(t_flat);
     f32x2 lo[PASSES], hi[PASSES];
 #pragma unroll
@@ -221,15 +227,15 @@ __device__ __forceinline__ void obs_flat_pieces(const ObsArgs& a, const FlatHead
         if (idx[p] < total) store16<NT>(out + idx[p], f32x4{lo[p].x, lo[p].y, hi[p].x, hi[p].y});
 }
 
-template <int NT>
-__global__ __launch_bounds__(1024) void obs_expand_flat_kernel(const ObsArgs a) {
+template <int NT, int TB>
+__global__ __launch_bounds__(1024) void obs_expand_flat_kernel(D2D_FLAT_PARAMS) {
     extern __shared__ __align__(16) float t_flat[];          // [6N]
-    const FlatHead h = flat_head(a);
-    switch (a.rows_per_wg) {                                              // rows_per_wg = pieces per workgroup here (1 .. 4)
-        case 1: obs_flat_pieces<NT, 1>(a, h, t_flat); break;
-        case 2: obs_flat_pieces<NT, 2>(a, h, t_flat); break;
-        case 3: obs_flat_pieces<NT, 3>(a, h, t_flat); break;
-        default: obs_flat_pieces<NT, 4>(a, h, t_flat); break;
+    const FlatHead h = flat_head<TB>(table, obs, q_magic, chunk_magic, N, chunks, q_per_row, xcd_remap);
+    switch (pieces) {                                                     // pieces per workgroup (1 .. 4)
+        case 1: obs_flat_pieces<NT, 1>(h, t_flat); break;
+        case 2: obs_flat_pieces<NT, 2>(h, t_flat); break;
+        case 3: obs_flat_pieces<NT, 3>(h, t_flat); break;
+        default: obs_flat_pieces<NT, 4>(h, t_flat); break;
     }
 }
 
@@ -282,9 +288,9 @@ __global__ __launch_bounds__(1024) void obs_expand_f64_kernel(const ObsArgs a) {
 // piece by multiply-shift, all LDS reads issued ahead of the stores.  (The row-aligned kernel above walked a row with a strided
 // loop and a three-way source select per element: 6.6 TB/s where this shape's float32 twin does 7.1 - 7.2, profiles/r4_obs_float64.jsonl.)
 template <int NT, int PASSES>        // the float64 twin of obs_flat_pieces: one ds_read_b64 per piece, store16 on the bit pattern of the double2
-__device__ __forceinline__ void obs_flat_f64_pieces(const ObsArgs& a, const FlatHead& h, float* t_flat) {
+__device__ __forceinline__ void obs_flat_f64_pieces(const FlatHead& h, float* t_flat) {
     typedef double f64x2 __attribute__((ext_vector_type(2)));
-    const unsigned N = a.N, tid = threadIdx.x, T = h.T, env = h.env, chunk = h.chunk;
+    const unsigned N = h.N, tid = threadIdx.x, T = h.T, env = h.env, chunk = h.chunk;
     const unsigned row_floats = 6u * N, q_per_row = h.q_per_row, total = N * q_per_row;      // q_per_row = 3N double2 per row
     const float* table_env = h.table + (size_t)env * row_floats;
     const bool wide = (row_floats & 3u) == 0u;                            // even N: T[env] is 16-byte aligned, whole float4
@@ -324,15 +330,15 @@ __device__ __forceinline__ void obs_flat_f64_pieces(const ObsArgs& a, const Flat
         }
 }
 
-template <int NT>
-__global__ __launch_bounds__(1024) void obs_expand_flat_f64_kernel(const ObsArgs a) {
+template <int NT, int TB>
+__global__ __launch_bounds__(1024) void obs_expand_flat_f64_kernel(D2D_FLAT_PARAMS) {
     extern __shared__ __align__(16) float t_flat[];          // [6N]
-    const FlatHead h = flat_head(a);
-    switch (a.rows_per_wg) {
-        case 1: obs_flat_f64_pieces<NT, 1>(a, h, t_flat); break;
-        case 2: obs_flat_f64_pieces<NT, 2>(a, h, t_flat); break;
-        case 3: obs_flat_f64_pieces<NT, 3>(a, h, t_flat); break;
-        default: obs_flat_f64_pieces<NT, 4>(a, h, t_flat); break;
+    const FlatHead h = flat_head<TB>(table, obs, q_magic, chunk_magic, N, chunks, q_per_row, xcd_remap);
+    switch (pieces) {
+        case 1: obs_flat_f64_pieces<NT, 1>(h, t_flat); break;
+        case 2: obs_flat_f64_pieces<NT, 2>(h, t_flat); break;
+        case 3: obs_flat_f64_pieces<NT, 3>(h, t_flat); break;
+        default: obs_flat_f64_pieces<NT, 4>(h, t_flat); break;
     }
 }
 
@@ -370,20 +376,38 @@ __global__ __launch_bounds__(1024) void obs_expand_direct_kernel(const ObsArgs a
     }
 }
 
+// the flat kernel of (dtype, policy) at the launch's block size
+template <bool F64, int NT, int TB>
+static void launch_flat_tb(const ObsArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t stream) {
+    if (F64) hipLaunchKernelGGL((obs_expand_flat_f64_kernel<NT, TB>), grid, block, lds, stream, D2D_FLAT_ARGS(a));
+    else hipLaunchKernelGGL((obs_expand_flat_kernel<NT, TB>), grid, block, lds, stream, D2D_FLAT_ARGS(a));
+}
+template <bool F64, int NT>
+static void launch_flat_nt(const ObsArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t stream) {
+    switch (block.x) {
+        case 1024: launch_flat_tb<F64, NT, 1024>(a, grid, block, lds, stream); break;
+        case 512: launch_flat_tb<F64, NT, 512>(a, grid, block, lds, stream); break;
+        default: launch_flat_tb<F64, NT, 0>(a, grid, block, lds, stream); break;
+    }
+}
+template <bool F64>
+static void launch_flat(const ObsArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t stream) {
+    switch (a.nontemporal) {
+        case 0: launch_flat_nt<F64, 0>(a, grid, block, lds, stream); break;
+        case 2: launch_flat_nt<F64, 2>(a, grid, block, lds, stream); break;
+        case 3: launch_flat_nt<F64, 3>(a, grid, block, lds, stream); break;
+        case 4: launch_flat_nt<F64, 4>(a, grid, block, lds, stream); break;
+        case 5: launch_flat_nt<F64, 5>(a, grid, block, lds, stream); break;
+        default: launch_flat_nt<F64, 1>(a, grid, block, lds, stream); break;
+    }
+}
+
 hipError_t launch_obs_expand(const ObsArgs& a, hipStream_t stream) {
     const size_t lds = (size_t)a.N * 6 * sizeof(float);
     dim3 grid((unsigned)a.B * (unsigned)a.chunks), block(a.block > 0 ? a.block : 256);
     if (a.out_f64) {
-        if (a.variant == 2 && a.rows_per_wg <= 4) {            // flat slabs (the default)
-            switch (a.nontemporal) {
-                case 0: hipLaunchKernelGGL((obs_expand_flat_f64_kernel<0>), grid, block, lds, stream, a); break;
-                case 2: hipLaunchKernelGGL((obs_expand_flat_f64_kernel<2>), grid, block, lds, stream, a); break;
-                case 3: hipLaunchKernelGGL((obs_expand_flat_f64_kernel<3>), grid, block, lds, stream, a); break;
-                case 4: hipLaunchKernelGGL((obs_expand_flat_f64_kernel<4>), grid, block, lds, stream, a); break;
-                case 5: hipLaunchKernelGGL((obs_expand_flat_f64_kernel<5>), grid, block, lds, stream, a); break;
-                default: hipLaunchKernelGGL((obs_expand_flat_f64_kernel<1>), grid, block, lds, stream, a); break;
-            }
-        } else if (a.nontemporal) hipLaunchKernelGGL(obs_expand_f64_kernel<true>, grid, block, lds, stream, a);
+        if (a.variant == 2 && a.rows_per_wg <= 4) launch_flat<true>(a, grid, block, lds, stream);      // flat slabs (the default)
+        else if (a.nontemporal) hipLaunchKernelGGL(obs_expand_f64_kernel<true>, grid, block, lds, stream, a);
         else hipLaunchKernelGGL(obs_expand_f64_kernel<false>, grid, block, lds, stream, a);
         return hipGetLastError();
     }
@@ -392,14 +416,7 @@ hipError_t launch_obs_expand(const ObsArgs& a, hipStream_t stream) {
         return hipGetLastError();
     }
     if (a.variant == 2 && a.vec == 4 && a.rows_per_wg <= 4) {
-        switch (a.nontemporal) {
-            case 0: hipLaunchKernelGGL((obs_expand_flat_kernel<0>), grid, block, lds, stream, a); break;
-            case 2: hipLaunchKernelGGL((obs_expand_flat_kernel<2>), grid, block, lds, stream, a); break;
-            case 3: hipLaunchKernelGGL((obs_expand_flat_kernel<3>), grid, block, lds, stream, a); break;
-            case 4: hipLaunchKernelGGL((obs_expand_flat_kernel<4>), grid, block, lds, stream, a); break;
-            case 5: hipLaunchKernelGGL((obs_expand_flat_kernel<5>), grid, block, lds, stream, a); break;
-            default: hipLaunchKernelGGL((obs_expand_flat_kernel<1>), grid, block, lds, stream, a); break;
-        }
+        launch_flat<false>(a, grid, block, lds, stream);
         return hipGetLastError();
     }
     if (a.vec == 4) {

@@ -23,7 +23,9 @@ extern "C" {
 #define D2D_TUNE_STEP_ABLATE 9   /* the one key that DOES change results: bit mask of kernel parts to skip (1 interferer walk,
                                     2 mask build, 4 mask clear, 8 result stores, 16 table store, 32 rb/pwr stores, 64 pass-0/1
                                     barriers, 128 per-env loads hit L2, ...) so that the rest can be timed                   */
-#define D2D_TUNE_OBS_STAGGER 16  /* wave w of an obs workgroup sleeps w * value * 64 clocks before its stores; 0 = off       */
+#define D2D_TUNE_OBS_STAGGER 16  /* wave w of an obs workgroup sleeps w * value * 64 clocks before its stores; 0 = off; the
+                                    row-aligned kernel (D2D_TUNE_OBS_VARIANT 3) only: the flat kernels' arguments are the
+                                    preloaded scalars and carry no diagnostic word                                        */
 /* ... and further VALUES of release keys: D2D_TUNE_OBS_NONTEMPORAL 2 sc1, 3 sc0 sc1, 4 sc0 sc1 nt (the scope bits of the
  * gfx942+ store encoding; 5 sc1 nt is the flat kernels' default and a release value, d2d_hip.h); D2D_TUNE_STEP_WALK 1 =
  * membership masks, flattened walk.                                                                                         */

@@ -46,7 +46,7 @@ def main():
     from gym_d2d_amd import build
     src = build.CSRC / a.source
     with tempfile.TemporaryDirectory() as tmp:
-        cmd = [build._hipcc(), *build.FLAGS, *a.defines.split(), '-I', str(build.INCLUDE), '-c', str(src), '-save-temps', '-o', 'x.o']
+        cmd = [build._hipcc(), *build.flags_for(a.source), *a.defines.split(), '-I', str(build.INCLUDE), '-c', str(src), '-save-temps', '-o', 'x.o']
         r = subprocess.run(cmd, cwd=tmp, capture_output=True, text=True)
         if r.returncode:
             sys.exit(r.stderr[-4000:])
