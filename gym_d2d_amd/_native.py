@@ -1,4 +1,4 @@
-"""ctypes binding of libd2d_hip.so (include/d2d_hip.h) and of the side libraries `SIDE`, `SOLVERS`, `ADDONS`, `FAMILIES` and `EXTRAS` list
+"""ctypes binding of libd2d_hip.so (include/d2d_hip.h) and of the side libraries `SIDE`, `SOLVERS`, `ADDONS`, `FAMILIES`, `EXTRAS` and `EXACT` list
 (libd2d_<name>.so, include/d2d_<name>.h).
 There is no CPU fallback: if a library or a gfx950 GPU is missing, the calls below raise."""
 from __future__ import annotations
@@ -96,6 +96,15 @@ BALANCE_MAX_LDS_BYTES = 163840
 STABLE_MAX_LINKS = 2048
 STABLE_MAX_RBS = 8192
 STABLE_MAX_LDS_BYTES = 163840
+# d2d_share_values's law / limits (include/d2d_share.h): the sensing kernel's, the movable links of one call, the background members
+# of an RB that takes movable links, the LDS of one workgroup and the bytes of the value block and the choice words together
+SHARE_LAW_INV_SQUARE, SHARE_LAW_POWER, SHARE_LAW_POW_K = 0, 1, 2
+SHARE_MAX_LINKS = 2048
+SHARE_MAX_RBS = 8192
+SHARE_MAX_MOVABLE = 12
+SHARE_MAX_BACKGROUND = 64
+SHARE_MAX_LDS_BYTES = 163840
+SHARE_MAX_BLOCK_BYTES = 8 << 30
 
 BUFFER_DTYPES = {BUF_ACTIONS: np.int32, BUF_RB: np.int32, BUF_PWR: np.int32, BUF_ENV_FLAGS: np.int32, BUF_RESET_PENDING: np.int32,
                  BUF_EPISODE: np.uint32}
@@ -288,6 +297,13 @@ STABLE_SIGNATURES = {
     'd2d_stable_last_error': (C.c_char_p, []),
 }
 
+# every symbol include/d2d_share.h declares
+SHARE_SIGNATURES = {
+    'd2d_share_values': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, C.c_int64, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
+    'd2d_share_solve': (C.c_int, [_P, _P, C.c_int64, _I, _I, _P, _P, _P, _P, _P]),
+    'd2d_share_last_error': (C.c_char_p, []),
+}
+
 # the side libraries: name -> every symbol include/d2d_<name>.h declares; libd2d_<name>.so, its error text in d2d_<name>_last_error
 SIDE = {'plugin': PLUGIN_SIGNATURES, 'episode': EPISODE_SIGNATURES, 'sense': SENSE_SIGNATURES, 'graph': GRAPH_SIGNATURES,
         'marginal': MARGINAL_SIGNATURES, 'mobility': MOBILITY_SIGNATURES, 'channel': CHANNEL_SIGNATURES, 'queue': QUEUE_SIGNATURES,
@@ -300,6 +316,8 @@ ADDONS = {'assignpwr': ASSIGNPWR_SIGNATURES, 'color': COLOR_SIGNATURES}
 FAMILIES = {'balance': BALANCE_SIGNATURES}
 # build.EXTRAS' libraries, likewise: what joined behind the families
 EXTRAS = {'stable': STABLE_SIGNATURES}
+# build.EXACT's libraries, likewise: what joined behind the extras
+EXACT = {'share': SHARE_SIGNATURES}
 
 _lib: Optional[C.CDLL] = None
 _side: dict = {}                    # name -> the opened, typed side library
@@ -317,6 +335,8 @@ assign_power_weights_launches = 0   # d2d_assign_power_weights launches made thr
 color_launches = 0                  # d2d_color_graph launches made through color_graph()
 balance_launches = 0                # d2d_balance_sinr launches made through balance_sinr()
 stable_launches = 0                 # d2d_stable_match launches made through stable_match()
+share_values_launches = 0           # d2d_share_values launches made through share_values()
+share_solve_launches = 0            # d2d_share_solve launches made through share_solve()
 mobility_launches = 0               # d2d_mobility_move calls made through mobility_move()
 channel_launches = 0                # d2d_channel_fill calls made through channel_fill()
 queue_launches = 0                  # d2d_queue_step calls made through queue_step()
@@ -346,14 +366,15 @@ def side_path(name: str) -> Path:
 
 
 def side_library(name: str) -> C.CDLL:
-    """dlopen libd2d_<name>.so once and type the entry points SIDE[name] (or SOLVERS[name], ADDONS[name], FAMILIES[name], EXTRAS[name]) lists.  Raises if it has not been built."""
+    """dlopen libd2d_<name>.so once and type the entry points SIDE[name] (or SOLVERS[name], ADDONS[name], FAMILIES[name], EXTRAS[name], EXACT[name]) lists.  Raises if it has not been built."""
     lib = _side.get(name)
     if lib is None:
         path = side_path(name)
         if not path.exists():
             raise ImportError(f'{path} is missing - build it with `python -m gym_d2d_amd.build`')
         lib = C.CDLL(str(path))
-        for symbol, (res, args) in (SIDE.get(name) or SOLVERS.get(name) or ADDONS.get(name) or FAMILIES.get(name) or EXTRAS[name]).items():
+        for symbol, (res, args) in (SIDE.get(name) or SOLVERS.get(name) or ADDONS.get(name) or FAMILIES.get(name) or EXTRAS.get(name)
+                                    or EXACT[name]).items():
             fn = getattr(lib, symbol)
             fn.restype = res
             fn.argtypes = args
@@ -385,6 +406,7 @@ def load_assignpwr_library() -> C.CDLL: return side_library('assignpwr')
 def load_color_library() -> C.CDLL: return side_library('color')
 def load_balance_library() -> C.CDLL: return side_library('balance')
 def load_stable_library() -> C.CDLL: return side_library('stable')
+def load_share_library() -> C.CDLL: return side_library('share')
 
 
 # Pointer arguments are passed as the ints they are: every argtype is c_void_p, which takes 0 as the null pointer and any int up to
@@ -605,6 +627,32 @@ def stable_match(link_pref_ptr: int, rb_pref_ptr: int, quota_ptr: int, n_envs: i
         link_pref_ptr, rb_pref_ptr, quota_ptr, n_envs, n_links, n_rbs, col_ptr, load_ptr, proposals_ptr, unmatched_ptr, stream_ptr))
     if n_envs:
         stable_launches += 1
+
+
+def share_values(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, link_tx_ptr: int, link_rx_ptr: int, cols_ptr: int,
+                 cap_cols_ptr: int, law: int, pow_k: int, n_envs: int, n_dev: int, n_links: int, n_rbs: int, movable_links_ptr: int,
+                 n_movable: int, allowed_ptr: int, values_ptr: int, closed_rb_ptr: int, stream_ptr: int = 0) -> None:
+    """d2d_share_values: the total capacity of every RB under every subset of the movable links - values float64 [n_envs, n_rbs,
+    2^n_movable] and closed_rb int32 [n_envs, n_rbs] (device pointers; movable_links_ptr int32 [n_movable], ascending link indices;
+    allowed_ptr 0: every RB, else uint32 [n_links, ceil(n_rbs / 32)])."""
+    global share_values_launches
+    _check_side('share', load_share_library().d2d_share_values(
+        pos_x_ptr, pos_y_ptr, rb_ptr, pwr_ptr, link_tx_ptr, link_rx_ptr, cols_ptr, cap_cols_ptr, law, pow_k, n_envs, n_dev, n_links,
+        n_rbs, movable_links_ptr, n_movable, allowed_ptr, values_ptr, closed_rb_ptr, stream_ptr))
+    if n_envs:
+        share_values_launches += 1
+
+
+def share_solve(values_ptr: int, quota_ptr: int, n_envs: int, n_rbs: int, n_movable: int, choice_ptr: int, col_ptr: int, value_ptr: int,
+                feasible_ptr: int, stream_ptr: int = 0) -> None:
+    """d2d_share_solve: the max-plus subset convolution of float64 values [n_envs, n_rbs, 2^n_movable] over the RBs - col int32
+    [n_envs, n_movable], value float64 and feasible int32 [n_envs] (device pointers; quota_ptr 0: no limit, else int32 [n_rbs];
+    choice_ptr uint16 [n_envs, n_rbs, 2^n_movable], the kernel's own)."""
+    global share_solve_launches
+    _check_side('share', load_share_library().d2d_share_solve(
+        values_ptr, quota_ptr, n_envs, n_rbs, n_movable, choice_ptr, col_ptr, value_ptr, feasible_ptr, stream_ptr))
+    if n_envs:
+        share_solve_launches += 1
 
 
 def mobility_move(pos_x_ptr: int, pos_y_ptr: int, vel_x_ptr: int, vel_y_ptr: int, fixed_mask_ptr: int, n_envs: int, n_cues: int,

@@ -22,7 +22,7 @@ from typing import Optional
 
 import numpy as np
 
-from .. import _native, assignment, balance, best_response, best_response_dynamics, coloring, graph, joint_assignment, marginal, power_control, sensing, stable_matching
+from .. import _native, assignment, balance, best_response, best_response_dynamics, coloring, graph, joint_assignment, marginal, power_control, sensing, sharing, stable_matching
 from .. import evaluate as evaluate_mod
 from .. import mobility as mobility_mod
 from .. import queues as queues_mod
@@ -288,6 +288,8 @@ class VecD2DEnv:
         self._balance = None
         # stable RB matching with quotas (solve_stable_matching(), stable_rbs()): likewise
         self._stable = None
+        # exact optimal RB sharing (sharing_values(), solve_sharing(), share_rbs()): likewise
+        self._share = None
 
     def _setup_autoreset(self) -> None:
         """Refuse what a device-side per-env reset cannot serve, then allocate the per-env bookkeeping: pending / episode are bound
@@ -1153,6 +1155,80 @@ class VecD2DEnv:
         rb = self.stable_rbs(movable, allowed, quota, rb_pref)[0]
         return best_response_dynamics.encode_actions(rb, self._t['pwr'], self._agent_levels(), self.num_links - self.num_agents)
 
+    # ------------------------------------------------------------------ exact optimal RB sharing for small link groups
+    def _share_kernel(self):
+        return self._kernel('_share', sharing, sharing.Sharing, lambda: (self._assignment_kernel(),))
+
+    def sharing_values(self, movable=None, allowed=None, power_dbm=None, out=None):
+        """What every RB is worth under every subset of the movable links, with the background as the last step left it: (values
+        float64 [B, R, 2^M], links int32 [M], closed int32 [B]), a tuple with those names.
+
+        movable: bool [N], the same for every env; None: the DUE-pair links, as assign_rbs() has it.  links holds them in ascending
+        link index and bit a of a subset mask S is links[a]; M must be in 1 .. 12 (D2D_SHARE_MAX_MOVABLE).  Every other link is
+        background: it stays on its RB (an rb outside [0, R) is on no RB and in no value) at its power.  power_dbm: int32 [B, N] on
+        the env's device, in the decoded plane's units, replaces the powers of ALL links, as color_rbs() takes it; None: the
+        decoded plane.  values[b, r, S] is the total capacity of RB r when exactly the movable links of S join r's background: the
+        sum, in double, in ascending link index, of the float32 capacities of all those members, each of them bit for bit
+        evaluate()'s - and so the step's - for that state.  values[b, r, 0] is the background of r alone.  allowed: bool [N, R] as
+        best_rb() takes it; a subset with a link that is not allowed on r is -inf.  An RB whose background has more than 64
+        members (D2D_SHARE_MAX_BACKGROUND) is closed: its S != 0 entries are -inf, its S = 0 entry is still its background's
+        capacity, and closed[b] counts such RBs.
+
+        Links on different RBs do not interfere, so the total capacity of ANY placement of the movable links, several per RB
+        included, is the sum over the RBs of values[b, r, S_r], S_r the movable links placed on r.
+
+        One kernel launch (csrc/d2d_share.hip), grid (env, RB), and one torch sum.  The env is left untouched.  Valid after reset()
+        and after every step(), autoreset and mobility included.  Torch path only: enqueued on torch's current stream, nothing is
+        synchronised; the block the env owns (8 B R 2^M bytes, rewritten by every call), or `out`, a contiguous float64 tensor of
+        that shape.  ValueError for M outside 1 .. 12, for a block that with solve_sharing()'s choice words would exceed 8 GiB
+        (D2D_SHARE_MAX_BLOCK_BYTES), and for what assign_rbs() refuses, under the name share_rbs()."""
+        k = self._share_kernel()
+        self._follow_torch_stream()
+        return k.values(self._t, movable, allowed, power_dbm, out, self._stream_ptr)
+
+    def solve_sharing(self, values, quota=None, out=None):
+        """The optimal many-to-one placement under ANY contiguous float64 [B, R, 2^M] tensor on the env's device (env, RB, subset of
+        the M rows): (col int32 [B, M], value float64 [B], feasible int32 [B]), a tuple with those names.
+
+        The total of a placement is the sum over the RBs of values[b, r, S_r], S_r the rows placed on r.  The optimum is the
+        max-plus subset convolution over the RBs: g[T] = max over S in T of g'[T - S] + values[b, r, S], RB after RB from g[0] = 0.
+        An entry that is not finite (-inf, +inf, NaN) is never chosen.  quota: None (no limit), an int, [R] ints or an int32 [R]
+        tensor; S may sit on r iff popcount(S) <= quota[r], 0 closes r to the rows.  Equal sums go to the numerically lowest S.
+        col[b, a] is the RB of mask bit a.  An env that has no admissible placement is infeasible - every col -1, value 0.0, feasible
+        0 - and does not disturb the others.  Every candidate is one double addition and max is exact: the result does not depend on
+        the order of evaluation, two calls give the same words, and quota 1 gives solve_assignment()'s optimum.
+
+        One kernel launch (csrc/d2d_share.hip), one workgroup per env, every RB inside it out of LDS, which is why M stops at 12.
+        The choice words, 2 B R 2^M bytes, are owned by the env.  Enqueued on torch's current stream, nothing is synchronised.  The
+        env's own tensors, rewritten by every call, or `out` = (col, value, feasible).  Refused as share_rbs() is."""
+        k = self._share_kernel()
+        self._follow_torch_stream()
+        return k.solve(values, quota, out, self._stream_ptr)
+
+    def share_rbs(self, movable=None, allowed=None, quota=None, power_dbm=None, out=None):
+        """The placement of the movable links, SEVERAL PER RB ALLOWED, that maximises the total capacity of the env, the background
+        staying where it is: (rb int32 [B, N], value_mbps float32 [B], feasible int32 [B], closed int32 [B]), a tuple with those
+        names.
+
+        Exact: sharing_values() holds the capacity of every RB under every subset of the movable links, mutual interference of the
+        links that share it included, and solve_sharing() takes the best of all R^M placements - a certificate for color_rbs(),
+        stable_rbs(quota > 1) and best_response_dynamics(), and an optimal "re-place these M <= 12 links" move.  rb is the current
+        plane with every movable link on its optimal RB; an infeasible env (allowed, quota or closed RBs leave no placement) keeps
+        its row, with value 0.0.  value_mbps is the env's TOTAL capacity under rb, float32 of the double optimum, comparable with
+        evaluate(rb, power)['total_mbps'] (a background link on no RB is in neither).  Two kernel launches and the gather and
+        scatter of the columns.  movable, allowed, power_dbm and closed as sharing_values(); quota as solve_sharing().  `out` =
+        (rb, value_mbps, feasible, closed)."""
+        k = self._share_kernel()
+        self._follow_torch_stream()
+        return k.rbs(self._t, movable, allowed, quota, power_dbm, out, self._stream_ptr)
+
+    def share_rbs_actions(self, movable=None, allowed=None, quota=None, power_dbm=None):
+        """share_rbs() as an action tensor, int32 [B, num_agents], ready for step(): every agent link on its RB of share_rbs() at
+        its current power level, encoded rb * power levels + level, as assign_rbs_actions() does.  Composes with
+        power_control_actions() the same way."""
+        rb = self.share_rbs(movable, allowed, quota, power_dbm)[0]
+        return best_response_dynamics.encode_actions(rb, self._t['pwr'], self._agent_levels(), self.num_links - self.num_agents)
+
     # ------------------------------------------------------------------ joint RB and power matching with SINR floors
     def _joint_assignment_kernel(self):
         return self._kernel('_joint', joint_assignment, joint_assignment.JointAssignment,
@@ -1363,4 +1439,7 @@ class VecD2DEnv:
         if self._stable is not None:
             self._stable.close()
             self._stable = None
+        if self._share is not None:
+            self._share.close()
+            self._share = None
         self.simulator.handle.close()
