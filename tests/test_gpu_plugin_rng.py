@@ -3,7 +3,9 @@ the oracle's restatement of it (ShadowSpec.normals) and independent of how the e
 tests, both widths inside guard elements at the shapes where csrc/d2d_plugin.hip's normal_kernel takes its other paths: tails of 1
 to 3 elements, fewer elements than a vector, row and env carries inside a vector, 65536 rows, 65536 columns, more vectors than
 the capped grid holds, and the refusal of a pointer off 16 bytes.  Not covered: blocks of 2^32 elements and more (the 64-bit index
-arithmetic, narrow == 0: 16 GiB planes), and gain_from_db_kernel, one expression per element without an entry point of its own.
+arithmetic, narrow == 0: 16 GiB planes).  gain_from_db_kernel, one expression per element without an entry point of its own, is
+covered by test_gpu_table_route.py through d2d_set_path_loss_link_table_dev: both widths against the float64 reference and, bit for
+bit, against the conversion inside the step, and past its capped grid at 2 x 1100 x 1100 float64 and 2048 x 2048 float32 entries.
 
 Measured on an MI355X (256 CUs): 44 tail-and-carry cases, 88 launches, worst |got - oracle| 6.76e-7 (2 x 1 x 65536, kind 1,
 first_env 2^32 - 2) at the bar of 1e-6, float32 equal to float64 cast once in every case; past the capped grid 24 x 600 x 600
@@ -99,8 +101,8 @@ def _oracle(n_envs, first_env, n_rows, n_cols, step, kind, seed):
 @pytest.mark.parametrize('n_envs,n_rows,n_cols,kind', EDGE_SHAPES)
 def test_plugin_normal_tails_and_carries_match_the_oracle(n_envs, n_rows, n_cols, kind, last_envs, step):
     """Both widths inside guards, against ShadowSpec.normals at the file's bar; first_env 0 or the last envs of the 32-bit counter
-    word.  Not covered: blocks of 2^32 elements and more (the 64-bit index arithmetic; 16 GiB), and gain_from_db_kernel, which is
-    one expression per element and has no entry point of its own."""
+    word.  Not covered: blocks of 2^32 elements and more (the 64-bit index arithmetic; 16 GiB).  (gain_from_db_kernel, which is one
+    expression per element and has no entry point of its own: test_gpu_table_route.py.)"""
     torch = pytest.importorskip('torch')
     first_env = 2 ** 32 - n_envs if last_envs else 0
     ref = _oracle(n_envs, first_env, n_rows, n_cols, step, kind, SEED)

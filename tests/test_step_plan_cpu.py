@@ -2,14 +2,12 @@
 which StepArgs geometry.  tests/c/step_plan.cpp drives plan_step, compiled with hipcc as host code; every kernel the table names
 must exist in the gfx950 code object of d2d_step.hip / d2d_rollout.hip.  The table holds the BASELINE configurations and the
 configurations the GPU tests describe by the kernel that serves them."""
-import json
 import re
-import subprocess
-from pathlib import Path
 
 import pytest
 
-ROOT = Path(__file__).resolve().parent.parent
+from step_plan_util import build_step_plan, kernel_names as _kernel_names, mangled as _mangled
+
 GEOMETRY = ('lpt', 'tpe', 'epw', 'mask_words', 'walk', 'fuse_obs', 'rec_uniform', 'nt_results', 'prefetch_envs', 'obs_expand')
 
 # (id, StepInputs as key=value - unnamed fields keep step_plan.cpp's defaults: one env of one link on one RB, SystemCapacity,
@@ -70,18 +68,7 @@ REFUSALS = [
 
 @pytest.fixture(scope='module')
 def plan(tmp_path_factory):
-    from gym_d2d_amd import build
-    exe = tmp_path_factory.mktemp('plan') / 'step_plan'
-    cmd = [build._hipcc(), '-O1', '-std=c++17', '-Wall', '-x', 'hip', '--offload-host-only', '-I', str(build.INCLUDE),
-           str(build.CSRC / 'd2d_plan.hip'), str(ROOT / 'tests' / 'c' / 'step_plan.cpp'), '-o', str(exe)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-
-    def run(configs):
-        r = subprocess.run([str(exe), *configs], capture_output=True, text=True, timeout=60)
-        assert r.returncode == 0, r.stderr
-        return [json.loads(line) for line in r.stdout.splitlines()]
-    return run
+    return build_step_plan(tmp_path_factory.mktemp('plan'))
 
 
 def test_plans(plan):
@@ -97,23 +84,6 @@ def test_plans(plan):
 def test_refusals(plan):
     got = plan([case[1] for case in REFUSALS])
     assert [(p.get('error'), p.get('message')) for p in got] == [(code, message) for _, _, code, message in REFUSALS]
-
-
-def _kernel_names(tmp_path, source):
-    from gym_d2d_amd import build
-    cmd = [build._hipcc(), *build.FLAGS, '-I', str(build.INCLUDE), '-c', str(build.CSRC / source), '-save-temps', '-o', 'k.o']
-    r = subprocess.run(cmd, cwd=tmp_path, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    asm = next(tmp_path.glob('*gfx950*.s')).read_text()
-    return set(re.findall(r'^\s+\.name:\s+(_ZN3d2d\w+)$', asm, flags=re.M))
-
-
-def _mangled(kernel):
-    mode, *args = re.match(r'\w+<(.*)>', kernel).group(1).split(',')
-    if kernel.startswith('rollout_kernel'):
-        return f'_ZN3d2d14rollout_kernelILi{mode}ELi{args[0]}ELi{args[1]}EEEvNS_8StepArgsE'
-    lpt, full, hot, opt = args
-    return f'_ZN3d2d11step_kernelILi{mode}ELi{lpt}ELb{int(full == "true")}ELi{hot}ELi{opt}EEEvNS_8StepArgsE'
 
 
 def test_every_planned_kernel_is_instantiated(tmp_path):
