@@ -22,7 +22,7 @@ from typing import Optional
 
 import numpy as np
 
-from .. import _native, assignment, balance, best_response, best_response_dynamics, coloring, graph, joint_assignment, marginal, power_control, sensing, sharing, stable_matching
+from .. import _native, assignment, balance, best_response, best_response_dynamics, coloring, graph, joint_assignment, marginal, power_ascent, power_control, sensing, sharing, stable_matching
 from .. import evaluate as evaluate_mod
 from .. import mobility as mobility_mod
 from .. import queues as queues_mod
@@ -290,6 +290,8 @@ class VecD2DEnv:
         self._stable = None
         # exact optimal RB sharing (sharing_values(), solve_sharing(), share_rbs()): likewise
         self._share = None
+        # sum-capacity power ascent with SINR floors (power_ascent()): likewise
+        self._ascent = None
 
     def _setup_autoreset(self) -> None:
         """Refuse what a device-side per-env reset cannot serve, then allocate the per-env bookkeeping: pending / episode are bound
@@ -954,6 +956,66 @@ class VecD2DEnv:
         first, p_min, levels = self._agent_power_levels()
         return power_control.encode_actions(self._t['rb'], power, p_min, levels, first)
 
+    # ------------------------------------------------------------------ sum-capacity power ascent
+    def _power_ascent_kernel(self):
+        return self._kernel('_ascent', power_ascent, power_ascent.PowerAscent, lambda: (*self._class_bounds(), self._agent_links()))
+
+    def power_ascent(self, adjustable=None, floor_sinr_db=None, start: str = 'held', min_gain_mbps: float = 0.0, max_rounds: int = 16,
+                     out=None, env_mask=None):
+        """The powers a coordinate ascent on the total capacity ends at, with the protected links kept above their SINR floors and
+        positions and RBs as the last step left them: (power_dbm int32 [B, N], sinr_db float32 [B, N], capacity_mbps float32 [B, N],
+        rounds int32 [B], moves int32 [B], converged uint8 [B]), a tuple with those names.
+
+        A link is on an RB iff 0 <= rb < R; the group of RB r is the set of links on r in ascending link index; groups do not
+        interact.  An adjustable link on an RB begins at its held power (start='held'), the lowest (start='min') or the highest
+        (start='max') power of its class; every other link keeps its held power throughout.
+
+        A turn of the adjustable link i on RB r, at the current power vector p: for every level q of i's class let p^q be p with
+        p[i] = q, and sinr_m(q), cap_m(q) the float32 values evaluate() gives the member m of r's group for (rb, p^q), bit for bit.
+        T(q) is the sum, in double, in ascending link index, of cap_m(q) over the group.  q is admissible iff q == p[i], or every
+        member m of the group (i included) with a floor above -inf has sinr_m(q) >= floor[m] or sinr_m(p[i]) < floor[m] (float32
+        comparisons, NaN compares false): a member already under its floor constrains nothing, as in assign_rbs_power(), and a
+        member that meets its floor is never pushed under it.  best is the lowest admissible level whose T is maximal among the
+        admissible levels (a NaN T is never chosen), and link i moves to best, at once, iff T(best) - T(p[i]) > min_gain_mbps.
+
+        The adjustable links take turns in ascending link index, each seeing the moves made before its turn (Gauss-Seidel).  A
+        round that moves nobody ends the ascent (converged 1, rounds = the rounds that moved a link); so do max_rounds rounds that
+        each moved a link (converged 0, rounds == max_rounds).  moves counts the moves.  Groups are independent: rounds is the
+        largest per-group count, moves the sum over the groups, converged 1 iff every group saw a quiet round.  Every move strictly
+        raises its group's T, which is a function of the group's power vector alone, so no state repeats: termination is a
+        property, and max_rounds only bounds the launch.  sinr_db and capacity_mbps are evaluate()'s planes for (rb, power_dbm), for
+        every link.  All turns of an env run in one workgroup of ONE kernel launch (csrc/d2d_ascent.hip) out of LDS: a wave owns an
+        RB group, its 64 lanes the power levels of the link whose turn it is.  One long group runs on one wave (G^2 pair
+        evaluations per turn): that is the known limit.  Valid after reset() and after every step(), autoreset steps included, as
+        power_control() is; with mobility= at the current positions.
+
+        adjustable: bool [N], the links that take turns; None: every agent link.  Links on fixed actions (cue_actions='traffic')
+        never move; neither does a link on no RB.  floor_sinr_db: None (no floors), a number, {'cue': x, 'due': y} or [N] values
+        (array or tensor), dB; -inf: no floor for that link.  min_gain_mbps: finite, >= 0.  max_rounds: 1 .. 4096.  The bounds are
+        the ones step() decodes, as in power_control(); a class of more than 64 power levels is refused.  env_mask: bool / uint8
+        [B], envs whose entry is 0 keep their rows; None: all.
+
+        Torch path only: enqueued on torch's current stream, nothing is synchronised; the six tensors the env owns, rewritten by
+        every call (clone them to keep them), or `out` = (power_dbm, sinr_db, capacity_mbps, rounds, moves, converged), contiguous
+        int32 / float32 / float32 [B, N], int32 / int32 / uint8 [B] on the env's device.  Serves what power_control() serves, as far
+        as an env fits the LDS of one workgroup; ValueError for export_actions=False, ShadowingPathLoss, every table route, pinned
+        device_config coordinates float32 cannot hold."""
+        k = self._power_ascent_kernel()
+        adj, floor = k.adjustable(adjustable), k.floor(floor_sinr_db, self.num_cues)
+        self._follow_torch_stream()
+        return k.solve(self._t, adj, floor, start, min_gain_mbps, max_rounds, out, self._stream_ptr, env_mask)
+
+    def power_ascent_actions(self, adjustable=None, floor_sinr_db=None, start: str = 'held', min_gain_mbps: float = 0.0,
+                             max_rounds: int = 16):
+        """power_ascent() as an action tensor, int32 [B, num_agents], ready for step(): every agent link stays on its RB (as the
+        decoded planes hold it) at the solved power, encoded rb * power levels + level (power_control.encode_actions); an agent
+        link that is not adjustable repeats its last action.  Links on fixed actions (cue_actions='traffic') have no column.
+        Composes with color_rbs_actions(), stable_rbs_actions() and best_response_dynamics_actions(): one call picks RBs, this one
+        picks powers."""
+        power = self.power_ascent(adjustable, floor_sinr_db, start, min_gain_mbps, max_rounds)[0]
+        first, p_min, levels = self._agent_power_levels()
+        return power_control.encode_actions(self._t['rb'], power, p_min, levels, first)
+
     # ------------------------------------------------------------------ sequential best-response dynamics
     def _best_response_dynamics_kernel(self):
         return self._kernel('_brdyn', best_response_dynamics, best_response_dynamics.BestResponseDynamics,
@@ -1442,4 +1504,7 @@ class VecD2DEnv:
         if self._share is not None:
             self._share.close()
             self._share = None
+        if self._ascent is not None:
+            self._ascent.close()
+            self._ascent = None
         self.simulator.handle.close()
