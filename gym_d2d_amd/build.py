@@ -33,7 +33,7 @@ ARCH = 'gfx950'
 
 SOURCES = ['d2d_step.hip', 'd2d_rollout.hip', 'd2d_obs.hip', 'd2d_reset.hip', 'd2d_gain.hip', 'd2d_plan.hip', 'd2d_capi.hip']
 # library stem -> its sources, in build order: the one table the digest, the up-to-date test, the compile and the link iterate
-LIBRARIES = {'hip': SOURCES, 'probe': ['d2d_probe.hip'],
+LIBRARIES = {'hip': SOURCES, 'probe': ['d2d_probe.hip', 'd2d_devfn.hip'],
              **{stem: [f'd2d_{stem}.hip'] for stem in ('plugin', 'episode', 'sense', 'graph', 'marginal', 'mobility', 'channel', 'queue',
                                                        'bestrb', 'powerctl', 'brdyn', 'evaluate')}}
 # libraries that are no add-on kernel family of the table above (which _native.SIDE mirrors entry for entry): built and stamped

@@ -87,10 +87,21 @@ namespace {
 
 thread_local std::string g_probe_error;
 
-int probe_fail(const std::string& msg) noexcept {
+}  // namespace
+
+namespace d2d {
+
+// the library's one error text: the device-function wrappers (d2d_devfn.hip) declare this and report through it
+__attribute__((visibility("hidden"))) int probe_fail(const std::string& msg) noexcept {
     try { g_probe_error = msg; } catch (...) { }
     return 1;
 }
+
+}  // namespace d2d
+
+namespace {
+
+using d2d::probe_fail;
 
 struct DeviceScope {
     int prev = -1;

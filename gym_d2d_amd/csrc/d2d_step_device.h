@@ -56,20 +56,25 @@ __device__ __forceinline__ void wave_sum_halves(float v, float& lo, float& hi) {
 }
 
 // (d^2)^h for h = -e/2 given as a head + tail pair (h.x: the 12 leading bits of h, so that h.x * exponent is exact; h.y = h - h.x,
-// both built by the host in double precision, d2d_capi.hip::refresh_tables), to ~2.5e-7 relative.  log2 of the mantissa and the
+// both built by the host in double precision, d2d_capi.hip::refresh_tables), to 2.7e-7 relative (the worst against float64 over d^2 in
+// [1e-2, 1e12], e in [2, 4.6]: 2.67e-7 at d = 69 km, e = 4.29; tests/test_gpu_devfn.py).  log2 of the mantissa and the
 // integer exponent are handled separately so the error does not scale with |log2(d^2)| (a plain exp2(h*log2(x)) loses ~2e-6), and
 // the EXPONENT ITSELF carries more than float precision: a float32 e is off by up to 6e-8 relative, which (d^2)^(-e/2) amplifies by
 // ln(d^2) * e/2 - 1.2e-6 at 300 m with COST-Hata's e = 3.5, the largest single term of the power-law modes' error until round 3.
 __device__ __forceinline__ float pow_neg_half(float d2, float2 h) {
     // Contraction OFF in here: hipcc's default -ffp-contract=fast fuses products into the additions below, and the head / tail
-    // arithmetic then adds exact residuals to unrounded terms.  Measured on the hardware (tools/probes/pow_accuracy.hip, the r2 form
-    // of this function): max relative error 1.56e-6 as the compiler fused it, 2.5e-7 as written.
+    // arithmetic then adds exact residuals to unrounded terms.  Measured on the hardware (round 2's form of this function): max
+    // relative error 1.56e-6 as the compiler fused it, 2.5e-7 as written; this form is held against float64 by tests/test_gpu_devfn.py
+    // (the figure above).
 #pragma clang fp contract(off)
     const float m = __builtin_amdgcn_frexp_mantf(d2);       // [0.5, 1)
     const float fe = (float)__builtin_amdgcn_frexp_expf(d2);
-    // v_log_f32 = log2, in [-1, 0); log2(0) = -inf is held at -1e30 so that the tail product below stays finite and d2 == 0
-    // still ends in exp2(+huge) = +inf (0 * -inf or +x * -inf in the tail made it NaN, unlike the 1 / d^2 mode)
-    const float l = fmaxf(__builtin_amdgcn_logf(m), -1.0e30f);
+    // v_log_f32 = log2, in [-1, 0) for every finite d2 > 0; log2(0) = -inf is held at -1e30 so that the tail product below stays finite
+    // and d2 == 0 still ends in exp2(+huge) = +inf (0 * -inf or +x * -inf in the tail made it NaN, unlike the 1 / d^2 mode), and
+    // log2(+inf) = +inf at 1e30 for the same reason: d2 == +inf ends in exp2(-huge) = 0 (0 * +inf or -x * +inf in the tail made THAT
+    // NaN under every exponent whose tail is not negative).  By v_minimum3_f32 / v_maximum3_f32, which hand a NaN on where
+    // v_max_f32 returns its other operand: a NaN d2 stays a NaN.
+    const float l = __builtin_elementwise_maximum(__builtin_elementwise_minimum(__builtin_amdgcn_logf(m), 1.0e30f), -1.0e30f);
     const float p = h.x * fe;                               // exact: 12 bits x at most 8
     const float ip = rintf(p);
     const float fr = (p - ip) + fmaf(h.x, l, h.y * (l + fe));
@@ -96,8 +101,9 @@ __device__ __forceinline__ float pow10_tenth(int p) {
 //                  which is wave-uniform, taken once for the whole group of pairs;
 //   (d^2)^phi      exp2(phi log2(d^2)), phi = -(n - k) / 2 in [-1/4, 1/4]: v_log's relative ulp on log2(d^2) <= 20 is an absolute
 //                  3e-7 in the exponent at most (the general split, pow_neg_half, exists because at |h| ~ 2 the same ulp is 2.4e-6).
-// About 4e-7 relative in all.  Every kernel calls this with the same association of the products (NP = 1 for a single pair), so
-// they agree bit for bit.  A zero distance ends non-finite (inf from the reciprocal, or NaN from inf * 0), as with 1 / d^2.
+// 6.9e-7 relative in all, with the rounding of the reciprocal and of up to four products on top (the worst against float64 over
+// d^2 in [1e-2, 1e6], k in 1 .. 8: 6.85e-7 at k = 6, d = 613 m, phi = 0.2488; tests/test_gpu_devfn.py).  Every kernel calls this
+// with the same association of the products (NP = 1 for a single pair), so they agree bit for bit.  A zero distance ends non-finite (inf from the reciprocal, or NaN from inf * 0), as with 1 / d^2.
 // KC != 0: k is known at compile time (the rollout kernel branches ONCE on the common case k == 4 and runs a copy of its pair section
 // without the tests on k: a taken branch costs a wave its instruction buffer); the operations, hence the bits, are the same.
 template <int NP, int KC = 0>
@@ -167,7 +173,8 @@ __device__ __forceinline__ void philox_step(unsigned c0, unsigned c1, unsigned c
 
 // cos(2 pi u) for u = k * 2^-24 in [0, 1): the quadrant reduction is EXACT in these units (4u splits into an integer quadrant and a
 // fraction with no rounding), then one rounding of x = f * pi / 2 and a minimax polynomial on [-pi/4, pi/4] (the reset sampler's
-// sincos_turns, csrc/d2d_reset.hip).  cosf(fl(2 pi u)) carries the argument's rounding - 3.7e-7 near 2 pi, times a Gaussian of up
+// sincos_turns, csrc/d2d_reset.hip): 1.07e-7 absolute at worst over all 2^24 arguments (at k = 2094735; tests/test_gpu_devfn.py).
+// cosf(fl(2 pi u)) carries the argument's rounding - 3.7e-7 near 2 pi, times a Gaussian of up
 // to 5.9, times chi dB: most of the 1e-5 bar where |sinr_db| < 1.
 __device__ __forceinline__ float cos_turns(float u) {
     const float t = 4.0f * u;                                           // [0, 4), exact
@@ -185,7 +192,9 @@ __device__ __forceinline__ float cos_turns(float u) {
 // Standard normal z of the call (tx link j -> rx link i, kind) of step `step` in env `env`: Box-Muller of Philox4x32-10 with counter
 // (env, step, j | i << 16, kind) and key (seed_lo, seed_hi).  Shared by the step kernel's shadowing (shadow_factor) and the plugin
 // library's generator (csrc/d2d_plugin.hip, ArrayPathLoss's view.normal()), so a plugin that adds chi * z draws what PL_SHADOW draws.
-// Box-Muller to ~1e-7 absolute in z (round 6; the oracle does the same transform of the same words in double): u1 = (k + 0.5) 2^-24 is
+// Box-Muller to 5.6e-7 absolute in z (the worst over 2^20 counters: 5.51e-7 at z = -2.88, where logf's ulp, cos_turns' 1.07e-7 times
+// the radius and the product's rounding add up; 3.5e-7 relative on the shadowing factor at chi = 2.7 dB; tests/test_gpu_devfn.py)
+// (round 6; the oracle does the same transform of the same words in double): u1 = (k + 0.5) 2^-24 is
 // a float32 value only for k < 2^23 - above, k + 0.5 needs 25 bits and rounds, and near u1 = 1 the Gaussian's radius sqrt(-2 ln u1)
 // amplifies that by 1 / (z u1) (z = 0.01: 3e-6; the largest k: the radius itself) - so the upper half goes through
 // log1p(-(1 - u1)), whose argument (2^24 - k - 0.5) 2^-24 IS exact; the angle by cos_turns.
