@@ -58,7 +58,9 @@ class Assignment(PairKernel):
 
     def links(self, movable):
         """(host int32 [M], device int32 [M]): the movable links in ascending link index - the DUE-pair links (None), or the links
-        `movable` (bool [N], array or tensor) marks, every one of which must have an action column."""
+        `movable` (bool [N], array or tensor) marks, every one of which must have an action column.  A TENSOR is read on the host -
+        the number of movable links shapes every output - which waits for everything queued before it on its stream; a host array
+        is uploaded (a synchronous copy) when it differs from the last call's, and a repeat comes from the cache."""
         torch = self.torch
         if movable is None:
             host = self.due

@@ -64,7 +64,8 @@ class Coloring(PairKernel):
         return self.agent_subset(movable, 'movable')
 
     def margin(self, margin_db, num_cues: int):
-        """float32 [N] on the device from a number, {'cue': x, 'due': y} or [N] values (array or tensor), dB; NaN is refused."""
+        """float32 [N] on the device from a number, {'cue': x, 'due': y} or [N] values (array or tensor), dB; NaN is refused - in a
+        TENSOR by reading it on the host, which waits for everything queued before it on its stream."""
         t = link_values(self, margin_db, num_cues, 'margin_db')
         if self.torch.is_tensor(margin_db) and bool(self.torch.isnan(t).any()):
             raise ValueError(f'margin_db must be a number, {{"cue": x, "due": y}} or [{self.n}] values, none of them NaN')

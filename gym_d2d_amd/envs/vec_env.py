@@ -888,7 +888,8 @@ class VecD2DEnv:
         autoreset steps included, as sense() is.
 
         target_sinr_db: a number, {'cue': x, 'due': y}, or [N] values (array or tensor), dB.  adjustable: bool [N], the links that
-        may move; None: every agent link.  Links on fixed actions (cue_actions='traffic') are never adjusted; a link that is not
+        may move (array, or a tensor that is combined with the agent links on the device and never read on the host); None: every
+        agent link.  Links on fixed actions (cue_actions='traffic') are never adjusted; a link that is not
         adjusted keeps its power and interferes; a link on no RB (rb outside [0, R)) keeps its power and has sinr_db NaN.  The
         bounds are the ones step() decodes: an agent's power is its action's level, 0 .. levels - 1 dBm (due_min_tx_power_dBm is
         not added back, as in d2d_env.py:94-96).  env_mask: bool / uint8 [B], envs whose entry is 0 keep their rows; None: all.
@@ -1113,7 +1114,9 @@ class VecD2DEnv:
         links int32 [M]), and harm float32 [B, M, R] behind them if harm=True.
 
         movable: bool [N] (tensor or array), the same for every env; None: the DUE-pair links.  Row a is the a-th movable link in
-        ascending link index, links[a].  Every other link is background: it stays on its current RB and power (an rb outside
+        ascending link index, links[a].  A movable TENSOR is read on the host, here and in every call that takes `movable` as this
+        one does (assign_rbs(), stable_rbs(), sharing_values(), share_rbs(), joint_assignment_weights(), assign_rbs_power() and
+        their *_actions forms): the number of movable links shapes the outputs, so that form waits for what is queued before it.  Every other link is background: it stays on its current RB and power (an rb outside
         [0, R) is on no RB).  The movable links are taken off the air: their current RB plays no part, their current power is the
         power they are placed with.  own[b, a, r] is link a's capacity (Mbps, the step's definition) alone with the background
         members of r; harm[b, a, r] what those members lose to it, 0.0 exactly on an RB without them, a victim pushed under its
@@ -1385,7 +1388,8 @@ class VecD2DEnv:
         coupling()[b, i, j] + p[b, j] >= (coupling()[b, i, i] + p[b, i]) - margin_db[i], every operation in float32 in that
         association (the receiver gains are on both sides, which is why coupling() fits although it carries none).  p is the
         decoded power plane, or power_dbm (int32 [B, N] on the env's device) - power_control()'s powers, say.  margin_db: a number,
-        {'cue': x, 'due': y} or [N] values (array or tensor), dB; -inf: that link is never a victim; NaN is a ValueError.
+        {'cue': x, 'due': y} or [N] values (array or tensor), dB; -inf: that link is never a victim; NaN is a ValueError - which a
+        margin_db TENSOR is read on the host for: that form waits for what is queued before it, every other one is enqueue-only.
 
         When proper is 1 every same-RB pair with an end that took a turn keeps those PAIRWISE margins.  Nothing is said about the
         aggregate SINR of several co-channel links, and there is no optimality certificate as assign_rbs() has one; several links

@@ -96,12 +96,13 @@ class PathLossView:
     an interferer's (simulator.py:97-101) - the pairs d2d_set_path_loss_link_table names."""
 
     def __init__(self, xp, tx_x, tx_y, rx_x, rx_y, tx_devices, rx_devices, like=None, *, step: int = 0, first_env: int = 0,
-                 seed: int = 0):
+                 seed: int = 0, columns: Optional[dict] = None):
         self.xp = xp
         self.tx_x, self.tx_y, self.rx_x, self.rx_y = tx_x, tx_y, rx_x, rx_y
         self.tx_devices, self.rx_devices = list(tx_devices), list(rx_devices)
         self._like = like if like is not None else tx_x
         self.step, self.first_env, self.seed = int(step), int(first_env), int(seed)
+        self._columns = columns if columns is not None else {}     # uploaded columns by value: the caller's, kept from view to view
 
     def normal(self, kind: int = 0):
         b, n = tuple(self.tx_x.shape)
@@ -131,7 +132,14 @@ class PathLossView:
     def _column(self, devices, fn, shape):
         vals = np.array([float(fn(d)) for d in devices], dtype=np.float64).reshape(shape)
         if self.xp.__name__ == 'torch':
-            return self.xp.as_tensor(vals, device=self._like.device)
+            # a column is uploaded (a synchronous copy) when its values are new; a repeat is a device-side copy of the kept one,
+            # so that a per-step model's evaluation stays enqueue-only and the caller still gets a tensor of its own
+            key = (vals.tobytes(), vals.shape, str(self._like.device))
+            if key not in self._columns:
+                if len(self._columns) >= 64:         # a model whose columns change from step to step: keep the dict bounded
+                    self._columns.clear()
+                self._columns[key] =self.xp.as_tensor(vals, device=self._like.device)
+            return self._columns[key].clone()
         return vals
 
     def tx_column(self, fn):

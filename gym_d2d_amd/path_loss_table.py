@@ -94,6 +94,10 @@ class PathLossTable:
         # per_step: positions may move on the device between steps (VecD2DEnv(autoreset=True) resets envs inside step()): the
         # per-link coordinates are gathered from POS_X / POS_Y again before every step
         self.device_resets = False
+        # per_step: what compute(view) would otherwise upload before every step - a synchronous copy each - is uploaded once per
+        # link list: the link index tensors of _link_coordinates and the view's per-device columns (PathLossView._column)
+        self.link_index = None
+        self.columns = {}
 
     def install(self) -> None:
         """Hand the native route's law to the handle and draw the seeds (again: restarts the built-in shadowing's stream)."""
@@ -128,6 +132,7 @@ class PathLossTable:
     def links_changed(self, link_tx: np.ndarray, link_rx: np.ndarray) -> None:
         self.link_tx, self.link_rx = link_tx, link_rx
         self.cols, self.live_bound = None, False    # d2d_set_links drops a table bound for the old list
+        self.link_index, self.columns = None, {}
         if self.channel is not None:
             self.channel.links = None
         if self.positions_known:
@@ -221,7 +226,9 @@ class PathLossTable:
         """(tx_x, tx_y, rx_x, rx_y) [B, N] of every link as tensors on `dev`: host-supplied positions as given (float64 possible),
         the Device objects' float64 positions for one env, else POS_X / POS_Y where the device-side reset wrote them (sync = False:
         the handle runs on torch's current stream, which orders the gather after the reset)."""
-        jt, jr = (torch.as_tensor(j.astype(np.int64), device=dev) for j in (self.link_tx, self.link_rx))
+        if self.link_index is None:
+            self.link_index = tuple(torch.as_tensor(j.astype(np.int64), device=dev) for j in (self.link_tx, self.link_rx))
+        jt, jr = self.link_index
         if self.positions is not None:
             p = torch.as_tensor(self.positions, device=dev)
         elif self.num_envs == 1 and not self.device_resets:
@@ -250,7 +257,8 @@ class PathLossTable:
             b1 = min(self.num_envs, b0 + chunk)
             part = cols if (b0, b1) == (0, self.num_envs) else tuple(c[b0:b1] for c in cols)
             res = self.model.compute(PathLossView(torch, *part, txd, rxd, like=cols[0], step=self.step,
-                                                  first_env=self.handle.env_offset + b0, seed=self.seed))
+                                                  first_env=self.handle.env_offset + b0, seed=self.seed,
+                                                  columns=self.columns))
             pl, snr = res if isinstance(res, tuple) else (res, None)
             if tuple(pl.shape) != (b1 - b0, n, n):
                 raise ValueError(f'ArrayPathLoss.compute must return [{b1 - b0},{n},{n}], got {tuple(pl.shape)}')

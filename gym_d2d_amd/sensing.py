@@ -206,6 +206,7 @@ class PairKernel:
             self.mem = _HipMemory()
             self.ptrs = tuple(self.mem.upload(a) for a in host.values())
         self._subset = None                          # (key, tensor) of the last agent_subset(): a repeated mask is not uploaded again
+        self._agent_dev = None                       # self.agent on the device, for an agent_subset() that is given a tensor
 
     def env_mask(self, env_mask):
         """None, or `env_mask` (bool / uint8 [B], tensor or array) as a contiguous uint8 tensor on the device."""
@@ -219,12 +220,20 @@ class PairKernel:
 
     def agent_subset(self, subset, name: str):
         """uint8 [N] on the device: the links of `self.agent` (None), or those of them `subset` (bool [N], array or tensor) marks;
-        `name` is what a refusal calls the argument."""
+        `name` is what a refusal calls the argument.  A tensor is never read on the host: it is refused by its metadata and
+        `subset & agent` is formed on the device, a fresh tensor per call, on the current stream (nothing is synchronised).  A host
+        array is uploaded when it differs from the last one - a synchronous copy - and a repeat comes from the cache."""
         torch = self.torch
+        if torch.is_tensor(subset):
+            if tuple(subset.shape) != (self.n,) or subset.dtype != torch.bool:
+                raise ValueError(f'{name} must be bool [{self.n}] (link) or None')
+            if self._agent_dev is None:              # uploaded once, by the first call that passes a tensor
+                self._agent_dev = torch.as_tensor(self.agent, device=self.device)
+            return (subset.to(self.device) & self._agent_dev).to(torch.uint8)
         if subset is None:
             host = self.agent
         else:
-            host = subset.cpu().numpy() if torch.is_tensor(subset) else np.asarray(subset)
+            host = np.asarray(subset)
             if host.shape != (self.n,) or host.dtype != np.bool_:
                 raise ValueError(f'{name} must be bool [{self.n}] (link) or None')
             host = host & self.agent
