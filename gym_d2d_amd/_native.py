@@ -1,4 +1,4 @@
-"""ctypes binding of libd2d_hip.so (include/d2d_hip.h) and of the side libraries `SIDE`, `SOLVERS`, `ADDONS`, `FAMILIES`, `EXTRAS`, `EXACT` and `GROWING` list
+"""ctypes binding of libd2d_hip.so (include/d2d_hip.h) and of the side libraries `SIDE`, `SOLVERS`, `ADDONS`, `FAMILIES`, `EXTRAS`, `EXACT`, `GROWING` and `LATER` list
 (libd2d_<name>.so, include/d2d_<name>.h).
 There is no CPU fallback: if a library or a gfx950 GPU is missing, the calls below raise."""
 from __future__ import annotations
@@ -114,6 +114,12 @@ ASCENT_MAX_RBS = 8192
 ASCENT_MAX_LEVELS = 64
 ASCENT_MAX_ROUNDS = 4096
 ASCENT_MAX_LDS_BYTES = 163840
+# d2d_rb_ascent's law / limits (include/d2d_rbascent.h): d2d_evaluate's, the rounds of one launch and the LDS of one workgroup
+RBASCENT_LAW_INV_SQUARE, RBASCENT_LAW_POWER, RBASCENT_LAW_POW_K = 0, 1, 2
+RBASCENT_MAX_LINKS = 2048
+RBASCENT_MAX_RBS = 8192
+RBASCENT_MAX_ROUNDS = 4096
+RBASCENT_MAX_LDS_BYTES = 163840
 
 BUFFER_DTYPES = {BUF_ACTIONS: np.int32, BUF_RB: np.int32, BUF_PWR: np.int32, BUF_ENV_FLAGS: np.int32, BUF_RESET_PENDING: np.int32,
                  BUF_EPISODE: np.uint32}
@@ -320,6 +326,13 @@ ASCENT_SIGNATURES = {
     'd2d_ascent_last_error': (C.c_char_p, []),
 }
 
+# every symbol include/d2d_rbascent.h declares
+RBASCENT_SIGNATURES = {
+    'd2d_rb_ascent': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, C.c_int64, _I, _I, _I, _P, _P, _P, C.c_double, _I, _P, _P, _P, _P,
+                                _P, _P, _P, _P]),
+    'd2d_rbascent_last_error': (C.c_char_p, []),
+}
+
 # the side libraries: name -> every symbol include/d2d_<name>.h declares; libd2d_<name>.so, its error text in d2d_<name>_last_error
 SIDE = {'plugin': PLUGIN_SIGNATURES, 'episode': EPISODE_SIGNATURES, 'sense': SENSE_SIGNATURES, 'graph': GRAPH_SIGNATURES,
         'marginal': MARGINAL_SIGNATURES, 'mobility': MOBILITY_SIGNATURES, 'channel': CHANNEL_SIGNATURES, 'queue': QUEUE_SIGNATURES,
@@ -334,8 +347,10 @@ FAMILIES = {'balance': BALANCE_SIGNATURES}
 EXTRAS = {'stable': STABLE_SIGNATURES}
 # build.EXACT's libraries, likewise: what joined behind the extras
 EXACT = {'share': SHARE_SIGNATURES}
-# build.GROWING's libraries, likewise: what joined behind the exact solvers, and the table the next library joins
+# build.GROWING's libraries, likewise: what joined behind the exact solvers
 GROWING = {'ascent': ASCENT_SIGNATURES}
+# build.LATER's libraries, likewise: what joined behind the power ascent, and the table the next library joins
+LATER = {'rbascent': RBASCENT_SIGNATURES}
 
 _lib: Optional[C.CDLL] = None
 _side: dict = {}                    # name -> the opened, typed side library
@@ -356,6 +371,7 @@ stable_launches = 0                 # d2d_stable_match launches made through sta
 share_values_launches = 0           # d2d_share_values launches made through share_values()
 share_solve_launches = 0            # d2d_share_solve launches made through share_solve()
 ascent_launches = 0                 # d2d_power_ascent launches made through power_ascent()
+rbascent_launches = 0               # d2d_rb_ascent launches made through rb_ascent()
 mobility_launches = 0               # d2d_mobility_move calls made through mobility_move()
 channel_launches = 0                # d2d_channel_fill calls made through channel_fill()
 queue_launches = 0                  # d2d_queue_step calls made through queue_step()
@@ -385,7 +401,7 @@ def side_path(name: str) -> Path:
 
 
 def side_library(name: str) -> C.CDLL:
-    """dlopen libd2d_<name>.so once and type the entry points SIDE[name] (or SOLVERS[name], ADDONS[name], FAMILIES[name], EXTRAS[name], EXACT[name], GROWING[name]) lists.  Raises if it has not been built."""
+    """dlopen libd2d_<name>.so once and type the entry points SIDE[name] (or SOLVERS[name], ADDONS[name], FAMILIES[name], EXTRAS[name], EXACT[name], GROWING[name], LATER[name]) lists.  Raises if it has not been built."""
     lib = _side.get(name)
     if lib is None:
         path = side_path(name)
@@ -393,7 +409,7 @@ def side_library(name: str) -> C.CDLL:
             raise ImportError(f'{path} is missing - build it with `python -m gym_d2d_amd.build`')
         lib = C.CDLL(str(path))
         for symbol, (res, args) in (SIDE.get(name) or SOLVERS.get(name) or ADDONS.get(name) or FAMILIES.get(name) or EXTRAS.get(name)
-                                    or EXACT.get(name) or GROWING[name]).items():
+                                    or EXACT.get(name) or GROWING.get(name) or LATER[name]).items():
             fn = getattr(lib, symbol)
             fn.restype = res
             fn.argtypes = args
@@ -427,6 +443,7 @@ def load_balance_library() -> C.CDLL: return side_library('balance')
 def load_stable_library() -> C.CDLL: return side_library('stable')
 def load_share_library() -> C.CDLL: return side_library('share')
 def load_ascent_library() -> C.CDLL: return side_library('ascent')
+def load_rbascent_library() -> C.CDLL: return side_library('rbascent')
 
 
 # Pointer arguments are passed as the ints they are: every argtype is c_void_p, which takes 0 as the null pointer and any int up to
@@ -691,6 +708,23 @@ def power_ascent(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, link
         capacity_ptr, rounds_ptr, moves_ptr, converged_ptr, stream_ptr))
     if n_envs:
         ascent_launches += 1
+
+
+def rb_ascent(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, link_tx_ptr: int, link_rx_ptr: int, cols_ptr: int,
+              cap_cols_ptr: int, law: int, pow_k: int, n_envs: int, n_dev: int, n_links: int, n_rbs: int, allowed_ptr: int, movable_ptr: int,
+              floor_ptr: int, min_gain_mbps: float, max_rounds: int, env_mask_ptr: int, rb_out_ptr: int, sinr_ptr: int, capacity_ptr: int,
+              rounds_ptr: int, moves_ptr: int, converged_ptr: int, stream_ptr: int = 0) -> None:
+    """d2d_rb_ascent: the sum-capacity RB ascent of every env in one launch - rb int32, sinr_db and capacity_mbps float32
+    [n_envs, n_links], rounds and moves int32, converged uint8 [n_envs] (device pointers; allowed_ptr 0: every RB, else uint32
+    [n_links, ceil(n_rbs / 32)]; movable_ptr 0: every link, else uint8 [n_links]; floor_ptr 0: no floors, else float32 [n_links],
+    -inf: none for that link; env_mask_ptr 0: every env, else uint8 [n_envs] and the envs whose byte is 0 keep their rows)."""
+    global rbascent_launches
+    _check_side('rbascent', load_rbascent_library().d2d_rb_ascent(
+        pos_x_ptr, pos_y_ptr, rb_ptr, pwr_ptr, link_tx_ptr, link_rx_ptr, cols_ptr, cap_cols_ptr, law, pow_k, n_envs, n_dev, n_links,
+        n_rbs, allowed_ptr, movable_ptr, floor_ptr, min_gain_mbps, max_rounds, env_mask_ptr, rb_out_ptr, sinr_ptr, capacity_ptr,
+        rounds_ptr, moves_ptr, converged_ptr, stream_ptr))
+    if n_envs:
+        rbascent_launches += 1
 
 
 def mobility_move(pos_x_ptr: int, pos_y_ptr: int, vel_x_ptr: int, vel_y_ptr: int, fixed_mask_ptr: int, n_envs: int, n_cues: int,

@@ -1,4 +1,4 @@
-"""Build every shared library of `LIBRARIES`, `SOLVERS`, `ADDONS`, `FAMILIES`, `EXTRAS`, `EXACT` and `GROWING` for gfx950 with hipcc - in-tree, so the .so files travel with the repo snapshot.
+"""Build every shared library of `LIBRARIES`, `SOLVERS`, `ADDONS`, `FAMILIES`, `EXTRAS`, `EXACT`, `GROWING` and `LATER` for gfx950 with hipcc - in-tree, so the .so files travel with the repo snapshot.
 
     stem      libd2d_<stem>.so                                        public header
     hip       the product: the C ABI                                  include/d2d_hip.h
@@ -11,6 +11,7 @@
     stable    the stable RB matching with quotas (4.20), listed in EXTRAS include/d2d_stable.h
     share     the exact optimal RB sharing (4.21), listed in EXACT        include/d2d_share.h
     ascent    the sum-capacity power ascent (4.22), listed in GROWING    include/d2d_ascent.h
+    rbascent  the sum-capacity RB ascent (4.23), listed in LATER         include/d2d_rbascent.h
 
     python -m gym_d2d_amd.build [--force] [--verbose]
     D2D_BUILD_DIAG=1 python -m gym_d2d_amd.build      # diagnostic build of libd2d_hip.so: the A/B tuning keys and the ablation
@@ -62,15 +63,21 @@ ALL = {**TARGETS, **EXTRAS}                      # TARGETS and the extras: fixed
 EXACT = {'share': ['d2d_share.hip']}
 WHOLE = {**ALL, **EXACT}                         # ALL and the exact solvers: fixed with them, as the tables above are
 # the libraries that joined behind WHOLE (which _native.GROWING mirrors): compiled and linked last, stamped with the rest, and a
-# missing one is rebuilt (growing_missing()).  This is the table the next library joins: nothing states its length.
+# missing one is rebuilt (growing_missing()).  Its one row is fixed, as the tables above are (tests/test_ascent_cpu.py states
+# it): what joins the build now joins LATER below.
 # ascent: the sum-capacity power ascent with SINR floors
 GROWING = {'ascent': ['d2d_ascent.hip']}
-EVERY = {**WHOLE, **GROWING}                     # every library of the build: what the digest, the compile and the link iterate
+EVERY = {**WHOLE, **GROWING}                     # WHOLE and what joined behind it: fixed with them, as the tables above are
+# the libraries that joined behind EVERY (which _native.LATER mirrors): compiled and linked last, stamped with the rest, and a
+# missing one is rebuilt (later_missing()).  The next library joins this table: nothing states its length.
+# rbascent: the sum-capacity RB ascent with SINR floors
+LATER = {'rbascent': ['d2d_rbascent.hip']}
+COMPLETE = {**EVERY, **LATER}                    # every library of the build: what the digest, the compile and the link iterate
 HEADERS = [CSRC / 'd2d_internal.h', CSRC / 'd2d_plan.h', CSRC / 'd2d_step_device.h', CSRC / 'd2d_store.h', CSRC / 'd2d_same_rb.h', CSRC / 'd2d_addon.h',
            CSRC / 'd2d_powerctl_device.h', CSRC / 'd2d_wave_key.h', INCLUDE / 'd2d_hip.h', INCLUDE / 'd2d_hip_diag.h',
            *(INCLUDE / f'd2d_{stem}.h' for stem in TARGETS if stem not in ('hip', 'probe')),
            *(INCLUDE / f'd2d_{stem}.h' for stem in EXTRAS), *(INCLUDE / f'd2d_{stem}.h' for stem in EXACT),
-           *(INCLUDE / f'd2d_{stem}.h' for stem in GROWING)]
+           *(INCLUDE / f'd2d_{stem}.h' for stem in GROWING), *(INCLUDE / f'd2d_{stem}.h' for stem in LATER)]
 
 
 def lib_path(stem: str, lib_dir: Path = LIB_DIR) -> Path:
@@ -107,7 +114,7 @@ def _hipcc() -> str:
 
 def digest_files() -> list:
     """The files source_digest() hashes, in order: every library's sources, then the headers."""
-    return [p for p in [CSRC / s for sources in EVERY.values() for s in sources] + HEADERS if p.exists()]
+    return [p for p in [CSRC / s for sources in COMPLETE.values() for s in sources] + HEADERS if p.exists()]
 
 
 def source_digest() -> str:
@@ -165,17 +172,22 @@ def growing_missing(lib_dir: Path = LIB_DIR) -> list:
     return [stem for stem in GROWING if not lib_path(stem, lib_dir).exists()]
 
 
+def later_missing(lib_dir: Path = LIB_DIR) -> list:
+    """The stems of LATER whose library is not there, in the table's order: a missing one is rebuilt."""
+    return [stem for stem in LATER if not lib_path(stem, lib_dir).exists()]
+
+
 def build(force: bool = False, verbose: bool = False) -> Path:
     LIB_DIR.mkdir(exist_ok=True)
     digest = source_digest()
     if not force and up_to_date(digest) and solvers_built() and addons_built() and not addons_missing() and not families_missing() \
-            and not extras_missing() and not exact_missing() and not growing_missing():
+            and not extras_missing() and not exact_missing() and not growing_missing() and not later_missing():
         return LIB_PATH
     hipcc = _hipcc()
     obj_dir = LIB_DIR / 'obj'
     obj_dir.mkdir(exist_ok=True)
     procs = []
-    for s in [s for sources in EVERY.values() for s in sources]:
+    for s in [s for sources in COMPLETE.values() for s in sources]:
         src = CSRC / s
         obj = obj_dir / (src.stem + '.o')
         cmd = [hipcc, *flags_for(s), '-I', str(INCLUDE), '-c', str(src), '-o', str(obj)]
@@ -188,7 +200,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
             raise RuntimeError(f'hipcc failed on {s}:\n{out}')
         if verbose and out.strip():
             print(out)
-    for stem, sources in EVERY.items():
+    for stem, sources in COMPLETE.items():
         objs = [str(obj_dir / (Path(s).stem + '.o')) for s in sources]
         cmd = [hipcc, '-shared', '-fPIC', f'--offload-arch={ARCH}', '-o', str(lib_path(stem)), *objs]
         if verbose:

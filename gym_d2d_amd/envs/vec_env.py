@@ -22,7 +22,7 @@ from typing import Optional
 
 import numpy as np
 
-from .. import _native, assignment, balance, best_response, best_response_dynamics, coloring, graph, joint_assignment, marginal, power_ascent, power_control, sensing, sharing, stable_matching
+from .. import _native, assignment, balance, best_response, best_response_dynamics, coloring, graph, joint_assignment, marginal, power_ascent, power_control, rb_ascent, sensing, sharing, stable_matching
 from .. import evaluate as evaluate_mod
 from .. import mobility as mobility_mod
 from .. import queues as queues_mod
@@ -292,6 +292,8 @@ class VecD2DEnv:
         self._share = None
         # sum-capacity power ascent with SINR floors (power_ascent()): likewise
         self._ascent = None
+        # sum-capacity RB ascent with SINR floors (rb_ascent()): likewise
+        self._rbascent = None
 
     def _setup_autoreset(self) -> None:
         """Refuse what a device-side per-env reset cannot serve, then allocate the per-env bookkeeping: pending / episode are bound
@@ -1017,6 +1019,68 @@ class VecD2DEnv:
         first, p_min, levels = self._agent_power_levels()
         return power_control.encode_actions(self._t['rb'], power, p_min, levels, first)
 
+    # ------------------------------------------------------------------ sum-capacity RB ascent
+    def _rb_ascent_kernel(self):
+        return self._kernel('_rbascent', rb_ascent, rb_ascent.RbAscent, lambda: (self._agent_links(),))
+
+    def rb_ascent(self, allowed=None, movable=None, floor_sinr_db=None, min_gain_mbps: float = 0.0, max_rounds: int = 16, out=None,
+                  env_mask=None):
+        """The RBs a cooperative local search on the total capacity ends at - a link moves to the RB where the TOTAL capacity gains
+        most - with the protected links kept above their SINR floors and positions and powers as the last step left them: (rb int32
+        [B, N], sinr_db float32 [B, N], capacity_mbps float32 [B, N], rounds int32 [B], moves int32 [B], converged uint8 [B]), a
+        tuple with those names.  Only rb changes.
+
+        A link is on an RB iff 0 <= rb < R; the group of RB r is the set of links on r in ascending link index.  A link is movable
+        iff it is on an RB, `movable` marks it (None: the agent links; links on cue_actions='traffic' never move) and it has at
+        least one allowed RB.
+
+        A turn of the movable link i, currently on RB c, at the current assignment rb.  For an RB r let rb^r be rb with rb[i] = r,
+        and sinr^r_m, cap^r_m the float32 values evaluate() gives link m for (rb^r, pwr), bit for bit.  Groups do not interact: for
+        r != c, cap^c_m of a member of r is its value "without i", and cap^r_m of a member of c is its value "with i gone".  With(r)
+        is the sum, in double, in ascending link index, of cap^r_m over group(r) and i; Without(r) is the same sum over group(r)
+        less i with i not on r (for r != c of cap^c_m, for r == c of cap^r'_m for any r' != c; an empty sum is 0.0).  D(r) =
+        With(r) - Without(r), one double subtraction, is what link i's presence on r is worth to the total.  r is a candidate iff
+        r != c, allowed[i][r] and r is admissible; r is admissible iff every m of group(r) and i with a floor above -inf has
+        sinr^r_m >= floor[m] or sinr^c_m < floor[m] (float32 comparisons, NaN compares false): a link already under its floor
+        constrains nothing, a link that meets its floor is never pushed under it - the rule of power_ascent() and
+        assign_rbs_power() - and leaving c constrains nothing.  best is the lowest candidate r whose D(r) is maximal among the
+        candidates (a NaN D is never chosen), and link i moves to best, at once, iff D(best) - D(c) > min_gain_mbps (a double
+        subtraction and comparison; a NaN does not move).
+
+        The movable links take turns in ascending link index, each seeing the moves made before its turn.  A round that moves
+        nobody ends the ascent (converged 1, rounds = the rounds that moved a link); so do max_rounds rounds that each moved a link
+        (converged 0, rounds == max_rounds).  Termination is a property: rounding is monotone, so a move implies With(best) -
+        Without(best) > With(c) - Without(c) in exact arithmetic over the double group sums; each group sum is a pure function of
+        the group's membership, so the exact sum of the group totals strictly rises on every move and no assignment repeats.
+        max_rounds only bounds the launch.  sinr_db and capacity_mbps are evaluate(rb, pwr)'s planes for every link, a link on no
+        RB included.  All turns of an env run in one workgroup of ONE kernel launch (csrc/d2d_rbascent.hip) out of LDS: lanes own
+        RBs, membership is a bitset.  A lane with a long group does G^2 pair evaluations while the others wait: that is the known
+        limit.  With one RB nobody has a candidate: moves 0, converged 1.  Alternate with power_ascent() to move RBs and powers in
+        turn.  Valid after reset() and after every step(), autoreset steps included, as best_response_dynamics() is.
+
+        allowed: bool [N, R] (tensor or array) as best_rb() takes it; None: every RB.  movable: bool [N]; None: every agent link.
+        floor_sinr_db: None (no floors), a number, {'cue': x, 'due': y} or [N] values (array or tensor), dB; -inf: no floor for
+        that link.  min_gain_mbps: finite, >= 0.  max_rounds: 1 .. 4096.  env_mask: bool / uint8 [B], envs whose entry is 0 keep
+        their rows; None: all.
+
+        Torch path only: enqueued on torch's current stream, nothing is synchronised; the six tensors the env owns, rewritten by
+        every call (clone them to keep them), or `out` = (rb, sinr_db, capacity_mbps, rounds, moves, converged), contiguous int32 /
+        float32 / float32 [B, N], int32 / int32 / uint8 [B] on the env's device.  Serves what power_ascent() serves, as far as an
+        env's links, allowed words and RB membership fit the LDS of one workgroup; ValueError for export_actions=False,
+        ShadowingPathLoss, every table route, pinned device_config coordinates float32 cannot hold."""
+        k = self._rb_ascent_kernel()
+        mov, floor = k.movable(movable), k.floor(floor_sinr_db, self.num_cues)
+        self._follow_torch_stream()
+        return k.solve(self._t, allowed, mov, floor, min_gain_mbps, max_rounds, out, self._stream_ptr, env_mask)
+
+    def rb_ascent_actions(self, allowed=None, movable=None, floor_sinr_db=None, min_gain_mbps: float = 0.0, max_rounds: int = 16):
+        """rb_ascent() as an action tensor, int32 [B, num_agents], ready for step(): every agent link on its solved RB at its
+        current power level (as the decoded planes hold it), encoded rb * power levels + level
+        (best_response_dynamics.encode_actions).  Links on fixed actions (cue_actions='traffic') have no column.  Composes with
+        power_ascent_actions(): one call picks RBs, the other picks powers."""
+        rb = self.rb_ascent(allowed, movable, floor_sinr_db, min_gain_mbps, max_rounds)[0]
+        return best_response_dynamics.encode_actions(rb, self._t['pwr'], self._agent_levels(), self.num_links - self.num_agents)
+
     # ------------------------------------------------------------------ sequential best-response dynamics
     def _best_response_dynamics_kernel(self):
         return self._kernel('_brdyn', best_response_dynamics, best_response_dynamics.BestResponseDynamics,
@@ -1511,4 +1575,7 @@ class VecD2DEnv:
         if self._ascent is not None:
             self._ascent.close()
             self._ascent = None
+        if self._rbascent is not None:
+            self._rbascent.close()
+            self._rbascent = None
         self.simulator.handle.close()
