@@ -120,6 +120,16 @@ RBASCENT_MAX_LINKS = 2048
 RBASCENT_MAX_RBS = 8192
 RBASCENT_MAX_ROUNDS = 4096
 RBASCENT_MAX_LDS_BYTES = 163840
+# d2d_goodput_ascent's law / move bits / limits (include/d2d_goodput.h): d2d_rb_ascent's, the levels of a link's power alphabet and
+# the largest weight
+GOODPUT_LAW_INV_SQUARE, GOODPUT_LAW_POWER, GOODPUT_LAW_POW_K = 0, 1, 2
+GOODPUT_MOVE_RB, GOODPUT_MOVE_POWER = 1, 2
+GOODPUT_MAX_LINKS = 2048
+GOODPUT_MAX_RBS = 8192
+GOODPUT_MAX_LEVELS = 64
+GOODPUT_MAX_ROUNDS = 4096
+GOODPUT_MAX_WEIGHT = 1 << 20
+GOODPUT_MAX_LDS_BYTES = 163840
 
 BUFFER_DTYPES = {BUF_ACTIONS: np.int32, BUF_RB: np.int32, BUF_PWR: np.int32, BUF_ENV_FLAGS: np.int32, BUF_RESET_PENDING: np.int32,
                  BUF_EPISODE: np.uint32}
@@ -333,6 +343,13 @@ RBASCENT_SIGNATURES = {
     'd2d_rbascent_last_error': (C.c_char_p, []),
 }
 
+# every symbol include/d2d_goodput.h declares
+GOODPUT_SIGNATURES = {
+    'd2d_goodput_ascent': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, C.c_int64, _I, _I, _I, _P, _P, _P, _P, C.c_double, _P, _P, _P, _I,
+                                     C.c_int64, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'd2d_goodput_last_error': (C.c_char_p, []),
+}
+
 # the side libraries: name -> every symbol include/d2d_<name>.h declares; libd2d_<name>.so, its error text in d2d_<name>_last_error
 SIDE = {'plugin': PLUGIN_SIGNATURES, 'episode': EPISODE_SIGNATURES, 'sense': SENSE_SIGNATURES, 'graph': GRAPH_SIGNATURES,
         'marginal': MARGINAL_SIGNATURES, 'mobility': MOBILITY_SIGNATURES, 'channel': CHANNEL_SIGNATURES, 'queue': QUEUE_SIGNATURES,
@@ -350,7 +367,7 @@ EXACT = {'share': SHARE_SIGNATURES}
 # build.GROWING's libraries, likewise: what joined behind the exact solvers
 GROWING = {'ascent': ASCENT_SIGNATURES}
 # build.LATER's libraries, likewise: what joined behind the power ascent, and the table the next library joins
-LATER = {'rbascent': RBASCENT_SIGNATURES}
+LATER = {'rbascent': RBASCENT_SIGNATURES, 'goodput': GOODPUT_SIGNATURES}
 
 _lib: Optional[C.CDLL] = None
 _side: dict = {}                    # name -> the opened, typed side library
@@ -372,6 +389,7 @@ share_values_launches = 0           # d2d_share_values launches made through sha
 share_solve_launches = 0            # d2d_share_solve launches made through share_solve()
 ascent_launches = 0                 # d2d_power_ascent launches made through power_ascent()
 rbascent_launches = 0               # d2d_rb_ascent launches made through rb_ascent()
+goodput_launches = 0                # d2d_goodput_ascent launches made through goodput_ascent()
 mobility_launches = 0               # d2d_mobility_move calls made through mobility_move()
 channel_launches = 0                # d2d_channel_fill calls made through channel_fill()
 queue_launches = 0                  # d2d_queue_step calls made through queue_step()
@@ -444,6 +462,7 @@ def load_stable_library() -> C.CDLL: return side_library('stable')
 def load_share_library() -> C.CDLL: return side_library('share')
 def load_ascent_library() -> C.CDLL: return side_library('ascent')
 def load_rbascent_library() -> C.CDLL: return side_library('rbascent')
+def load_goodput_library() -> C.CDLL: return side_library('goodput')
 
 
 # Pointer arguments are passed as the ints they are: every argtype is c_void_p, which takes 0 as the null pointer and any int up to
@@ -725,6 +744,28 @@ def rb_ascent(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, link_tx
         rounds_ptr, moves_ptr, converged_ptr, stream_ptr))
     if n_envs:
         rbascent_launches += 1
+
+
+def goodput_ascent(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, link_tx_ptr: int, link_rx_ptr: int, cols_ptr: int,
+                   cap_cols_ptr: int, law: int, pow_k: int, n_envs: int, n_dev: int, n_links: int, n_rbs: int, p_min_ptr: int, p_max_ptr: int,
+                   weight_ptr: int, demand_ptr: int, bits_per_mbps: float, allowed_ptr: int, movable_ptr: int, floor_ptr: int,
+                   move_mask: int, min_gain: int, max_rounds: int, env_mask_ptr: int, rb_out_ptr: int, power_ptr: int, sinr_ptr: int,
+                   capacity_ptr: int, served_ptr: int, value_ptr: int, rounds_ptr: int, moves_ptr: int, converged_ptr: int,
+                   stream_ptr: int = 0) -> None:
+    """d2d_goodput_ascent: the queue-aware goodput ascent of every env in one launch - rb and power_dbm int32, sinr_db and
+    capacity_mbps float32, served_bits int32 [n_envs, n_links], value int64, rounds and moves int32, converged uint8 [n_envs]
+    (device pointers; p_min / p_max int32 [n_links]; weight_ptr 0: 1, else uint32 [n_envs, n_links] in [0, 2^20]; demand_ptr 0:
+    uncapped, else int32 [n_envs, n_links]; allowed_ptr 0: every RB, else uint32 [n_links, ceil(n_rbs / 32)]; movable_ptr 0: every
+    link, else uint8 [n_links]; floor_ptr 0: no floors, else float32 [n_links], -inf: none for that link; move_mask: GOODPUT_MOVE_RB |
+    GOODPUT_MOVE_POWER; env_mask_ptr 0: every env, else uint8 [n_envs] and the envs whose byte is 0 keep their rows)."""
+    global goodput_launches
+    _check_side('goodput', load_goodput_library().d2d_goodput_ascent(
+        pos_x_ptr, pos_y_ptr, rb_ptr, pwr_ptr, link_tx_ptr, link_rx_ptr, cols_ptr, cap_cols_ptr, law, pow_k, n_envs, n_dev, n_links,
+        n_rbs, p_min_ptr, p_max_ptr, weight_ptr, demand_ptr, bits_per_mbps, allowed_ptr, movable_ptr, floor_ptr, move_mask, min_gain,
+        max_rounds, env_mask_ptr, rb_out_ptr, power_ptr, sinr_ptr, capacity_ptr, served_ptr, value_ptr, rounds_ptr, moves_ptr,
+        converged_ptr, stream_ptr))
+    if n_envs:
+        goodput_launches += 1
 
 
 def mobility_move(pos_x_ptr: int, pos_y_ptr: int, vel_x_ptr: int, vel_y_ptr: int, fixed_mask_ptr: int, n_envs: int, n_cues: int,

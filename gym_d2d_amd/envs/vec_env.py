@@ -22,7 +22,7 @@ from typing import Optional
 
 import numpy as np
 
-from .. import _native, assignment, balance, best_response, best_response_dynamics, coloring, graph, joint_assignment, marginal, power_ascent, power_control, rb_ascent, sensing, sharing, stable_matching
+from .. import _native, assignment, balance, best_response, best_response_dynamics, coloring, goodput_ascent, graph, joint_assignment, marginal, power_ascent, power_control, rb_ascent, sensing, sharing, stable_matching
 from .. import evaluate as evaluate_mod
 from .. import mobility as mobility_mod
 from .. import queues as queues_mod
@@ -294,6 +294,8 @@ class VecD2DEnv:
         self._ascent = None
         # sum-capacity RB ascent with SINR floors (rb_ascent()): likewise
         self._rbascent = None
+        # queue-aware goodput ascent over RBs and powers (goodput_ascent()): likewise
+        self._goodput = None
 
     def _setup_autoreset(self) -> None:
         """Refuse what a device-side per-env reset cannot serve, then allocate the per-env bookkeeping: pending / episode are bound
@@ -1081,6 +1083,89 @@ class VecD2DEnv:
         rb = self.rb_ascent(allowed, movable, floor_sinr_db, min_gain_mbps, max_rounds)[0]
         return best_response_dynamics.encode_actions(rb, self._t['pwr'], self._agent_levels(), self.num_links - self.num_agents)
 
+    # ------------------------------------------------------------------ queue-aware goodput ascent
+    def _goodput_ascent_kernel(self):
+        return self._kernel('_goodput', goodput_ascent, goodput_ascent.GoodputAscent, lambda: (*self._class_bounds(), self._agent_links()))
+
+    def goodput_ascent(self, demand_bits=None, weight=None, bits_per_mbps=None, move=('rb', 'power'), allowed=None, movable=None,
+                       floor_sinr_db=None, min_gain_bits: int = 0, max_rounds: int = 16, out=None, env_mask=None):
+        """The RBs and powers a local search on the weighted bits the links can DELIVER ends at - the baseline of
+        GoodputRewardFunction, and with backlog weights the max-weight scheduler - with the protected links kept above their SINR
+        floors and positions as the last step left them: (rb int32 [B, N], power_dbm int32 [B, N], sinr_db float32 [B, N],
+        capacity_mbps float32 [B, N], served_bits int32 [B, N], value int64 [B], rounds int32 [B], moves int32 [B], converged uint8
+        [B]), a tuple with those names.  Every decision compares integers: no float ordering enters any choice.
+
+        For a state s = (rb, pwr): cap_m(s) and sinr_m(s) are the float32 values evaluate() gives link m, bit for bit.  budget(c) is
+        the packet queues' rule (include/d2d_queue.h, rule 5): floor(double(c) * bits_per_mbps) clipped to [0, 2^31 - 1]; a NaN,
+        negative or zero capacity gives 0, +inf gives 2^31 - 1.  served_m(s) = min(budget(cap_m(s)), demand_m), term_m(s) =
+        int64(weight_m) * served_m(s), and V(s) is the sum of term_m(s) over ALL links - those that never move and those on no RB
+        included.  V stays below 2^62, so int64 sums are exact and order-free.
+
+        A link takes turns iff it is on an RB (0 <= rb < R), `movable` marks it (None: the agent links; links on
+        cue_actions='traffic' never move) and, with move=('rb',) only, it has an allowed RB.  A turn of link i, on RB c at power p,
+        works on the candidate states s' that differ from s in link i alone: with 'rb' in move, (r, p) for every r != c with
+        allowed[i][r]; with 'power' in move, (c, q) for every level q != p of the link's class.  A turn changes the RB or the
+        power, never both.  Delta(s') = V(s') - V(s); only the members of c's group, of r's group and link i contribute.  s' is
+        admissible iff every such member m with a floor above -inf has sinr_m(s') >= floor[m] or sinr_m(s) < floor[m] (float32
+        comparisons, NaN compares false) - the rule of power_ascent() and rb_ascent(), for both kinds of candidate.  best is the
+        admissible candidate of maximal Delta, ties to the lowest power, then to the lowest RB, and link i moves to best, at once,
+        iff Delta(best) > min_gain_bits.
+
+        The links take turns in ascending link index, each seeing the moves made before its turn.  A round that moves nobody ends
+        the ascent (converged 1, rounds = the rounds that moved a link); so do max_rounds rounds that each moved a link (converged
+        0, rounds == max_rounds).  Every move raises the integer V by at least 1 and V is bounded, so no state repeats: max_rounds
+        only bounds the launch.  sinr_db and capacity_mbps are evaluate(rb, power_dbm)'s planes for every link; value is V of the
+        final state.  All turns of an env run in one workgroup of ONE kernel launch (csrc/d2d_goodput.hip) out of LDS: the
+        candidates of a turn are one flat list dealt over the threads, RBs first, then levels.  A thread with a long group does G^2
+        pair evaluations while the others wait: that is the known limit.  Valid after reset() and after every step(), autoreset
+        steps included, as rb_ascent() is.
+
+        demand_bits, weight: ints - a scalar, [N] or [B, N] values (array or tensor), broadcast.  demand_bits None: on an env with
+        traffic= the live backlog_bits plane of queues(), as it is when the launch runs; a negative value counts as 0.  weight
+        None: 1; values in [0, 2^20] (host values are checked; a tensor is not read on the host, and the kernel takes a larger
+        word as 2^20).  bits_per_mbps None: traffic.bits_per_mbps_step.  On an env without traffic= both demand_bits and
+        bits_per_mbps must be given.  move: 'rb', 'power' or both.  allowed: bool [N, R] as best_rb() takes it; None: every RB.
+        movable: bool [N]; None: every agent link.  floor_sinr_db: None (no floors), a number, {'cue': x, 'due': y} or [N]
+        values, dB; -inf: no floor for that link.  min_gain_bits: an int in [0, 2^62), in weighted bits.  max_rounds: 1 .. 4096.
+        The power bounds are the ones step() decodes; a class of more than 64 power levels is refused.  env_mask: bool / uint8
+        [B], envs whose entry is 0 keep their rows; None: all.
+
+        Recipes.  The goodput baseline: the defaults on a traffic env - weight 1, demand the backlog.  Classic max-weight
+        scheduling: weight = backlog_bits >> k, scaled into [0, 2^20], with demand_bits = 2^31 - 1 (uncapped).
+
+        Two limits.  The prediction uses the backlog as it is now: bits that arrive or expire before the next service are not in
+        it.  A link with nothing to send still transmits, because the step has no off state: "muting" a link means its lowest
+        power level, which is where ties send it.
+
+        Torch path only: enqueued on torch's current stream, nothing is synchronised; the nine tensors the env owns, rewritten by
+        every call (clone them to keep them), or `out` = (rb, power_dbm, sinr_db, capacity_mbps, served_bits, value, rounds, moves,
+        converged), contiguous int32 / int32 / float32 / float32 / int32 [B, N], int64 / int32 / int32 / uint8 [B] on the env's
+        device.  Serves what rb_ascent() serves, as far as an env fits the LDS of one workgroup (96 bytes per link and the RB
+        membership); ValueError for export_actions=False, ShadowingPathLoss, every table route, pinned device_config coordinates
+        float32 cannot hold."""
+        k = self._goodput_ascent_kernel()
+        if self._queues is None and (demand_bits is None or bits_per_mbps is None):
+            raise ValueError('goodput_ascent() on an env without traffic= needs demand_bits and bits_per_mbps: there is no backlog '
+                             'plane and no step length to take them from')
+        if demand_bits is None:
+            demand_bits = self._queues.backlog_bits
+        if bits_per_mbps is None:
+            bits_per_mbps = self._t['traffic'].bits_per_mbps_step
+        mov, floor = k.movable(movable), k.floor(floor_sinr_db, self.num_cues)
+        self._follow_torch_stream()
+        return k.solve(self._t, demand_bits, weight, bits_per_mbps, move, allowed, mov, floor, min_gain_bits, max_rounds, out,
+                       self._stream_ptr, env_mask)
+
+    def goodput_ascent_actions(self, demand_bits=None, weight=None, bits_per_mbps=None, move=('rb', 'power'), allowed=None, movable=None,
+                               floor_sinr_db=None, min_gain_bits: int = 0, max_rounds: int = 16):
+        """goodput_ascent() as an action tensor, int32 [B, num_agents], ready for step(): every agent link on its solved RB at its
+        solved power, encoded rb * power levels + level (power_control.encode_actions, the encoder of power_ascent_actions(), on
+        the solved RBs where rb_ascent_actions() puts them).  Links on fixed actions (cue_actions='traffic') have no column.  One
+        call picks RBs and powers: no alternation of rb_ascent_actions() and power_ascent_actions() through step()."""
+        res = self.goodput_ascent(demand_bits, weight, bits_per_mbps, move, allowed, movable, floor_sinr_db, min_gain_bits, max_rounds)
+        first, p_min, levels = self._agent_power_levels()
+        return power_control.encode_actions(res[0], res[1], p_min, levels, first)
+
     # ------------------------------------------------------------------ sequential best-response dynamics
     def _best_response_dynamics_kernel(self):
         return self._kernel('_brdyn', best_response_dynamics, best_response_dynamics.BestResponseDynamics,
@@ -1578,4 +1663,7 @@ class VecD2DEnv:
         if self._rbascent is not None:
             self._rbascent.close()
             self._rbascent = None
+        if self._goodput is not None:
+            self._goodput.close()
+            self._goodput = None
         self.simulator.handle.close()
