@@ -130,6 +130,13 @@ GOODPUT_MAX_LEVELS = 64
 GOODPUT_MAX_ROUNDS = 4096
 GOODPUT_MAX_WEIGHT = 1 << 20
 GOODPUT_MAX_LDS_BYTES = 163840
+# d2d_deviation_gains' / d2d_best_deviation's law / limits (include/d2d_deviate.h): d2d_goodput_ascent's, and the bytes of one table
+DEVIATE_LAW_INV_SQUARE, DEVIATE_LAW_POWER, DEVIATE_LAW_POW_K = 0, 1, 2
+DEVIATE_MAX_LINKS = 2048
+DEVIATE_MAX_RBS = 8192
+DEVIATE_MAX_LEVELS = 64
+DEVIATE_MAX_LDS_BYTES = 163840
+DEVIATE_MAX_TABLE_BYTES = 8 << 30
 
 BUFFER_DTYPES = {BUF_ACTIONS: np.int32, BUF_RB: np.int32, BUF_PWR: np.int32, BUF_ENV_FLAGS: np.int32, BUF_RESET_PENDING: np.int32,
                  BUF_EPISODE: np.uint32}
@@ -350,6 +357,14 @@ GOODPUT_SIGNATURES = {
     'd2d_goodput_last_error': (C.c_char_p, []),
 }
 
+# every symbol include/d2d_deviate.h declares
+DEVIATE_SIGNATURES = {
+    'd2d_deviation_gains': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, C.c_int64, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    'd2d_best_deviation': (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, C.c_int64, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, C.c_double, _P,
+                                     _P, _P, _P, _P, _P, _P]),
+    'd2d_deviate_last_error': (C.c_char_p, []),
+}
+
 # the side libraries: name -> every symbol include/d2d_<name>.h declares; libd2d_<name>.so, its error text in d2d_<name>_last_error
 SIDE = {'plugin': PLUGIN_SIGNATURES, 'episode': EPISODE_SIGNATURES, 'sense': SENSE_SIGNATURES, 'graph': GRAPH_SIGNATURES,
         'marginal': MARGINAL_SIGNATURES, 'mobility': MOBILITY_SIGNATURES, 'channel': CHANNEL_SIGNATURES, 'queue': QUEUE_SIGNATURES,
@@ -367,7 +382,7 @@ EXACT = {'share': SHARE_SIGNATURES}
 # build.GROWING's libraries, likewise: what joined behind the exact solvers
 GROWING = {'ascent': ASCENT_SIGNATURES}
 # build.LATER's libraries, likewise: what joined behind the power ascent, and the table the next library joins
-LATER = {'rbascent': RBASCENT_SIGNATURES, 'goodput': GOODPUT_SIGNATURES}
+LATER = {'rbascent': RBASCENT_SIGNATURES, 'deviate': DEVIATE_SIGNATURES, 'goodput': GOODPUT_SIGNATURES}
 
 _lib: Optional[C.CDLL] = None
 _side: dict = {}                    # name -> the opened, typed side library
@@ -390,6 +405,7 @@ share_solve_launches = 0            # d2d_share_solve launches made through shar
 ascent_launches = 0                 # d2d_power_ascent launches made through power_ascent()
 rbascent_launches = 0               # d2d_rb_ascent launches made through rb_ascent()
 goodput_launches = 0                # d2d_goodput_ascent launches made through goodput_ascent()
+deviate_launches = 0                # d2d_deviation_gains / d2d_best_deviation calls made through deviation_gains() / best_deviation()
 mobility_launches = 0               # d2d_mobility_move calls made through mobility_move()
 channel_launches = 0                # d2d_channel_fill calls made through channel_fill()
 queue_launches = 0                  # d2d_queue_step calls made through queue_step()
@@ -463,6 +479,7 @@ def load_share_library() -> C.CDLL: return side_library('share')
 def load_ascent_library() -> C.CDLL: return side_library('ascent')
 def load_rbascent_library() -> C.CDLL: return side_library('rbascent')
 def load_goodput_library() -> C.CDLL: return side_library('goodput')
+def load_deviate_library() -> C.CDLL: return side_library('deviate')
 
 
 # Pointer arguments are passed as the ints they are: every argtype is c_void_p, which takes 0 as the null pointer and any int up to
@@ -766,6 +783,39 @@ def goodput_ascent(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, li
         converged_ptr, stream_ptr))
     if n_envs:
         goodput_launches += 1
+
+
+def deviation_gains(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, link_tx_ptr: int, link_rx_ptr: int, cols_ptr: int,
+                    cap_cols_ptr: int, law: int, pow_k: int, n_envs: int, n_dev: int, n_links: int, n_rbs: int, p_min_ptr: int, p_max_ptr: int,
+                    links_ptr: int, n_sel: int, n_levels: int, allowed_ptr: int, floor_ptr: int, env_mask_ptr: int, gain_ptr: int,
+                    stream_ptr: int = 0) -> None:
+    """d2d_deviation_gains: what the total capacity gains when one selected link alone plays (RB, level), every entry of float32
+    [n_envs, n_sel, n_rbs, n_levels] in one launch, -inf where the entry is closed (device pointers; p_min / p_max int32 [n_links];
+    links int32 [n_sel], ascending and distinct; allowed_ptr 0: every RB, else uint32 [n_links, ceil(n_rbs / 32)]; floor_ptr 0: no
+    floors, else float32 [n_links], -inf: none for that link; env_mask_ptr 0: every env, else uint8 [n_envs] and the envs whose byte
+    is 0 keep their rows)."""
+    global deviate_launches
+    _check_side('deviate', load_deviate_library().d2d_deviation_gains(
+        pos_x_ptr, pos_y_ptr, rb_ptr, pwr_ptr, link_tx_ptr, link_rx_ptr, cols_ptr, cap_cols_ptr, law, pow_k, n_envs, n_dev, n_links,
+        n_rbs, p_min_ptr, p_max_ptr, links_ptr, n_sel, n_levels, allowed_ptr, floor_ptr, env_mask_ptr, gain_ptr, stream_ptr))
+    if n_envs:
+        deviate_launches += 1
+
+
+def best_deviation(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, link_tx_ptr: int, link_rx_ptr: int, cols_ptr: int,
+                   cap_cols_ptr: int, law: int, pow_k: int, n_envs: int, n_dev: int, n_links: int, n_rbs: int, p_min_ptr: int, p_max_ptr: int,
+                   links_ptr: int, n_sel: int, n_levels: int, allowed_ptr: int, floor_ptr: int, min_gain_mbps: float, env_mask_ptr: int,
+                   rb_out_ptr: int, pwr_out_ptr: int, gain_link_ptr: int, regret_ptr: int, leader_ptr: int, stream_ptr: int = 0) -> None:
+    """d2d_best_deviation: every selected link's best unilateral deviation and the env's regret, no table - rb and power_dbm int32,
+    gain_mbps float64 [n_envs, n_links], regret_mbps float64 and leader int32 [n_envs] (device pointers; the inputs as
+    deviation_gains() takes them)."""
+    global deviate_launches
+    _check_side('deviate', load_deviate_library().d2d_best_deviation(
+        pos_x_ptr, pos_y_ptr, rb_ptr, pwr_ptr, link_tx_ptr, link_rx_ptr, cols_ptr, cap_cols_ptr, law, pow_k, n_envs, n_dev, n_links,
+        n_rbs, p_min_ptr, p_max_ptr, links_ptr, n_sel, n_levels, allowed_ptr, floor_ptr, min_gain_mbps, env_mask_ptr, rb_out_ptr,
+        pwr_out_ptr, gain_link_ptr, regret_ptr, leader_ptr, stream_ptr))
+    if n_envs:
+        deviate_launches += 1
 
 
 def mobility_move(pos_x_ptr: int, pos_y_ptr: int, vel_x_ptr: int, vel_y_ptr: int, fixed_mask_ptr: int, n_envs: int, n_cues: int,

@@ -22,7 +22,7 @@ from typing import Optional
 
 import numpy as np
 
-from .. import _native, assignment, balance, best_response, best_response_dynamics, coloring, goodput_ascent, graph, joint_assignment, marginal, power_ascent, power_control, rb_ascent, sensing, sharing, stable_matching
+from .. import _native, assignment, balance, best_response, best_response_dynamics, coloring, deviation, goodput_ascent, graph, joint_assignment, marginal, power_ascent, power_control, rb_ascent, sensing, sharing, stable_matching
 from .. import evaluate as evaluate_mod
 from .. import mobility as mobility_mod
 from .. import queues as queues_mod
@@ -296,6 +296,8 @@ class VecD2DEnv:
         self._rbascent = None
         # queue-aware goodput ascent over RBs and powers (goodput_ascent()): likewise
         self._goodput = None
+        # unilateral-deviation gains over every (RB, power) action (deviation_gains(), best_deviation()): likewise
+        self._deviation = None
 
     def _setup_autoreset(self) -> None:
         """Refuse what a device-side per-env reset cannot serve, then allocate the per-env bookkeeping: pending / episode are bound
@@ -1166,6 +1168,95 @@ class VecD2DEnv:
         first, p_min, levels = self._agent_power_levels()
         return power_control.encode_actions(res[0], res[1], p_min, levels, first)
 
+    # ------------------------------------------------------------------ unilateral-deviation gains
+    def _deviation_kernel(self):
+        return self._kernel('_deviation', deviation, deviation.Deviation, lambda: (*self._class_bounds(), self._agent_links()))
+
+    def deviation_gains(self, links=None, allowed=None, floor_sinr_db=None, out=None, env_mask=None):
+        """The whole counterfactual row of every selected link: what the env's total capacity would gain if link i ALONE had taken
+        the action (RB r, power level l), for every r and every l of its alphabet, with positions and every other link as the last
+        step left them: (gain_mbps float32 [B, M, R, Lmax], links int32 [M], levels int32 [M]).  It is the COMA / aristocrat-utility
+        baseline, the table behind exploitability and regret (the joint action is a Nash point of the team game iff no row holds a
+        positive entry) and, under SINR floors, an exact safe-action mask: a closed entry is -inf.  It is also the product
+        neighbourhood, where an RB and a power change in one move, which no ascent of this package searches.
+
+        A link is on an RB iff 0 <= rb < R; the group of RB r is the set of links on r in ascending link index.  For a selected link
+        i on RB c at power p, an RB r and a power q = p_min[i] + l: s^(r,q) is the held state with rb[i] = r, pwr[i] = q, and
+        cap_m(.), sinr_m(.) are the float32 values evaluate() gives link m for a state, bit for bit.  With(r,q) is the sum, in
+        double, in ascending link index, of cap_m(s^(r,q)) over group(r) and i; Without(r) is the same sum over group(r) less i
+        with i on no RB (an empty sum is 0.0).  D(r,q) = With(r,q) - Without(r) is what link i's presence on r at q is worth to
+        the total, and gain(r,q) = D(r,q) - D(c,p), each one double subtraction: gain(c,p) is +0.0 exactly, and because groups do
+        not interact gain(r,q) is, in exact arithmetic, the change of the env's total capacity when link i alone plays (r,q).
+        (r,q) is admissible iff it is (c,p), or every m of group(r) and i with a floor above -inf has sinr_m(s^(r,q)) >= floor[m]
+        or sinr_m(s) < floor[m] (float32 comparisons, NaN compares false): a link already under its floor constrains nothing, a
+        link that meets its floor is never pushed under it - the rule of rb_ascent() and goodput_ascent() - and leaving c
+        constrains nothing.  An entry is open iff l < L_i (the levels of link i's class), allowed[i][r] (the held RB c is open
+        whatever `allowed` says), it is admissible and link i is on an RB.  A closed entry is -inf, an open one gain(r,q) rounded
+        once to float32; a NaN stays NaN.
+
+        The innermost two axes are in step()'s action order rb * levels + level: where the selected links share one class,
+        gain_mbps.view(B, M, R * Lmax) is indexed by the action itself.  Lmax is the largest L_i of the selection; a link of fewer
+        levels has its last Lmax - L_i columns closed.  `levels` is L_i per selected link, `links` the selection.
+
+        Every entry is independent: B M R Lmax of them in ONE kernel launch (csrc/d2d_deviate.hip), one env served by several
+        workgroups that each stage it in LDS, the entries dealt flat over the threads so that the table leaves in full rows.  An
+        entry with a long group costs G^2 pair evaluations: that is the known limit.  Valid after reset() and after every step(),
+        autoreset steps included, as rb_ascent() is.
+
+        links: None (every agent link), or ascending, distinct link indices (a list or an array of ints); links on fixed actions
+        (cue_actions='traffic') are never selected and may not be named.  allowed: bool [N, R] (tensor or array) as best_rb()
+        takes it; None: every RB.  floor_sinr_db: None (no floors), a number, {'cue': x, 'due': y} or [N] values (array or
+        tensor), dB; -inf: no floor for that link.  env_mask: bool / uint8 [B], envs whose entry is 0 keep their rows; None: all.
+        The power bounds are the ones step() decodes; a class of more than 64 power levels is refused, and so is a table of more
+        than 8 GiB (4 B M R Lmax bytes; the text names the count): select fewer links, or take best_deviation().
+
+        Torch path only: enqueued on torch's current stream, nothing is synchronised; the table the env owns, rewritten by every
+        call (clone it to keep it), or `out`, a contiguous float32 [B, M, R, Lmax] tensor on the env's device.  Serves what
+        rb_ascent() serves, as far as an env's links, allowed words and RB membership fit the LDS of one workgroup (80 bytes per
+        link); ValueError for export_actions=False, ShadowingPathLoss, every table route, pinned device_config coordinates float32
+        cannot hold."""
+        k = self._deviation_kernel()
+        floor = k.floor(floor_sinr_db, self.num_cues)
+        self._follow_torch_stream()
+        return k.gains(self._t, links, allowed, floor, out, self._stream_ptr, env_mask)
+
+    def best_deviation(self, links=None, allowed=None, floor_sinr_db=None, min_gain_mbps: float = 0.0, out=None, env_mask=None):
+        """Every selected link's best unilateral deviation and the env's regret, without the table of deviation_gains(): (rb int32
+        [B, N], power_dbm int32 [B, N], gain_mbps float64 [B, N], regret_mbps float64 [B], leader int32 [B]), a tuple with those
+        names.
+
+        With gain(r,q) and "open" as deviation_gains() words them: best is the open entry other than the held (c,p) of maximal
+        double gain, ties to the lowest power, then to the lowest RB (goodput_ascent()'s rule); a NaN is never chosen.  If
+        gain(best) > min_gain_mbps, (rb, power_dbm)[b, i] = best and gain_mbps[b, i] = gain(best), the double, not rounded to
+        float32; else the held (c,p) with 0.0.  A link that is not selected keeps (rb, pwr) with 0.0.  regret_mbps[b] is the
+        largest gain_mbps of the env - 0.0 at a Nash point of the team game, as far as min_gain_mbps and the floors let a link
+        move - and leader[b] the lowest link that has it, -1 when nobody would move.  Every choice is a reduction of integer keys:
+        two calls give the same words.
+
+        links, allowed, floor_sinr_db, env_mask: as deviation_gains() takes them.  min_gain_mbps: finite, >= 0.
+
+        Torch path only: two launches (csrc/d2d_deviate.hip: the entries, then one workgroup per env for regret and leader) on
+        torch's current stream, nothing is synchronised; the five tensors the env owns, rewritten by every call (clone them to
+        keep them), or `out` = (rb, power_dbm, gain_mbps, regret_mbps, leader), contiguous int32 / int32 / float64 [B, N], float64
+        / int32 [B] on the env's device.  Serves what deviation_gains() serves."""
+        k = self._deviation_kernel()
+        floor = k.floor(floor_sinr_db, self.num_cues)
+        self._follow_torch_stream()
+        return k.best(self._t, links, allowed, floor, min_gain_mbps, out, self._stream_ptr, env_mask)
+
+    def best_deviation_actions(self, links=None, allowed=None, floor_sinr_db=None, min_gain_mbps: float = 0.0):
+        """One STEEPEST-ASCENT step as an action tensor, int32 [B, num_agents], ready for step(): in every env only the `leader` of
+        best_deviation() takes its best (rb, power) and every other agent link repeats its current action (as the decoded planes
+        hold it), encoded rb * power levels + level (power_control.encode_actions).  An env whose leader is -1 repeats its
+        actions.  On an env without mobility the step raises the total capacity by regret_mbps; repeated, it ends at regret 0.
+        Links on fixed actions (cue_actions='traffic') have no column."""
+        res = self.best_deviation(links, allowed, floor_sinr_db, min_gain_mbps)
+        moves = torch.arange(self.num_links, device=self.device, dtype=torch.int32)[None, :] == res.leader[:, None]
+        rb = torch.where(moves, res.rb, self._t['rb'])
+        power = torch.where(moves, res.power_dbm, self._t['pwr'])
+        first, p_min, levels = self._agent_power_levels()
+        return power_control.encode_actions(rb, power, p_min, levels, first)
+
     # ------------------------------------------------------------------ sequential best-response dynamics
     def _best_response_dynamics_kernel(self):
         return self._kernel('_brdyn', best_response_dynamics, best_response_dynamics.BestResponseDynamics,
@@ -1666,4 +1757,7 @@ class VecD2DEnv:
         if self._goodput is not None:
             self._goodput.close()
             self._goodput = None
+        if self._deviation is not None:
+            self._deviation.close()
+            self._deviation = None
         self.simulator.handle.close()
