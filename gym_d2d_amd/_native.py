@@ -137,6 +137,13 @@ DEVIATE_MAX_RBS = 8192
 DEVIATE_MAX_LEVELS = 64
 DEVIATE_MAX_LDS_BYTES = 163840
 DEVIATE_MAX_TABLE_BYTES = 8 << 30
+# d2d_evaluate_table's entry types / limits (include/d2d_evaltab.h): the entry types are F32 / F64 above, the limits d2d_evaluate's
+EVALTAB_F32, EVALTAB_F64 = 0, 1
+EVALTAB_MAX_LINKS = 2048
+EVALTAB_MAX_RBS = 8192
+EVALTAB_CHUNK = 8
+EVALTAB_MAX_CANDIDATES = 65535 * EVALTAB_CHUNK
+EVALTAB_MAX_LDS_BYTES = 163840
 
 BUFFER_DTYPES = {BUF_ACTIONS: np.int32, BUF_RB: np.int32, BUF_PWR: np.int32, BUF_ENV_FLAGS: np.int32, BUF_RESET_PENDING: np.int32,
                  BUF_EPISODE: np.uint32}
@@ -365,6 +372,12 @@ DEVIATE_SIGNATURES = {
     'd2d_deviate_last_error': (C.c_char_p, []),
 }
 
+# every symbol include/d2d_evaltab.h declares
+EVALTAB_SIGNATURES = {
+    'd2d_evaluate_table': (C.c_int, [_P, _I, _I, _P, _P, _P, _P, _P, _P, C.c_int64, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    'd2d_evaltab_last_error': (C.c_char_p, []),
+}
+
 # the side libraries: name -> every symbol include/d2d_<name>.h declares; libd2d_<name>.so, its error text in d2d_<name>_last_error
 SIDE = {'plugin': PLUGIN_SIGNATURES, 'episode': EPISODE_SIGNATURES, 'sense': SENSE_SIGNATURES, 'graph': GRAPH_SIGNATURES,
         'marginal': MARGINAL_SIGNATURES, 'mobility': MOBILITY_SIGNATURES, 'channel': CHANNEL_SIGNATURES, 'queue': QUEUE_SIGNATURES,
@@ -382,7 +395,7 @@ EXACT = {'share': SHARE_SIGNATURES}
 # build.GROWING's libraries, likewise: what joined behind the exact solvers
 GROWING = {'ascent': ASCENT_SIGNATURES}
 # build.LATER's libraries, likewise: what joined behind the power ascent, and the table the next library joins
-LATER = {'rbascent': RBASCENT_SIGNATURES, 'deviate': DEVIATE_SIGNATURES, 'goodput': GOODPUT_SIGNATURES}
+LATER = {'rbascent': RBASCENT_SIGNATURES, 'deviate': DEVIATE_SIGNATURES, 'evaltab': EVALTAB_SIGNATURES, 'goodput': GOODPUT_SIGNATURES}
 
 _lib: Optional[C.CDLL] = None
 _side: dict = {}                    # name -> the opened, typed side library
@@ -406,6 +419,7 @@ ascent_launches = 0                 # d2d_power_ascent launches made through pow
 rbascent_launches = 0               # d2d_rb_ascent launches made through rb_ascent()
 goodput_launches = 0                # d2d_goodput_ascent launches made through goodput_ascent()
 deviate_launches = 0                # d2d_deviation_gains / d2d_best_deviation calls made through deviation_gains() / best_deviation()
+evaltab_launches = 0                # d2d_evaluate_table launches made through evaluate_table()
 mobility_launches = 0               # d2d_mobility_move calls made through mobility_move()
 channel_launches = 0                # d2d_channel_fill calls made through channel_fill()
 queue_launches = 0                  # d2d_queue_step calls made through queue_step()
@@ -480,6 +494,7 @@ def load_ascent_library() -> C.CDLL: return side_library('ascent')
 def load_rbascent_library() -> C.CDLL: return side_library('rbascent')
 def load_goodput_library() -> C.CDLL: return side_library('goodput')
 def load_deviate_library() -> C.CDLL: return side_library('deviate')
+def load_evaltab_library() -> C.CDLL: return side_library('evaltab')
 
 
 # Pointer arguments are passed as the ints they are: every argtype is c_void_p, which takes 0 as the null pointer and any int up to
@@ -614,6 +629,22 @@ def evaluate(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, link_tx_
         n_links, n_rbs, sinr_ptr, capacity_ptr, total_ptr, stream_ptr))
     if n_envs:
         evaluate_launches += 1
+
+
+def evaluate_table(table_ptr: int, table_dtype: int, table_rows: int, rb_ptr: int, pwr_ptr: int, link_tx_ptr: int, link_rx_ptr: int,
+                   cols_ptr: int, cap_cols_ptr: int, n_envs: int, n_cand: int, n_dev: int, n_links: int, n_rbs: int, sinr_ptr: int,
+                   capacity_ptr: int, total_ptr: int, domain_ptr: int, stream_ptr: int = 0) -> None:
+    """d2d_evaluate_table: the planes n_cand candidate assignments per env would give on the dB table at table_ptr (EVALTAB_F32 /
+    EVALTAB_F64 entries, [n_envs, table_rows, n_links] by (tx link, rx link), table_rows = n_links or n_links + 1) - sinr_db and
+    capacity_mbps float32 [n_envs, n_cand, n_links] (either pointer 0: not written), total_mbps float32 and domain int32 [n_envs,
+    n_cand] (device pointers; rb_ptr / pwr_ptr int32 [n_envs, n_cand, n_links]; cols_ptr float32 [3, n_dev]: tx_lin, rx_lin,
+    noise_mw)."""
+    global evaltab_launches
+    _check_side('evaltab', load_evaltab_library().d2d_evaluate_table(
+        table_ptr, table_dtype, table_rows, rb_ptr, pwr_ptr, link_tx_ptr, link_rx_ptr, cols_ptr, cap_cols_ptr, n_envs, n_cand, n_dev,
+        n_links, n_rbs, sinr_ptr, capacity_ptr, total_ptr, domain_ptr, stream_ptr))
+    if n_envs:
+        evaltab_launches += 1
 
 
 def assign_weights(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, link_tx_ptr: int, link_rx_ptr: int, cols_ptr: int,

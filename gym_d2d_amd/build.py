@@ -14,6 +14,7 @@
     rbascent  the sum-capacity RB ascent (4.23), listed in LATER         include/d2d_rbascent.h
     goodput   the queue-aware goodput ascent (4.24), listed in LATER      include/d2d_goodput.h
     deviate   the unilateral-deviation gains (4.25), listed in LATER      include/d2d_deviate.h
+    evaltab   the what-if evaluation on a path-loss table (4.26), in LATER include/d2d_evaltab.h
 
     python -m gym_d2d_amd.build [--force] [--verbose]
     D2D_BUILD_DIAG=1 python -m gym_d2d_amd.build      # diagnostic build of libd2d_hip.so: the A/B tuning keys and the ablation
@@ -73,9 +74,9 @@ EVERY = {**WHOLE, **GROWING}                     # WHOLE and what joined behind 
 # the libraries that joined behind EVERY (which _native.LATER mirrors): compiled and linked last, stamped with the rest, and a
 # missing one is rebuilt (later_missing()).  The next library joins this table: nothing states its length.
 # rbascent: the sum-capacity RB ascent with SINR floors; goodput: the queue-aware goodput ascent (4.24);
-# deviate: the unilateral-deviation gains over every (RB, power) action (4.25) - in front of goodput, which stays the build's last
-# row (tests/test_goodput_ascent_cpu.py states it)
-LATER = {'rbascent': ['d2d_rbascent.hip'], 'deviate': ['d2d_deviate.hip'], 'goodput': ['d2d_goodput.hip']}
+# deviate: the unilateral-deviation gains over every (RB, power) action (4.25); evaltab: the what-if evaluation on a path-loss table
+# (4.26) - both in front of goodput, which stays the build's last row (tests/test_goodput_ascent_cpu.py states it)
+LATER = {'rbascent': ['d2d_rbascent.hip'], 'deviate': ['d2d_deviate.hip'], 'evaltab': ['d2d_evaltab.hip'], 'goodput': ['d2d_goodput.hip']}
 COMPLETE = {**EVERY, **LATER}                    # every library of the build: what the digest, the compile and the link iterate
 HEADERS = [CSRC / 'd2d_internal.h', CSRC / 'd2d_plan.h', CSRC / 'd2d_step_device.h', CSRC / 'd2d_store.h', CSRC / 'd2d_same_rb.h', CSRC / 'd2d_addon.h',
            CSRC / 'd2d_powerctl_device.h', CSRC / 'd2d_wave_key.h', INCLUDE / 'd2d_hip.h', INCLUDE / 'd2d_hip_diag.h',

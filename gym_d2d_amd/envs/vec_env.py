@@ -26,6 +26,7 @@ from .. import _native, assignment, balance, best_response, best_response_dynami
 from .. import evaluate as evaluate_mod
 from .. import mobility as mobility_mod
 from .. import queues as queues_mod
+from .. import table_evaluate as table_evaluate_mod
 from ..path_loss_table import CHANNEL, PER_STEP, positions_move_unserved
 from ..simulator import BASE_STATION_ID, Simulator
 from ..traffic_model import DownlinkTrafficModel
@@ -298,6 +299,8 @@ class VecD2DEnv:
         self._goodput = None
         # unilateral-deviation gains over every (RB, power) action (deviation_gains(), best_deviation()): likewise
         self._deviation = None
+        # what-if evaluation on a path-loss table (evaluate_table()): likewise
+        self._table_evaluate = None
 
     def _setup_autoreset(self) -> None:
         """Refuse what a device-side per-env reset cannot serve, then allocate the per-env bookkeeping: pending / episode are bound
@@ -1344,6 +1347,65 @@ class VecD2DEnv:
         rb, pwr = evaluate_mod.decode_actions(actions, levels, *fixed)
         return k.planes(self._t, rb, pwr, planes, None, self._stream_ptr)
 
+    # ------------------------------------------------------------------ what-if evaluation on a path-loss table
+    def _table_evaluate_kernel(self):
+        return self._kernel('_table_evaluate', table_evaluate_mod, table_evaluate_mod.TableEvaluate)
+
+    def evaluate_table(self, rb, power_dbm, table=None, planes=('sinr_db', 'capacity_mbps'), out=None):
+        """evaluate() for the envs whose step reads a path-loss TABLE: what K complete joint assignments per env would give when
+        the step reads `table` - a dict with 'total_mbps' float32 [B, K], 'domain' int32 [B, K] and the requested planes float32
+        [B, K, N].
+
+        rb, power_dbm, planes: as evaluate() takes them (contiguous int32 [B, K, N] in the units of info['rb'] / info['tx_pwr_dbm'];
+        K >= 1 is free per call; an rb outside [0, num_rbs) puts the link on no RB).  sinr_db[b, k] and capacity_mbps[b, k] are,
+        bit for bit, the planes a step() with that assignment exports when it reads that table; total_mbps[b, k] is evaluate()'s
+        total, the sum of capacity_mbps[b, k] accumulated in double in a fixed order (two calls give the same bits).  domain[b, k]
+        is 1 iff an entry read for that candidate - every link's own entry [i, i] and entry [j, i] of every pair on one RB - is NaN
+        or -inf (the step's D2D_FLAG_PATH_LOSS_DOMAIN, raised only where read); +inf is a legal entry (gain 0); the planes of a
+        flagged candidate are whatever the arithmetic gives.  One kernel launch (csrc/d2d_evaltab.hip).
+
+        table=None: the env's live table AS IT STANDS, that is, the channel realisation of the last step() (or of reset()'s own
+        step).  Served on every route that has one: 'channel' (SpatialChannelPathLoss), 'per_step' (a per-step ArrayPathLoss), and
+        'array' when compute() returned the SNR row; ValueError on any other route, which names table=.  "As it stands" means:
+        with fading the next step() draws again, with mobility= the next step() moves the devices first, and after an autoreset
+        step the block of an env that was reset is its NEW layout's - in each of these the next step's planes are another
+        realisation's.  With fading=None and nothing moving the table IS the next step's and the prediction is exact.
+
+        table=: a contiguous float32 or float64 tensor [B, N, N] or [B, N+1, N] on the env's device, in dB by (tx link, rx link).
+        Works on every route, native models included, and with export_actions=False: the hook for Monte-Carlo over fading draws
+        of one's own and for scoring under a measured channel.  Row N is never read (it feeds snr_db only); SINR and capacity use
+        the signal entry [i, i].
+
+        The env is left untouched: no counter, plane, queue, position or table word changes.  Torch path only: enqueued on torch's
+        current stream, nothing is synchronised; the tensors the env owns, reallocated when K changes and rewritten by every call
+        (clone them to keep them), or `out`, a dict of contiguous tensors with exactly the returned keys and shapes (float32,
+        domain int32)."""
+        k = self._table_evaluate_kernel()
+        self._follow_torch_stream()
+        return k.planes(rb, power_dbm, table, planes, out, self._stream_ptr)
+
+    def evaluate_table_actions(self, actions, table=None, planes=('sinr_db', 'capacity_mbps')):
+        """evaluate_table() of K candidate action sets: actions is an integer tensor [B, K, num_agents], every [:, k] in the layout
+        step() takes (rb * power levels + level).  Links on fixed actions (cue_actions='traffic') have no column and keep their
+        current rb / power in every candidate: with such links - and only then - the env must export its decoded planes
+        (export_actions=True), ValueError otherwise.  Decoded by evaluate.decode_actions; the result and its validity are
+        evaluate_table()'s."""
+        k = self._table_evaluate_kernel()
+        if not torch.is_tensor(actions) or actions.ndim != 3 or tuple(actions.shape[::2]) != (self.num_envs, self.num_agents) \
+                or actions.device != self.device:
+            raise ValueError(f'actions must be an integer tensor [{self.num_envs}, K, {self.num_agents}] (env, candidate, agent) on '
+                             f'{self.device}')
+        first = self.num_links - self.num_agents
+        if first:
+            why = table_evaluate_mod.fixed_links_refusal(self.simulator, self.export_actions)
+            if why:
+                raise ValueError(why)
+        levels = self._agent_levels()
+        self._follow_torch_stream()
+        fixed = (self._t['rb'][:, :first], self._t['pwr'][:, :first]) if first else (None, None)
+        rb, pwr = evaluate_mod.decode_actions(actions, levels, *fixed)
+        return k.planes(rb, pwr, table, planes, None, self._stream_ptr)
+
     # ------------------------------------------------------------------ optimal one-to-one RB matching
     def _assignment_kernel(self):
         return self._kernel('_assign', assignment, assignment.Assignment,
@@ -1730,6 +1792,9 @@ class VecD2DEnv:
         if self._evaluate is not None:
             self._evaluate.close()
             self._evaluate = None
+        if self._table_evaluate is not None:
+            self._table_evaluate.close()
+            self._table_evaluate = None
         if self._assign is not None:
             self._assign.close()
             self._assign = None
