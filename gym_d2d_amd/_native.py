@@ -144,6 +144,12 @@ EVALTAB_MAX_RBS = 8192
 EVALTAB_CHUNK = 8
 EVALTAB_MAX_CANDIDATES = 65535 * EVALTAB_CHUNK
 EVALTAB_MAX_LDS_BYTES = 163840
+# d2d_table_rb_ascent's entry types / limits (include/d2d_tabascent.h): d2d_evaluate_table's entry types, d2d_rb_ascent's limits
+TABASCENT_F32, TABASCENT_F64 = 0, 1
+TABASCENT_MAX_LINKS = 2048
+TABASCENT_MAX_RBS = 8192
+TABASCENT_MAX_ROUNDS = 4096
+TABASCENT_MAX_LDS_BYTES = 163840
 
 BUFFER_DTYPES = {BUF_ACTIONS: np.int32, BUF_RB: np.int32, BUF_PWR: np.int32, BUF_ENV_FLAGS: np.int32, BUF_RESET_PENDING: np.int32,
                  BUF_EPISODE: np.uint32}
@@ -378,6 +384,13 @@ EVALTAB_SIGNATURES = {
     'd2d_evaltab_last_error': (C.c_char_p, []),
 }
 
+# every symbol include/d2d_tabascent.h declares
+TABASCENT_SIGNATURES = {
+    'd2d_table_rb_ascent': (C.c_int, [_P, _I, _I, _P, _P, _P, _P, _P, _P, C.c_int64, _I, _I, _I, _P, _P, _P, C.c_double, _I, _P, _P, _P, _P,
+                                      _P, _P, _P, _P, _P, _P]),
+    'd2d_tabascent_last_error': (C.c_char_p, []),
+}
+
 # the side libraries: name -> every symbol include/d2d_<name>.h declares; libd2d_<name>.so, its error text in d2d_<name>_last_error
 SIDE = {'plugin': PLUGIN_SIGNATURES, 'episode': EPISODE_SIGNATURES, 'sense': SENSE_SIGNATURES, 'graph': GRAPH_SIGNATURES,
         'marginal': MARGINAL_SIGNATURES, 'mobility': MOBILITY_SIGNATURES, 'channel': CHANNEL_SIGNATURES, 'queue': QUEUE_SIGNATURES,
@@ -395,7 +408,8 @@ EXACT = {'share': SHARE_SIGNATURES}
 # build.GROWING's libraries, likewise: what joined behind the exact solvers
 GROWING = {'ascent': ASCENT_SIGNATURES}
 # build.LATER's libraries, likewise: what joined behind the power ascent, and the table the next library joins
-LATER = {'rbascent': RBASCENT_SIGNATURES, 'deviate': DEVIATE_SIGNATURES, 'evaltab': EVALTAB_SIGNATURES, 'goodput': GOODPUT_SIGNATURES}
+LATER = {'rbascent': RBASCENT_SIGNATURES, 'deviate': DEVIATE_SIGNATURES, 'evaltab': EVALTAB_SIGNATURES,
+         'tabascent': TABASCENT_SIGNATURES, 'goodput': GOODPUT_SIGNATURES}
 
 _lib: Optional[C.CDLL] = None
 _side: dict = {}                    # name -> the opened, typed side library
@@ -420,6 +434,7 @@ rbascent_launches = 0               # d2d_rb_ascent launches made through rb_asc
 goodput_launches = 0                # d2d_goodput_ascent launches made through goodput_ascent()
 deviate_launches = 0                # d2d_deviation_gains / d2d_best_deviation calls made through deviation_gains() / best_deviation()
 evaltab_launches = 0                # d2d_evaluate_table launches made through evaluate_table()
+tabascent_launches = 0              # d2d_table_rb_ascent calls made through table_rb_ascent() (two kernel launches each)
 mobility_launches = 0               # d2d_mobility_move calls made through mobility_move()
 channel_launches = 0                # d2d_channel_fill calls made through channel_fill()
 queue_launches = 0                  # d2d_queue_step calls made through queue_step()
@@ -495,6 +510,7 @@ def load_rbascent_library() -> C.CDLL: return side_library('rbascent')
 def load_goodput_library() -> C.CDLL: return side_library('goodput')
 def load_deviate_library() -> C.CDLL: return side_library('deviate')
 def load_evaltab_library() -> C.CDLL: return side_library('evaltab')
+def load_tabascent_library() -> C.CDLL: return side_library('tabascent')
 
 
 # Pointer arguments are passed as the ints they are: every argtype is c_void_p, which takes 0 as the null pointer and any int up to
@@ -645,6 +661,27 @@ def evaluate_table(table_ptr: int, table_dtype: int, table_rows: int, rb_ptr: in
         n_links, n_rbs, sinr_ptr, capacity_ptr, total_ptr, domain_ptr, stream_ptr))
     if n_envs:
         evaltab_launches += 1
+
+
+def table_rb_ascent(table_ptr: int, table_dtype: int, table_rows: int, rb_ptr: int, pwr_ptr: int, link_tx_ptr: int, link_rx_ptr: int,
+                    cols_ptr: int, cap_cols_ptr: int, n_envs: int, n_dev: int, n_links: int, n_rbs: int, allowed_ptr: int, movable_ptr: int,
+                    floor_ptr: int, min_gain_mbps: float, max_rounds: int, env_mask_ptr: int, gains_ptr: int, rb_out_ptr: int,
+                    sinr_ptr: int, capacity_ptr: int, rounds_ptr: int, moves_ptr: int, converged_ptr: int, domain_ptr: int,
+                    stream_ptr: int = 0) -> None:
+    """d2d_table_rb_ascent: the sum-capacity RB ascent of every env on the dB table at table_ptr (TABASCENT_F32 / TABASCENT_F64
+    entries, [n_envs, table_rows, n_links] by (tx link, rx link), table_rows = n_links or n_links + 1) - rb int32, sinr_db and
+    capacity_mbps float32 [n_envs, n_links], rounds and moves int32, converged uint8, domain int32 [n_envs] (device pointers; rb_ptr /
+    pwr_ptr int32 [n_envs, n_links]: the start state; cols_ptr float32 [3, n_dev]: tx_lin, rx_lin, noise_mw; gains_ptr: the float32
+    work space [n_envs, n_links, n_links]; allowed_ptr 0: every RB, else uint32 [n_links, ceil(n_rbs / 32)]; movable_ptr 0: every link,
+    else uint8 [n_links]; floor_ptr 0: no floors, else float32 [n_links], -inf: none for that link; env_mask_ptr 0: every env, else
+    uint8 [n_envs] and the envs whose byte is 0 keep their rows)."""
+    global tabascent_launches
+    _check_side('tabascent', load_tabascent_library().d2d_table_rb_ascent(
+        table_ptr, table_dtype, table_rows, rb_ptr, pwr_ptr, link_tx_ptr, link_rx_ptr, cols_ptr, cap_cols_ptr, n_envs, n_dev, n_links,
+        n_rbs, allowed_ptr, movable_ptr, floor_ptr, min_gain_mbps, max_rounds, env_mask_ptr, gains_ptr, rb_out_ptr, sinr_ptr,
+        capacity_ptr, rounds_ptr, moves_ptr, converged_ptr, domain_ptr, stream_ptr))
+    if n_envs:
+        tabascent_launches += 1
 
 
 def assign_weights(pos_x_ptr: int, pos_y_ptr: int, rb_ptr: int, pwr_ptr: int, link_tx_ptr: int, link_rx_ptr: int, cols_ptr: int,

@@ -27,6 +27,7 @@ from .. import evaluate as evaluate_mod
 from .. import mobility as mobility_mod
 from .. import queues as queues_mod
 from .. import table_evaluate as table_evaluate_mod
+from .. import table_rb_ascent as table_rb_ascent_mod
 from ..path_loss_table import CHANNEL, PER_STEP, positions_move_unserved
 from ..simulator import BASE_STATION_ID, Simulator
 from ..traffic_model import DownlinkTrafficModel
@@ -301,6 +302,8 @@ class VecD2DEnv:
         self._deviation = None
         # what-if evaluation on a path-loss table (evaluate_table()): likewise
         self._table_evaluate = None
+        # sum-capacity RB ascent on a path-loss table (rb_ascent_table()): likewise
+        self._table_rbascent = None
 
     def _setup_autoreset(self) -> None:
         """Refuse what a device-side per-env reset cannot serve, then allocate the per-env bookkeeping: pending / episode are bound
@@ -1406,6 +1409,72 @@ class VecD2DEnv:
         rb, pwr = evaluate_mod.decode_actions(actions, levels, *fixed)
         return k.planes(rb, pwr, table, planes, None, self._stream_ptr)
 
+    # ------------------------------------------------------------------ sum-capacity RB ascent on a path-loss table
+    def _table_rb_ascent_kernel(self):
+        return self._kernel('_table_rbascent', table_rb_ascent_mod, table_rb_ascent_mod.TableRbAscent, lambda: (self._agent_links(),))
+
+    def rb_ascent_table(self, table=None, rb=None, power_dbm=None, allowed=None, movable=None, floor_sinr_db=None,
+                        min_gain_mbps: float = 0.0, max_rounds: int = 16, out=None, env_mask=None):
+        """rb_ascent() for the envs whose step reads a path-loss TABLE: the RBs a cooperative local search on the total capacity ends
+        at when the step reads `table` - (rb int32 [B, N], sinr_db float32 [B, N], capacity_mbps float32 [B, N], rounds int32 [B],
+        moves int32 [B], converged uint8 [B], domain int32 [B]), a tuple with those names.  Only rb changes.
+
+        The statement is rb_ascent()'s, steps and round rule, with one substitution: sinr^r_m and cap^r_m are the float32 values
+        evaluate_table() gives link m for (rb^r, pwr) on `table`, bit for bit.  A link is on an RB iff 0 <= rb < R; the group of RB r
+        is the set of links on r in ascending link index; a link is movable iff it is on an RB, `movable` marks it (None: the agent
+        links; links on cue_actions='traffic' never move) and it has at least one allowed RB.  In the turn of the movable link i on
+        RB c, With(r) is the sum, in double, in ascending link index, of cap^r_m over group(r) and i, Without(r) the same sum over
+        group(r) less i with i not on r, D(r) = With(r) - Without(r); r is a candidate iff r != c, allowed[i][r] and every m of
+        group(r) and i with a floor above -inf has sinr^r_m >= floor[m] or sinr^c_m < floor[m] (float32, NaN compares false); best is
+        the lowest candidate whose D is maximal (a NaN D is never chosen) and link i moves to it, at once, iff D(best) - D(c) >
+        min_gain_mbps (a NaN does not move).  The movable links take turns in ascending link index; a round that moves nobody ends
+        the ascent (converged 1), and so do max_rounds rounds that each moved a link (converged 0).  Termination is rb_ascent()'s
+        property.  sinr_db and capacity_mbps are evaluate_table(rb, pwr, table)'s planes for every link, a link on no RB included.
+
+        table: exactly what evaluate_table() takes.  None: the env's live table AS IT STANDS, the channel realisation of the last
+        step() - served on the 'channel' and 'per_step' routes and on 'array' with an SNR row, ValueError on any other route, which
+        names table=; with fading the next step() draws again, with mobility= it moves first (see evaluate_table()).  A tensor:
+        contiguous float32 or float64 [B, N, N] or [B, N+1, N] on the env's device, in dB by (tx link, rx link), on every route,
+        native models and ShadowingPathLoss included; row N is never read.
+
+        rb, power_dbm: the start state, contiguous int32 [B, N] in the units of info['rb'] / info['tx_pwr_dbm'].  None: the decoded
+        planes of the last step, which needs export_actions=True (ValueError otherwise, naming rb= and power_dbm=); given
+        explicitly they work with export_actions=False.
+
+        domain[b] is 1 iff ANY entry [j, i] with j, i < N of env b's block is NaN or -inf - the whole block, not "where read": a
+        trajectory may read any pair.  +inf is a legal entry (gain 0).  The other outputs of a flagged env are whatever the
+        arithmetic gives.
+
+        allowed, movable, floor_sinr_db, min_gain_mbps, max_rounds, env_mask (envs whose entry is 0 keep all seven rows), out:
+        rb_ascent()'s meaning, checks and limits.  Two kernel launches (csrc/d2d_tabascent.hip): the table is converted once into
+        float32 linear gains, receiver-major, in a work space the env owns - 4 B N N bytes, allocated by the first call and kept:
+        4.3 GB at 4096 envs x 512 links - and all turns of an env then run in one workgroup out of LDS, the pair gains read from
+        that block.  A lane with a long group does G^2 pair loads while the others wait: that is the known limit.
+
+        The env is left untouched.  Torch path only: enqueued on torch's current stream, nothing is synchronised; the seven tensors
+        the env owns, rewritten by every call (clone them to keep them), or `out` = (rb, sinr_db, capacity_mbps, rounds, moves,
+        converged, domain), contiguous int32 / float32 / float32 [B, N], int32 / int32 / uint8 / int32 [B] on the env's device.
+        ValueError for shapes whose links, allowed words and RB membership exceed the LDS of one workgroup, with the byte count."""
+        k = self._table_rb_ascent_kernel()
+        if (rb is None or power_dbm is None) and not self.export_actions:
+            raise ValueError(table_rb_ascent_mod.no_start_state())
+        rb = self._t['rb'] if rb is None else k.start(rb, 'rb')
+        pwr = self._t['pwr'] if power_dbm is None else k.start(power_dbm, 'power_dbm')
+        mov, floor = k.movable(movable), k.floor(floor_sinr_db, self.num_cues)
+        self._follow_torch_stream()
+        return k.solve(table, rb, pwr, allowed, mov, floor, min_gain_mbps, max_rounds, out, self._stream_ptr, env_mask)
+
+    def rb_ascent_table_actions(self, table=None, allowed=None, movable=None, floor_sinr_db=None, min_gain_mbps: float = 0.0,
+                                max_rounds: int = 16):
+        """rb_ascent_table() from the decoded planes of the last step as an action tensor, int32 [B, num_agents], ready for step():
+        every agent link on its solved RB at its current power level (as the decoded planes hold it), encoded rb * power levels +
+        level (best_response_dynamics.encode_actions).  Links on fixed actions (cue_actions='traffic') have no column.  Needs
+        export_actions=True."""
+        if not self.export_actions and self.use_torch:
+            raise ValueError(table_rb_ascent_mod.no_start_state('rb_ascent_table_actions()'))
+        rb = self.rb_ascent_table(table, None, None, allowed, movable, floor_sinr_db, min_gain_mbps, max_rounds)[0]
+        return best_response_dynamics.encode_actions(rb, self._t['pwr'], self._agent_levels(), self.num_links - self.num_agents)
+
     # ------------------------------------------------------------------ optimal one-to-one RB matching
     def _assignment_kernel(self):
         return self._kernel('_assign', assignment, assignment.Assignment,
@@ -1795,6 +1864,9 @@ class VecD2DEnv:
         if self._table_evaluate is not None:
             self._table_evaluate.close()
             self._table_evaluate = None
+        if self._table_rbascent is not None:
+            self._table_rbascent.close()
+            self._table_rbascent = None
         if self._assign is not None:
             self._assign.close()
             self._assign = None
