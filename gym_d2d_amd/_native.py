@@ -150,6 +150,11 @@ TABASCENT_MAX_LINKS = 2048
 TABASCENT_MAX_RBS = 8192
 TABASCENT_MAX_ROUNDS = 4096
 TABASCENT_MAX_LDS_BYTES = 163840
+# d2d_table_marginal's entry types / limits (include/d2d_tabmarg.h): d2d_evaluate_table's entry types, d2d_marginal_capacity's limits
+TABMARG_F32, TABMARG_F64 = 0, 1
+TABMARG_MAX_LINKS = 2048
+TABMARG_MAX_RBS = 8192
+TABMARG_MAX_LDS_BYTES = 163840
 
 BUFFER_DTYPES = {BUF_ACTIONS: np.int32, BUF_RB: np.int32, BUF_PWR: np.int32, BUF_ENV_FLAGS: np.int32, BUF_RESET_PENDING: np.int32,
                  BUF_EPISODE: np.uint32}
@@ -391,6 +396,12 @@ TABASCENT_SIGNATURES = {
     'd2d_tabascent_last_error': (C.c_char_p, []),
 }
 
+# every symbol include/d2d_tabmarg.h declares
+TABMARG_SIGNATURES = {
+    'd2d_table_marginal': (C.c_int, [_P, _I, _I, _P, _P, _P, _P, _P, _P, C.c_int64, _I, _I, _I, _P, _P, _P, _P]),
+    'd2d_tabmarg_last_error': (C.c_char_p, []),
+}
+
 # the side libraries: name -> every symbol include/d2d_<name>.h declares; libd2d_<name>.so, its error text in d2d_<name>_last_error
 SIDE = {'plugin': PLUGIN_SIGNATURES, 'episode': EPISODE_SIGNATURES, 'sense': SENSE_SIGNATURES, 'graph': GRAPH_SIGNATURES,
         'marginal': MARGINAL_SIGNATURES, 'mobility': MOBILITY_SIGNATURES, 'channel': CHANNEL_SIGNATURES, 'queue': QUEUE_SIGNATURES,
@@ -408,7 +419,7 @@ EXACT = {'share': SHARE_SIGNATURES}
 # build.GROWING's libraries, likewise: what joined behind the exact solvers
 GROWING = {'ascent': ASCENT_SIGNATURES}
 # build.LATER's libraries, likewise: what joined behind the power ascent, and the table the next library joins
-LATER = {'rbascent': RBASCENT_SIGNATURES, 'deviate': DEVIATE_SIGNATURES, 'evaltab': EVALTAB_SIGNATURES,
+LATER = {'rbascent': RBASCENT_SIGNATURES, 'deviate': DEVIATE_SIGNATURES, 'tabmarg': TABMARG_SIGNATURES, 'evaltab': EVALTAB_SIGNATURES,
          'tabascent': TABASCENT_SIGNATURES, 'goodput': GOODPUT_SIGNATURES}
 
 _lib: Optional[C.CDLL] = None
@@ -435,6 +446,7 @@ goodput_launches = 0                # d2d_goodput_ascent launches made through g
 deviate_launches = 0                # d2d_deviation_gains / d2d_best_deviation calls made through deviation_gains() / best_deviation()
 evaltab_launches = 0                # d2d_evaluate_table launches made through evaluate_table()
 tabascent_launches = 0              # d2d_table_rb_ascent calls made through table_rb_ascent() (two kernel launches each)
+tabmarg_launches = 0                # d2d_table_marginal launches made through table_marginal()
 mobility_launches = 0               # d2d_mobility_move calls made through mobility_move()
 channel_launches = 0                # d2d_channel_fill calls made through channel_fill()
 queue_launches = 0                  # d2d_queue_step calls made through queue_step()
@@ -511,6 +523,7 @@ def load_goodput_library() -> C.CDLL: return side_library('goodput')
 def load_deviate_library() -> C.CDLL: return side_library('deviate')
 def load_evaltab_library() -> C.CDLL: return side_library('evaltab')
 def load_tabascent_library() -> C.CDLL: return side_library('tabascent')
+def load_tabmarg_library() -> C.CDLL: return side_library('tabmarg')
 
 
 # Pointer arguments are passed as the ints they are: every argtype is c_void_p, which takes 0 as the null pointer and any int up to
@@ -661,6 +674,21 @@ def evaluate_table(table_ptr: int, table_dtype: int, table_rows: int, rb_ptr: in
         n_links, n_rbs, sinr_ptr, capacity_ptr, total_ptr, domain_ptr, stream_ptr))
     if n_envs:
         evaltab_launches += 1
+
+
+def table_marginal(table_ptr: int, table_dtype: int, table_rows: int, rb_ptr: int, pwr_ptr: int, link_tx_ptr: int, link_rx_ptr: int,
+                   cols_ptr: int, cap_cols_ptr: int, n_envs: int, n_dev: int, n_links: int, n_rbs: int, harm_ptr: int, diff_ptr: int,
+                   domain_ptr: int, stream_ptr: int = 0) -> None:
+    """d2d_table_marginal: every link's harm and difference reward (Mbps) on the dB table at table_ptr (TABMARG_F32 / TABMARG_F64
+    entries, [n_envs, table_rows, n_links] by (tx link, rx link), table_rows = n_links or n_links + 1) into two float32 planes
+    [n_envs, n_links], and domain int32 [n_envs] (device pointers; rb_ptr / pwr_ptr int32 [n_envs, n_links]; cols_ptr float32
+    [3, n_dev]: tx_lin, rx_lin, noise_mw)."""
+    global tabmarg_launches
+    _check_side('tabmarg', load_tabmarg_library().d2d_table_marginal(
+        table_ptr, table_dtype, table_rows, rb_ptr, pwr_ptr, link_tx_ptr, link_rx_ptr, cols_ptr, cap_cols_ptr, n_envs, n_dev, n_links,
+        n_rbs, harm_ptr, diff_ptr, domain_ptr, stream_ptr))
+    if n_envs:
+        tabmarg_launches += 1
 
 
 def table_rb_ascent(table_ptr: int, table_dtype: int, table_rows: int, rb_ptr: int, pwr_ptr: int, link_tx_ptr: int, link_rx_ptr: int,

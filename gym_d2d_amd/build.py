@@ -14,6 +14,7 @@
     rbascent  the sum-capacity RB ascent (4.23), listed in LATER         include/d2d_rbascent.h
     goodput   the queue-aware goodput ascent (4.24), listed in LATER      include/d2d_goodput.h
     deviate   the unilateral-deviation gains (4.25), listed in LATER      include/d2d_deviate.h
+    tabmarg   the difference rewards on a path-loss table (4.28), in LATER include/d2d_tabmarg.h
     evaltab   the what-if evaluation on a path-loss table (4.26), in LATER include/d2d_evaltab.h
     tabascent the sum-capacity RB ascent on a path-loss table (4.27), in LATER include/d2d_tabascent.h
 
@@ -76,10 +77,11 @@ EVERY = {**WHOLE, **GROWING}                     # WHOLE and what joined behind 
 # missing one is rebuilt (later_missing()).  The next library joins this table: nothing states its length.
 # rbascent: the sum-capacity RB ascent with SINR floors; goodput: the queue-aware goodput ascent (4.24);
 # deviate: the unilateral-deviation gains over every (RB, power) action (4.25); evaltab: the what-if evaluation on a path-loss table
-# (4.26); tabascent: the sum-capacity RB ascent on a path-loss table (4.27) - all three in front of goodput, which stays the build's
-# last row (tests/test_goodput_ascent_cpu.py states it)
-LATER = {'rbascent': ['d2d_rbascent.hip'], 'deviate': ['d2d_deviate.hip'], 'evaltab': ['d2d_evaltab.hip'],
-         'tabascent': ['d2d_tabascent.hip'], 'goodput': ['d2d_goodput.hip']}
+# (4.26); tabascent: the sum-capacity RB ascent on a path-loss table (4.27); tabmarg: the difference rewards on a path-loss table
+# (4.28), between deviate and evaltab - all four in front of goodput, which stays the build's last row
+# (tests/test_goodput_ascent_cpu.py states it)
+LATER = {'rbascent': ['d2d_rbascent.hip'], 'deviate': ['d2d_deviate.hip'], 'tabmarg': ['d2d_tabmarg.hip'],
+         'evaltab': ['d2d_evaltab.hip'], 'tabascent': ['d2d_tabascent.hip'], 'goodput': ['d2d_goodput.hip']}
 COMPLETE = {**EVERY, **LATER}                    # every library of the build: what the digest, the compile and the link iterate
 HEADERS = [CSRC / 'd2d_internal.h', CSRC / 'd2d_plan.h', CSRC / 'd2d_step_device.h', CSRC / 'd2d_store.h', CSRC / 'd2d_same_rb.h', CSRC / 'd2d_addon.h',
            CSRC / 'd2d_powerctl_device.h', CSRC / 'd2d_wave_key.h', INCLUDE / 'd2d_hip.h', INCLUDE / 'd2d_hip_diag.h',

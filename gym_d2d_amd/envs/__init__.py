@@ -3,7 +3,7 @@
 this cycle and fails on `import gym_d2d.simulator` first."""
 
 __all__ = ['D2DEnv', 'VecD2DEnv', 'RbSensingObsFunction', 'NeighborObsFunction', 'DifferenceRewardFunction', 'QueueObsFunction',
-           'GoodputRewardFunction', 'BestRbObsFunction']
+           'GoodputRewardFunction', 'BestRbObsFunction', 'TableDifferenceRewardFunction']
 
 
 def __getattr__(name):
@@ -31,4 +31,7 @@ def __getattr__(name):
     if name == 'BestRbObsFunction':
         from .obs_fn import BestRbObsFunction
         return BestRbObsFunction
+    if name == 'TableDifferenceRewardFunction':
+        from .reward_fn import TableDifferenceRewardFunction
+        return TableDifferenceRewardFunction
     raise AttributeError(name)

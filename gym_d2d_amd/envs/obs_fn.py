@@ -58,7 +58,10 @@ class ArrayObsFunction(ABC):
     (VecD2DEnv.neighbors: receiver-major, row [b, i] belongs to the RECEIVING link i, strongest first): selected at reset() and for
     the envs an autoreset step reset, never per step; without the attribute nothing is built, allocated or launched.  A subclass that
     sets `needs_best_rb = True` also gets best_rb int32, best_sinr_db and gain_db float32 [B,N] (VecD2DEnv.best_rb: one launch of
-    csrc/d2d_bestrb.hip behind every step and reset); without the attribute nothing is loaded, allocated or launched."""
+    csrc/d2d_bestrb.hip behind every step and reset); without the attribute nothing is loaded, allocated or launched.  A subclass
+    that sets `needs_table_marginal = True` also gets difference_mbps and harm_mbps float32 [B,N] on the path-loss table the step
+    just read (VecD2DEnv.marginal_capacity_table: one launch of csrc/d2d_tabmarg.hip behind every step and reset; table routes
+    only, refused at construction elsewhere)."""
     native_mode = _native.OBS_TABLE
     needs_rb_sensing = False
     needs_neighbors = 0

@@ -2,7 +2,7 @@
 kernel (csrc/d2d_step.hip, pass 3); `native_id` / `native_param` select the branch.  Calling a built-in with a
 NativeState just re-keys the kernel's per-agent output.  A user subclass that overrides __call__ runs as Python.
 DifferenceRewardFunction and GoodputRewardFunction are the array-native ones: VecD2DEnv hands them the planes of csrc/d2d_marginal.hip
-and csrc/d2d_queue.hip."""
+and csrc/d2d_queue.hip; TableDifferenceRewardFunction gets those of csrc/d2d_tabmarg.hip on the table routes."""
 from __future__ import annotations
 
 from abc import ABC, abstractmethod
@@ -89,6 +89,22 @@ class DifferenceRewardFunction(RewardFunction):
     def __call__(self, actions, state):
         raise RuntimeError('DifferenceRewardFunction is computed from the batched planes of VecD2DEnv (marginal_capacity()); the '
                            'single-env dict D2DEnv does not serve it')
+
+
+class TableDifferenceRewardFunction(RewardFunction):
+    """DifferenceRewardFunction for the envs whose step reads a path-loss table ('channel', 'per_step', 'array' with an SNR row):
+    D_i = G(a) - G(a without link i) on the table the step just read (csrc/d2d_tabmarg.hip).  VecD2DEnv only:
+    `needs_table_marginal` asks the env for view.difference_mbps / view.harm_mbps [B, N], one extra kernel launch per step; an env
+    without a live table, with export_actions=False or on the NumPy path refuses it at construction."""
+    native_id = _native.REWARD_NONE
+    needs_table_marginal = True
+
+    def compute(self, view):
+        return view.difference_mbps
+
+    def __call__(self, actions, state):
+        raise RuntimeError('TableDifferenceRewardFunction is computed from the batched planes of VecD2DEnv '
+                           '(marginal_capacity_table()); the single-env dict D2DEnv does not serve it')
 
 
 class GoodputRewardFunction(RewardFunction):

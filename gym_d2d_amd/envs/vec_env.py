@@ -27,6 +27,7 @@ from .. import evaluate as evaluate_mod
 from .. import mobility as mobility_mod
 from .. import queues as queues_mod
 from .. import table_evaluate as table_evaluate_mod
+from .. import table_marginal as table_marginal_mod
 from .. import table_rb_ascent as table_rb_ascent_mod
 from ..path_loss_table import CHANNEL, PER_STEP, positions_move_unserved
 from ..simulator import BASE_STATION_ID, Simulator
@@ -304,6 +305,17 @@ class VecD2DEnv:
         self._table_evaluate = None
         # sum-capacity RB ascent on a path-loss table (rb_ascent_table()): likewise
         self._table_rbascent = None
+        # difference rewards on a path-loss table (marginal_capacity_table()): likewise nothing unless it is called or the reward /
+        # obs function asks
+        self._table_marginal = None
+        self._obs_table_marginal = bool(getattr(self.obs_fn, 'needs_table_marginal', False)) and self._array_obs
+        self._wants_table_marginal = self._obs_table_marginal or bool(getattr(self.reward_fn, 'needs_table_marginal', False))
+        if self._wants_table_marginal:             # refusals surface here, not inside the first step
+            who = self.reward_fn if getattr(self.reward_fn, 'needs_table_marginal', False) else self.obs_fn
+            why = table_marginal_mod.reward_refusal(sim, self.export_actions, self.use_torch, type(who).__name__)
+            if why:
+                raise ValueError(why)
+            self._table_marginal_kernel()
 
     def _setup_autoreset(self) -> None:
         """Refuse what a device-side per-env reset cannot serve, then allocate the per-env bookkeeping: pending / episode are bound
@@ -475,6 +487,8 @@ class VecD2DEnv:
         view = self._view()
         if self._obs_marginal:
             view = self._with_marginal(view)
+        if self._obs_table_marginal:
+            view = self._with_table_marginal(view)
         if self._obs_best_rb:
             view = self._with_best_rb(view)
         return self._observe(view)
@@ -588,6 +602,8 @@ class VecD2DEnv:
         view = self._view()
         if self._wants_marginal:
             view = self._with_marginal(view)
+        if self._wants_table_marginal:
+            view = self._with_table_marginal(view)            # one launch behind the step, on the table the step just read
         if self._wants_best_rb:
             view = self._with_best_rb(view)
         obs = self._observe(view)
@@ -636,6 +652,8 @@ class VecD2DEnv:
             self._select_neighbors(None if refresh else t['reset'])   # the envs this step reset stand at new positions; moved: all
         if self._wants_marginal:
             view = self._with_marginal(view)                  # after the step: the envs it reset at their new positions and actions
+        if self._wants_table_marginal:
+            view = self._with_table_marginal(view)            # likewise: the table is the last fill, the reset envs' new blocks included
         if self._wants_best_rb:
             view = self._with_best_rb(view)                   # likewise: one launch behind the step serves every env
         obs = self._observe(view)
@@ -1475,6 +1493,50 @@ class VecD2DEnv:
         rb = self.rb_ascent_table(table, None, None, allowed, movable, floor_sinr_db, min_gain_mbps, max_rounds)[0]
         return best_response_dynamics.encode_actions(rb, self._t['pwr'], self._agent_levels(), self.num_links - self.num_agents)
 
+    # ------------------------------------------------------------------ difference rewards on a path-loss table
+    def _table_marginal_kernel(self):
+        return self._kernel('_table_marginal', table_marginal_mod, table_marginal_mod.TableMarginal)
+
+    def marginal_capacity_table(self, table=None, rb=None, power_dbm=None, out=None):
+        """marginal_capacity() for the envs whose step reads a path-loss TABLE: what every link costs the others when the step reads
+        `table` - (difference_mbps float32 [B, N], harm_mbps float32 [B, N], domain int32 [B]), a tuple with those names.
+
+        harm_mbps[b, i] is the capacity the OTHER links of link i's RB would gain if link i alone went off the air - the sum over
+        them of cap_j without i's transmitter minus cap_j with it, the `sinr > rx_sensitivity` threshold of the step included - and
+        difference_mbps[b, i] = capacity_mbps[b, i] - harm_mbps[b, i], where capacity_mbps is evaluate_table()'s plane for (rb,
+        power_dbm) on `table`, bit for bit (with the defaults: the last step's own capacity_mbps).  harm >= 0; a link alone on its
+        RB, or on no RB (rb outside [0, num_rbs)), has harm == 0.0 and difference == capacity exactly.  domain[b] is 1 iff an entry
+        read for env b's state - every link's own entry [i, i] and entry [j, i] of every pair on one RB - is NaN or -inf
+        (evaluate_table()'s rule, per env); +inf is a legal entry (gain 0, harm 0); the planes of a flagged env are whatever the
+        arithmetic gives.  One kernel launch (csrc/d2d_tabmarg.hip) that reads the table in place: no [B, N, N] work space.
+
+        table: exactly what rb_ascent_table() takes.  None: the env's live table AS IT STANDS, the channel realisation of the last
+        step() - served on the 'channel' and 'per_step' routes and on 'array' with an SNR row, ValueError on any other route, which
+        names table=.  A tensor: contiguous float32 or float64 [B, N, N] or [B, N+1, N] on the env's device, in dB by (tx link, rx
+        link), on every route, native models and ShadowingPathLoss included; row N is never read.
+
+        rb, power_dbm: contiguous int32 [B, N] in the units of info['rb'] / info['tx_pwr_dbm'].  None: the decoded planes of the
+        last step, which needs export_actions=True (ValueError otherwise, naming rb= and power_dbm=); given explicitly they work with
+        export_actions=False.
+
+        The env is left untouched.  Torch path only: enqueued on torch's current stream, nothing is synchronised; the three tensors
+        the env owns, rewritten by every call (clone them to keep them), or `out` = (difference_mbps, harm_mbps, domain), contiguous
+        float32 / float32 [B, N] and int32 [B] on the env's device that do not share memory.  marginal_capacity() itself keeps
+        refusing the table routes."""
+        k = self._table_marginal_kernel()
+        if (rb is None or power_dbm is None) and not self.export_actions:
+            raise ValueError(table_marginal_mod.no_start_state())
+        rb = self._t['rb'] if rb is None else k.start(rb, 'rb')
+        pwr = self._t['pwr'] if power_dbm is None else k.start(power_dbm, 'power_dbm')
+        self._follow_torch_stream()
+        return k.marginal(table, rb, pwr, out, self._stream_ptr)
+
+    def _with_table_marginal(self, view):
+        """The view plus difference_mbps / harm_mbps on the table the step just read, as a namespace of its own (_with_marginal's
+        form): the cached view stays what every other consumer sees."""
+        diff, harm, _ = self.marginal_capacity_table()
+        return SimpleNamespace(**vars(view), difference_mbps=diff, harm_mbps=harm)
+
     # ------------------------------------------------------------------ optimal one-to-one RB matching
     def _assignment_kernel(self):
         return self._kernel('_assign', assignment, assignment.Assignment,
@@ -1867,6 +1929,9 @@ class VecD2DEnv:
         if self._table_rbascent is not None:
             self._table_rbascent.close()
             self._table_rbascent = None
+        if self._table_marginal is not None:
+            self._table_marginal.close()
+            self._table_marginal = None
         if self._assign is not None:
             self._assign.close()
             self._assign = None
