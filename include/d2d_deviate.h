@@ -72,7 +72,9 @@
  *
  *   80 n_links + has_allowed round16(4 n_links ceil(n_rbs / 32)) + round16(4 ceil(n_links / 32) n_rbs) + 5216
  *
- * (has_allowed = allowed != NULL), which must fit D2D_DEVIATE_MAX_LDS_BYTES.
+ * (has_allowed = allowed != NULL), which must fit D2D_DEVIATE_MAX_LDS_BYTES.  This bound binds before D2D_DEVIATE_MAX_LINKS does:
+ * 80 x 2048 is the whole 163840 and the 5216 come on top, so 2048 links never fit - with n_rbs = 1 and no mask the largest shape
+ * taken is 1979 links (163792 bytes; 1980 need 163872).
  * 1 <= n_links <= D2D_DEVIATE_MAX_LINKS, 1 <= n_rbs <= D2D_DEVIATE_MAX_RBS, 1 <= pow_k <= 8 with D2D_DEVIATE_LAW_POW_K,
  * n_envs >= 0 (0: nothing to do).  Returns 0, or non-zero with a message in d2d_deviate_last_error().                            */
 #ifndef D2D_DEVIATE_H

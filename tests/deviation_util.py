@@ -54,10 +54,9 @@ def lds_bytes(n, r, allowed=False):
     return 80 * n + (r16(4 * n * ((r + 31) // 32)) if allowed else 0) + r16(4 * ((n + 31) // 32) * r) + 5216
 
 
-@lru_cache(maxsize=None)
-def make_case(name):
-    """The seeded state of a case, in power_control_util's form, with the case's own alphabets."""
-    k = CASES[name]
+def build_case(name, k):
+    """The seeded state of the case dict `k` (a CASES entry, or one in its form) under the seed its name gives, in
+    power_control_util's form, with the case's own alphabets."""
     cues, dues, r = k['cues'], k['dues'], k['r']
     n = cues + dues
     levels = np.array([k['cue_max'] + 1] * cues + [k['due_max'] + 1] * dues)
@@ -76,6 +75,12 @@ def make_case(name):
                            raw=raw.astype(np.int32), rb=rb.astype(np.int32), pwr=pwr.astype(np.int32), tx=tx, rx=rx,
                            p_min=np.zeros_like(levels), p_max=levels - 1, levels=levels, spec=spec, cols=orc.device_columns(*cfgs[1:]),
                            cue_max=k['cue_max'], due_max=k['due_max'])
+
+
+@lru_cache(maxsize=None)
+def make_case(name):
+    """build_case of a CASES entry, computed once."""
+    return build_case(name, CASES[name])
 
 
 def env_config(c):
@@ -251,8 +256,9 @@ def oracle_planes(c, e, rb_rows, pwr_rows):
     return out['sinr_db'], out['capacity_mbps']
 
 
-def by_oracle(c, envs, links, allowed=None, floor=None, min_gain=0.0, rb=None, pwr=None):
-    """The statement on the float64 oracle's planes for the envs `envs` and the links `links` of a case, under one setting.  Returns
+def by_oracle(c, envs, links, allowed=None, floor=None, min_gain=0.0, rb=None, pwr=None, planes=None):
+    """The statement on the float64 oracle's planes for the envs `envs` and the links `links` of a case, under one setting; `planes(c,
+    e, i, rb_rows, pwr_rows)` fills link i's planes of env e in oracle_planes' place (deviation_large_util.restricted_planes).  Returns
     restate()'s namespace with three more fields: near bool [E, M, R, Lmax] (some member of group(r) u {i} has a float64 SINR within
     THRESHOLD_DB of its sensitivity or of its floor in the entry's state, in the held state or with i gone), delta float64 [E, M, R,
     Lmax] (the env's oracle total at s^(r,q) less the total at s, summed over ALL links) and total float64 [E] (the total at s)."""
@@ -264,7 +270,8 @@ def by_oracle(c, envs, links, allowed=None, floor=None, min_gain=0.0, rb=None, p
     kept = {}
 
     def fill(i, rb_rows, pwr_rows):
-        both = [oracle_planes(c, e, rb_rows[x], pwr_rows[x]) for x, e in enumerate(envs)]
+        both = [oracle_planes(c, e, rb_rows[x], pwr_rows[x]) if planes is None else planes(c, e, i, rb_rows[x], pwr_rows[x])
+                for x, e in enumerate(envs)]
         kept[i] = (np.stack([s for s, _ in both]), np.stack([k for _, k in both]))
         return kept[i]
 
